@@ -2,6 +2,14 @@
 """bench.py -- CMLPL training-step throughput on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B2|B3|P|B4|B5] [--global-batch BT+BTU]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (patches/s, ms_per_step).
+`--full` adds what takes runs of its own: the conv1 calibration window and the dominant kernel's hipEvent pair inside
+the timed region (-> `roofline`, `roofline_others`) and the CPU baseline of the oracle (`cpu_baseline`; skipped with
+`--no-cpu-baseline`).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see
+step_outputs / write_outputs); the inputs are seeded, so two builds run with the same arguments can be compared
+array for array.
 
 N > 1 works both ways: typed as above, the parent starts N ranks itself (cmlpl_amd/launch.py: fresh child
 processes with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, before anything touches the GPU) and relays rank 0's
@@ -71,9 +79,16 @@ def parse_args(argv=None):
                          "through the single-GPU engine and the first step's logged scalars must agree (1e-4 relative) "
                          "-- exits non-zero otherwise")
     ap.add_argument("--breakdown", action="store_true", help="print a per-kernel time table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline figures (calibration window, dominant conv1 kernel timed inside the "
+                         "timed region) and, at N = 1, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "B3" and args.global_batch is None:
         args.global_batch = "512+512"
     return args
@@ -102,6 +117,50 @@ def synth(shape, bt, btu, seed, device):
              Y=torch.randint(0, K, (bt,), generator=g),
              XPu=torch.randn(btu, C, H, W, generator=g), Xu=torch.randn(btu, bands, generator=g))
     return {k: v.to(device) for k, v in d.items()}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all arrays together
+DUMP_WHOLE_BYTES = 10 ** 6         # arrays this small are never sampled
+DUMP_SAMPLE_SEED = 1088
+
+
+def step_outputs(eng, scal):
+    """What a caller of the timed path holds after its last step: the logged scalars (engine.SCALAR_NAMES order), both
+    networks' logits and features of the batch ([2][n][..]), the gradients, the parameters after the Adam update and
+    the two memory banks.  On the data-parallel engine outputs() is a collective: every rank calls this."""
+    import numpy as np
+    from cmlpl_amd.engine import SCALAR_NAMES
+    logits, feat = eng.outputs()
+    host = lambda t: t.detach().float().cpu().numpy()
+    return {"scalars": np.array([scal[k] for k in SCALAR_NAMES], dtype=np.float64),
+            "logits": host(logits), "feat": host(feat), "grads": host(eng.grads), "params": host(eng.params),
+            "bank_feats": host(eng.bank_feats), "bank_probs": host(eng.bank_probs)}
+
+
+def write_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES, whole=DUMP_WHOLE_BYTES):
+    """arrays {name: float32 / float64 numpy array} -> out_dir/<name>.npy.  If together they hold more than `limit`
+    bytes, the arrays of at most `whole` bytes (scalars, logits) are still written whole and the larger ones share
+    what is left of the limit, each keeping the same fraction of its elements: a fixed sample of the flattened array
+    at the positions numpy.random.default_rng(DUMP_SAMPLE_SEED).choice(size, k, replace=False), sorted (the same
+    positions in every run with the same arguments).  Returns {name: number of elements written}."""
+    import numpy as np
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {a.dtype}, want float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= whole)
+    if total > limit and small >= limit:
+        raise ValueError(f"the arrays of at most {whole} bytes alone hold {small} bytes, over the limit of {limit}")
+    frac = 1.0 if total <= limit else (limit - small) / (total - small)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        k = a.size if a.nbytes <= whole else int(a.size * frac)
+        if k < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = int(a.size)
+    return written
 
 
 def conv1_flops(shape, n, nets=2):
@@ -312,10 +371,108 @@ def run_rank(args):
 
     run(args.warmup, 0)
     barrier()
-    # Which kernel is the dominant one is decided by measurement: a short calibration window (untimed) brackets
-    # the three conv1 launches with hipEvent pairs on the launch stream; the longest one is then bracketed inside
-    # the timed region (one event pair per step keeps the perturbation of the step time below 1 %).
+    first = args.warmup
+    cal = None
+    if args.full:
+        cal = calibrate_conv1(lib, run, barrier, first)
+        first += CALIB_STEPS
+        _lib.check("cmlpl_timing_begin", lib.cmlpl_timing_begin(1 << cal["dom_id"], args.steps + 8))
+    thr0 = cgroup_throttle()
+    t0 = time.perf_counter()
+    run(args.steps, first)
+    barrier()
+    dt = time.perf_counter() - t0
+    thr1 = cgroup_throttle()
+    if cal is not None:
+        _lib.check("cmlpl_timing_end", lib.cmlpl_timing_end(cal["ms"], cal["cnt"]))
+    if dist is not None:
+        t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    scal = eng.read_scalars()
+    if not all(v == v and abs(v) != float("inf") for v in scal.values()) and not os.environ.get("CMLPL_BENCH_ALLOW_NONFINITE"):   # (ablation builds)
+        raise SystemExit(f"bench.py: non-finite loss after the timed region: {scal}")
+    if args.dump_outputs:       # before anything else runs a step
+        arrays = step_outputs(eng, scal)
+        if rank == 0:
+            write_outputs(arrays, args.dump_outputs)
+
+    n_local = bt + btu
+    patches = n_local * world * args.steps
+    out = {
+        "metric": "HSI patches/sec per training step", "value": patches / dt, "unit": "patches/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f32 (convolutions: f32 operands as 3 exact bf16 pieces on the bf16 MFMA, 6 of 9 piece products, f32 "
+                 "accumulate, per-product worst case 2^-21 -- conv1's tap loops of the per-sample kernels as 2 fp16 pieces with "
+                 "power-of-two operand scales, 3 piece products, worst case 2^-20 / mean 2^-23, falling back to the 3-piece loop "
+                 "outside fp16's range; max-norm error measured at f32 level against f64; everything else f32 MFMA / "
+                 "f32 VALU)", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: synthetic PaviaU-shaped patches {shape[1]}x{shape[2]}x{shape[0]}, "
+                               f"spectrum {shape[3]}, {shape[4]} classes, {bt} labelled + {btu} unlabelled "
+                               f"rows per GPU (batch {n_local}), dual BaseNet2 fwd/bwd + contrastive/mutual losses + "
+                               f"bank + Adam, epoch 1 (memory-bank smoothing active), in-kernel PCG4D noise / Philox dropout",
+                   "global_batch": n_local * world, "parallelism": f"dp{world}",
+                   # how a rank's step is driven at N > 1: one C call with the collectives on RCCL directly, or the stages
+                   # from Python over torch.distributed (the fallback of cmlpl_amd.distributed.pick_comm)
+                   **({"collectives": type(eng.comm).__name__ + (", one C call per step" if eng._native_comm() is not False else ", stages driven from Python")}
+                      if dist is not None else {})},
+    }
+    if cal is not None:
+        out.update(roofline(lib, cal, shape, n_local, args.workload))
+    out.update({
+        "final_losses": {k: scal[k] for k in ("total_s", "total_w", "cls_s", "ctr_s", "con_s")},
+        # A sample whose gradient image is zero everywhere -- an unlabelled row no loss term reaches through the
+        # convolutions, i.e. one under the confidence threshold (train.py:221: 0.999 in the first epochs) -- skips its
+        # data-gradient loops and conv0 weight gradient in the fused backward and is left out of the weight-gradient
+        # launch (exact: zeros times finite operands).  How many of the last step's unlabelled rows were ABOVE the
+        # threshold, per network: the others were skipped.  CMLPL_ZERO_SKIP=0 measures with nothing skipped; the
+        # algorithmic FLOPs of the backward / weight-gradient lines in roofline_others count the skipped rows as done.
+        "backward_zero_images": {"unlabelled_rows": btu * world, "confident_s": scal["n_mask_s"], "confident_w": scal["n_mask_w"]},
+        # did the container's CPU quota freeze this process inside the timed region?  (a throttled period stops every
+        # thread for up to a CFS period, ~100 ms: profiles/r06_stall_rootcause.txt)  null where cpu.stat is not readable
+        "host_throttled": None if thr0 is None or thr1 is None else
+                          {"periods": thr1[0] - thr0[0], "ms": (thr1[1] - thr0[1]) / 1e3},
+    })
+
+    if args.breakdown:     # every rank runs the extra steps (they contain collectives); rank 0 prints
+        import ctypes as C
+        nk = len(_lib.KERNEL_NAMES)
+        ms, cnt = (C.c_double * nk)(), (C.c_int64 * nk)()
+        _lib.check("cmlpl_timing_begin", lib.cmlpl_timing_begin(0xFFFFFFFF, 40 * 24))
+        run(40, first + args.steps)
+        barrier()
+        _lib.check("cmlpl_timing_end", lib.cmlpl_timing_end(ms, cnt))
+        tot = sum(ms[i] for i in range(len(_lib.KERNEL_NAMES)))
+        if rank == 0:
+            print(f"per-kernel device time over 40 steps (hipEvent pairs; sum {tot / 40 * 1e3:.1f} us/step):",
+                  file=sys.stderr)
+            for i, nm in enumerate(_lib.KERNEL_NAMES):
+                if cnt[i]:
+                    print(f"  {nm:12s} {ms[i] / cnt[i] * 1e3:9.1f} us/launch  x{cnt[i] // 40}/step  "
+                          f"{100 * ms[i] / tot:5.1f} %", file=sys.stderr)
+
+    if dist is not None:
+        barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        if args.full:
+            # on rank 0 at N = 1 only; a bounded sample (about 20 s) of the same workload on the host cores
+            out["cpu_baseline"] = cpu_baseline(shape, bt, btu) if (world == 1 and not args.no_cpu_baseline) else None
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(out) + "\n").encode())
+
+
+CALIB_STEPS = 10
+
+
+def calibrate_conv1(lib, run, barrier, first_index):
+    """--full: which conv1 kernel is the dominant one is decided by measurement.  A short calibration window (untimed)
+    brackets the three conv1 launches (and conv0's / conv2's, to see which of them are fused into them) with hipEvent
+    pairs on the launch stream; the longest one is then bracketed inside the timed region (one event pair per step
+    keeps the perturbation of the step time below 1 %)."""
     import ctypes as C
+    from cmlpl_amd import _lib
     nk = len(_lib.KERNEL_NAMES)
     ms = (C.c_double * nk)()
     cnt = (C.c_int64 * nk)()
@@ -325,41 +482,36 @@ def run_rank(args):
     id_conv2f = _lib.KERNEL_NAMES.index("conv2_fwd")
     id_conv2d = _lib.KERNEL_NAMES.index("conv2_dgrad")
     id_conv2w = _lib.KERNEL_NAMES.index("conv2_wgrad")
-    calib_steps = 10
     _lib.check("cmlpl_timing_begin", lib.cmlpl_timing_begin(
         sum(1 << i for i in ids.values()) | (1 << id_conv0) | (1 << id_conv0w) | (1 << id_conv2f) | (1 << id_conv2d) | (1 << id_conv2w),
-        7 * calib_steps + 8))
-    run(calib_steps, args.warmup)
+        7 * CALIB_STEPS + 8))
+    run(CALIB_STEPS, first_index)
     barrier()
     _lib.check("cmlpl_timing_end", lib.cmlpl_timing_end(ms, cnt))
     calib = {k: ms[i] / max(cnt[i], 1) for k, i in ids.items()}
-    # no separate conv0 launch => the forward kernel is the fused conv0 + conv1 one and carries both FLOP counts
-    fused_fwd = cnt[id_conv0] == 0
-    fused_bwd = cnt[id_conv0w] == 0
-    # no separate conv2 launches either => they run in the tails of the fused per-sample kernels
-    tail_fwd = fused_fwd and cnt[id_conv2f] == 0
-    head_bwd = fused_bwd and cnt[id_conv2d] == 0
-    wgrad_pair = cnt[id_conv2w] == 0        # conv2's weight gradient rides in conv1's launch
     dom_name = max(calib, key=calib.get)
-    dom_id = ids[dom_name]
-    _lib.check("cmlpl_timing_begin", lib.cmlpl_timing_begin(1 << dom_id, args.steps + 8))
-    thr0 = cgroup_throttle()
-    t0 = time.perf_counter()
-    run(args.steps, args.warmup + calib_steps)
-    barrier()
-    dt = time.perf_counter() - t0
-    thr1 = cgroup_throttle()
-    _lib.check("cmlpl_timing_end", lib.cmlpl_timing_end(ms, cnt))
-    if dist is not None:
-        t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    scal = eng.read_scalars()
-    if not all(v == v and abs(v) != float("inf") for v in scal.values()) and not os.environ.get("CMLPL_BENCH_ALLOW_NONFINITE"):   # (ablation builds)
-        raise SystemExit(f"bench.py: non-finite loss after the timed region: {scal}")
+    return {
+        "calib": calib, "dom_name": dom_name, "dom_id": ids[dom_name],
+        # no separate conv0 launch => the forward kernel is the fused conv0 + conv1 one and carries both FLOP counts
+        "fused_fwd": cnt[id_conv0] == 0,
+        "fused_bwd": cnt[id_conv0w] == 0,
+        # no separate conv2 launches either => they run in the tails of the fused per-sample kernels
+        "tail_fwd": cnt[id_conv0] == 0 and cnt[id_conv2f] == 0,
+        "head_bwd": cnt[id_conv0w] == 0 and cnt[id_conv2d] == 0,
+        "wgrad_pair": cnt[id_conv2w] == 0,        # conv2's weight gradient rides in conv1's launch
+        # the timed region's event pairs land here (cmlpl_timing_end after the timed steps)
+        "ms": ms, "cnt": cnt,
+    }
 
-    n_local = bt + btu
-    patches = n_local * world * args.steps
+
+def roofline(lib, cal, shape, n_local, workload):
+    """--full: the `roofline` (dominant conv1 kernel, timed inside the timed region) and `roofline_others` (the other two,
+    from the calibration window) fields of the result line."""
+    import ctypes as C
+    from cmlpl_amd import _lib
+    calib, dom_name, dom_id, ms, cnt = cal["calib"], cal["dom_name"], cal["dom_id"], cal["ms"], cal["cnt"]
+    fused_fwd, fused_bwd, tail_fwd, head_bwd, wgrad_pair = (cal[k] for k in ("fused_fwd", "fused_bwd", "tail_fwd",
+                                                                              "head_bwd", "wgrad_pair"))
     dom_ms = ms[dom_id] / max(cnt[dom_id], 1)
     wgrad_split = os.environ.get("CMLPL_WGRAD3_B3", "1") != "0"
     c1 = conv1_flops(shape, n_local)
@@ -415,27 +567,10 @@ def run_rank(args):
                                  (", two-piece fp16 planes)" if wgrad_split and (tp & 4) else ")"))
     kflops = {k: sum(v.values()) for k, v in kseg.items()}
     kpeak = {k: blended_peak(v) for k, v in kseg.items()}
-    traffic, traffic_src = recorded_traffic(args.workload, n_local)
+    traffic, traffic_src = recorded_traffic(workload, n_local)
     flops = kflops[dom_name]
     achieved = flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-    out = {
-        "metric": "HSI patches/sec per training step", "value": patches / dt, "unit": "patches/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "f32 (convolutions: f32 operands as 3 exact bf16 pieces on the bf16 MFMA, 6 of 9 piece products, f32 "
-                 "accumulate, per-product worst case 2^-21 -- conv1's tap loops of the per-sample kernels as 2 fp16 pieces with "
-                 "power-of-two operand scales, 3 piece products, worst case 2^-20 / mean 2^-23, falling back to the 3-piece loop "
-                 "outside fp16's range; max-norm error measured at f32 level against f64; everything else f32 MFMA / "
-                 "f32 VALU)", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: synthetic PaviaU-shaped patches {shape[1]}x{shape[2]}x{shape[0]}, "
-                               f"spectrum {shape[3]}, {shape[4]} classes, {bt} labelled + {btu} unlabelled "
-                               f"rows per GPU (batch {n_local}), dual BaseNet2 fwd/bwd + contrastive/mutual losses + "
-                               f"bank + Adam, epoch 1 (memory-bank smoothing active), in-kernel PCG4D noise / Philox dropout",
-                   "global_batch": n_local * world, "parallelism": f"dp{world}",
-                   # how a rank's step is driven at N > 1: one C call with the collectives on RCCL directly, or the stages
-                   # from Python over torch.distributed (the fallback of cmlpl_amd.distributed.pick_comm)
-                   **({"collectives": type(eng.comm).__name__ + (", one C call per step" if eng._native_comm() is not False else ", stages driven from Python")}
-                      if dist is not None else {})},
+    return {
         "roofline": {"bound": "mfma", "kernel": labels[dom_name],
                      "achieved": achieved, "peak": kpeak[dom_name], "unit": "TFLOP/s",
                      "frac": achieved / kpeak[dom_name],
@@ -454,48 +589,13 @@ def run_rank(args):
                      "flops_per_launch": flops, "ms_per_launch": dom_ms, "launches_timed": int(cnt[dom_id])},
         # the other two conv1 kernels (same algorithmic FLOPs), from the calibration window
         "roofline_others": [
-            {"kernel": labels[k], "ms_per_launch": calib[k], "launches_timed": calib_steps,
+            {"kernel": labels[k], "ms_per_launch": calib[k], "launches_timed": CALIB_STEPS,
              "flops_per_launch": kflops[k], "flops_by_mfma_kind": kseg[k], "peak": kpeak[k],
              "achieved": kflops[k] / (calib[k] * 1e-3) / 1e12 if calib[k] > 0 else 0.0,
              "frac": (kflops[k] / (calib[k] * 1e-3) / 1e12 / kpeak[k]) if calib[k] > 0 else 0.0,
              "traffic": traffic.get(k)}
             for k in CONV1_KERNELS if k != dom_name],
-        "final_losses": {k: scal[k] for k in ("total_s", "total_w", "cls_s", "ctr_s", "con_s")},
-        # A sample whose gradient image is zero everywhere -- an unlabelled row no loss term reaches through the
-        # convolutions, i.e. one under the confidence threshold (train.py:221: 0.999 in the first epochs) -- skips its
-        # data-gradient loops and conv0 weight gradient in the fused backward and is left out of the weight-gradient
-        # launch (exact: zeros times finite operands).  How many of the last step's unlabelled rows were ABOVE the
-        # threshold, per network: the others were skipped.  CMLPL_ZERO_SKIP=0 measures with nothing skipped; the
-        # algorithmic FLOPs of the backward / weight-gradient lines in roofline_others count the skipped rows as done.
-        "backward_zero_images": {"unlabelled_rows": btu * world, "confident_s": scal["n_mask_s"], "confident_w": scal["n_mask_w"]},
-        # did the container's CPU quota freeze this process inside the timed region?  (a throttled period stops every
-        # thread for up to a CFS period, ~100 ms: profiles/r06_stall_rootcause.txt)  null where cpu.stat is not readable
-        "host_throttled": None if thr0 is None or thr1 is None else
-                          {"periods": thr1[0] - thr0[0], "ms": (thr1[1] - thr0[1]) / 1e3},
     }
-
-    if args.breakdown:     # every rank runs the extra steps (they contain collectives); rank 0 prints
-        _lib.check("cmlpl_timing_begin", lib.cmlpl_timing_begin(0xFFFFFFFF, 40 * 24))
-        run(40, args.warmup + calib_steps + args.steps)
-        barrier()
-        _lib.check("cmlpl_timing_end", lib.cmlpl_timing_end(ms, cnt))
-        tot = sum(ms[i] for i in range(len(_lib.KERNEL_NAMES)))
-        if rank == 0:
-            print(f"per-kernel device time over 40 steps (hipEvent pairs; sum {tot / 40 * 1e3:.1f} us/step):",
-                  file=sys.stderr)
-            for i, nm in enumerate(_lib.KERNEL_NAMES):
-                if cnt[i]:
-                    print(f"  {nm:12s} {ms[i] / cnt[i] * 1e3:9.1f} us/launch  x{cnt[i] // 40}/step  "
-                          f"{100 * ms[i] / tot:5.1f} %", file=sys.stderr)
-
-    if dist is not None:
-        barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        # on rank 0 at N = 1 only; a bounded sample (about 20 s) of the same workload on the host cores
-        out["cpu_baseline"] = cpu_baseline(shape, bt, btu) if (world == 1 and not args.no_cpu_baseline) else None
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
 
 def cgroup_throttle():

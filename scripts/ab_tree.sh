@@ -7,6 +7,6 @@ for i in $(seq 1 $REPS); do
   for cfg in "$@"; do
     IFS='|' read -r name envs dir <<< "$cfg"
     echo -n "$name: "
-    (cd $ROOT/$dir && env $envs python bench.py --steps 200 --no-cpu-baseline $ARGS 2>/dev/null) | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; o=d['roofline_others']; print('%.4f ms/step  dom %.1f us  others %s' % (d['ms_per_step'], r['ms_per_launch']*1e3, ' '.join('%.1f' % (x['ms_per_launch']*1e3) for x in o)))" || echo failed
+    (cd $ROOT/$dir && env $envs python bench.py --steps 200 --full --no-cpu-baseline $ARGS 2>/dev/null) | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; o=d['roofline_others']; print('%.4f ms/step  dom %.1f us  others %s' % (d['ms_per_step'], r['ms_per_launch']*1e3, ' '.join('%.1f' % (x['ms_per_launch']*1e3) for x in o)))" || echo failed
   done
 done

@@ -21,4 +21,4 @@ python3 scripts/pmc_summary.py $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write --jso
 python3 scripts/pmc_sq_summary.py $OUT/${TAG}_pmc_sq $OUT/${TAG}_pmc_sq2 > $OUT/${TAG}_pmc_mfma.txt || true
 # the traffic record bench.py quotes (it carries the source hash): in place before the bench line of this round is taken
 [ "$WL" = B2 ] && cp $OUT/${TAG}_pmc_traffic.json profiles/pmc_traffic.json
-python3 bench.py --workload $WL --steps 200 > $OUT/${TAG}_bench.json 2> /dev/null
+python3 bench.py --workload $WL --steps 200 --full > $OUT/${TAG}_bench.json 2> /dev/null

@@ -1,6 +1,7 @@
 """bench.py prints exactly ONE JSON line on stdout with the fields the driver reads (task contract): metric / value /
 unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
-config.workload, plus `roofline` and `cpu_baseline`."""
+config.workload; with --full also `roofline` and `cpu_baseline`.  A plain run carries the headline only and
+--dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -13,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "3", "--no-cpu-baseline"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "3", "--no-cpu-baseline",
+                        "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -43,6 +44,48 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert rf["traffic"] is None or rf["traffic"] > 1e6     # null when the kernels changed since the recorded PMC pass
     assert len(d["roofline_others"]) == 2
     assert all(v == v for v in d["final_losses"].values())                               # finite
+
+
+def _plain_run_with_dump(dump, steps, warmup):
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: warm-up, the timed steps and the headline line (no calibration window, roofline or CPU baseline);
+    --dump-outputs writes the arrays of the last timed step as float32 / float64 .npy files, 64 MB at most.  Warm-up 2 +
+    7 timed steps and warm-up 3 + 6 run the same nine steps (batch indices 0..8), so their dumps agree bit for bit;
+    warm-up 2 + 6 stops one step earlier and its dump differs: the files hold the state after the last timed step."""
+    import numpy as np
+    from cmlpl_amd.engine import SCALAR_NAMES
+    d = _plain_run_with_dump(tmp_path / "w2s7", 7, 2)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["unit"] == "patches/s" and d["steps"] == 7 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 1000.0 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert not {"roofline", "roofline_others", "cpu_baseline"} & set(d)
+    names = ("scalars", "logits", "feat", "grads", "params", "bank_feats", "bank_probs")
+    load = lambda dump: {n: np.load(dump / (n + ".npy")) for n in names}
+    dump = tmp_path / "w2s7"
+    assert sorted(p.name for p in dump.iterdir()) == sorted(n + ".npy" for n in names)
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 * 10 ** 6
+    a = load(dump)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["logits"].shape == (2, 256, 9) and a["feat"].shape == (2, 256, 1024)
+    sc = dict(zip(SCALAR_NAMES, a["scalars"].tolist()))
+    assert all(sc[k] == v for k, v in d["final_losses"].items())       # scalars.npy is in SCALAR_NAMES order
+    _plain_run_with_dump(tmp_path / "w3s6", 6, 3)
+    same = load(tmp_path / "w3s6")
+    for n in names:
+        assert np.array_equal(a[n], same[n]), n                         # the same nine steps
+    _plain_run_with_dump(tmp_path / "w2s6", 6, 2)
+    early = load(tmp_path / "w2s6")
+    for n in ("scalars", "logits", "feat", "grads", "params", "bank_feats"):
+        assert not np.array_equal(a[n], early[n]), n                    # one step fewer
 
 
 def _run_bench_ranks(args, env, timeout):
@@ -88,7 +131,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, CMLPL_ONE_GPU="1", CMLPL_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = _run_bench_ranks(["--gpus", "2", "--steps", "8", "--warmup", "2", "--workload", "B3"], env, 900)
+    r = _run_bench_ranks(["--gpus", "2", "--steps", "8", "--warmup", "2", "--workload", "B3", "--full"], env, 900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines

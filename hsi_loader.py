@@ -3,7 +3,12 @@ item tuples -- (XP f32[C,w,w], X f32[bands], Y int) for 'label' / 'unlabel' / 't
 'wholeset' -- read from the ``.npy`` files ``sample_generation.py`` writes.  ``SyntheticHSIDataSet``
 serves N(0,1) patches of any window shape when the datasets are not on disk (they are not shipped).
 ``device_arrays()`` hands the whole split to the GPU once: the training driver keeps it resident in
-HBM and gathers batches by index there instead of copying 24.6 MB over PCIe per step."""
+HBM and gathers batches by index there instead of copying 24.6 MB over PCIe per step.
+A directory that this repository's ``sample_generation.py`` wrote has no XP.npy but ``cube.npy`` + ``scene.json``: the
+windows are then cut from the cube (``CubeWindows``), with the same item tuples."""
+import json
+import os
+
 import numpy as np
 import torch
 from torch.utils import data
@@ -18,13 +23,66 @@ def _tile_to(arr, max_iters):
     return np.concatenate(parts) if parts else arr[:0]
 
 
+def _mirror(i, n):
+    """MirrowCut's reflection (tools/hyper_tools.py:35-55) of indices at most n outside [0, n)"""
+    return np.where(i < 0, -i - 1, np.where(i >= n, 2 * n - 1 - i, i))
+
+
+def _scene_meta(root):
+    path = root + 'scene.json'
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        return json.load(f)
+
+
+class CubeWindows:
+    """The w x w windows of the pixels ``idx`` (row-major pixel numbers) of a scene cube [rows, cols, C], cut on demand
+    through the mirror index as tools/hyper_tools.py:226-243 ExtractPatches cuts them: stands where the rows of XP.npy
+    stood.  ``shape`` is theirs, [n, C, w, w]; item i is the float32 window [C, w, w] of pixel idx[i]."""
+
+    def __init__(self, cube, w, idx):
+        self.cube, self.w, self.idx = cube, int(w), np.asarray(idx, dtype=np.int64)
+        self.shape = (len(self.idx), cube.shape[2], self.w, self.w)
+
+    def __len__(self):
+        return len(self.idx)
+
+    def cut(self, idx):
+        """windows [len(idx), C, w, w] of the pixels idx, on the host"""
+        rows, cols, _ = self.cube.shape
+        r, c = np.divmod(np.asarray(idx, dtype=np.int64), cols)
+        off = np.arange(self.w) - self.w // 2
+        ri = _mirror(r[:, None] + off, rows)
+        ci = _mirror(c[:, None] + off, cols)
+        return np.moveaxis(np.asarray(self.cube[ri[:, :, None], ci[:, None, :]], dtype=np.float32), 3, 1)
+
+    def __getitem__(self, index):
+        return self.cut(self.idx[[index]])[0]
+
+    def device_tensor(self, device):
+        """all windows as one tensor on ``device``: ONE cmlpl_extract_patches call on a GPU"""
+        device = torch.device(device)
+        if device.type != 'cuda' or len(self.idx) == 0:
+            return torch.from_numpy(self.cut(self.idx)).to(device)
+        from cmlpl_amd.patches import extract_patches
+        cube = torch.from_numpy(np.ascontiguousarray(self.cube, dtype=np.float32)).to(device)
+        return extract_patches(cube, torch.from_numpy(self.idx).to(device), self.w)
+
+
 class HSIDataSet(data.Dataset):
     def __init__(self, dataID, setindex='label', max_iters=None, num_unlabel=1000, root=None):
         self.setindex = setindex
         self.root = root or _ROOTS[int(dataID)]
-        XP = np.load(self.root + 'XP.npy', mmap_mode='r')
         X = np.load(self.root + 'X.npy', mmap_mode='r')
         Y = np.load(self.root + 'Y.npy') - 1
+        if os.path.exists(self.root + 'XP.npy'):
+            XP = np.load(self.root + 'XP.npy', mmap_mode='r')
+        else:
+            meta = _scene_meta(self.root)
+            if meta is None:
+                raise FileNotFoundError(f"{self.root}: neither XP.npy nor cube.npy + scene.json (sample_generation.py)")
+            XP = CubeWindows(np.load(self.root + 'cube.npy', mmap_mode='r'), meta['w'], np.arange(len(X)))
         if setindex == 'wholeset':
             self.XP, self.X, self.Y = XP, X, None
             return
@@ -32,6 +90,11 @@ class HSIDataSet(data.Dataset):
         idx = np.load(self.root + fname)
         if setindex == 'unlabel':
             idx = idx[:num_unlabel]
+        if isinstance(XP, CubeWindows):
+            if max_iters is not None and setindex in ('label', 'unlabel'):
+                idx = _tile_to(idx, max_iters)
+            self.XP, self.X, self.Y = CubeWindows(XP.cube, XP.w, idx), np.asarray(X[idx]), Y[idx]
+            return
         self.XP, self.X, self.Y = np.asarray(XP[idx]), np.asarray(X[idx]), Y[idx]
         if max_iters is not None and setindex in ('label', 'unlabel'):
             self.XP, self.X, self.Y = (_tile_to(a, max_iters) for a in (self.XP, self.X, self.Y))
@@ -47,7 +110,10 @@ class HSIDataSet(data.Dataset):
         return XP, X, int(self.Y[index])
 
     def device_arrays(self, device):
-        XP = torch.from_numpy(np.ascontiguousarray(self.XP, dtype=np.float32)).to(device)
+        if isinstance(self.XP, CubeWindows):
+            XP = self.XP.device_tensor(device)
+        else:
+            XP = torch.from_numpy(np.ascontiguousarray(self.XP, dtype=np.float32)).to(device)
         X = torch.from_numpy(np.ascontiguousarray(self.X, dtype=np.float32)).to(device)
         Y = None if self.Y is None else torch.from_numpy(np.asarray(self.Y, dtype=np.int64)).to(device)
         return XP, X, Y
@@ -55,10 +121,10 @@ class HSIDataSet(data.Dataset):
     def cube_source(self, device, scene=None, dataID=None):
         """The 'wholeset' as the scene it was cut from, for whole-image inference without the materialised patches
         (tools.hyper_tools.test_whole): ``cube.npy`` ([rows, cols, C], the z-scored / PCA'd scene the patches were cut
-        from -- INTEGRATION.md says which line of the reference's preprocessing has it in hand) next to XP.npy.  None
+        from: this repository's sample_generation.py writes it, with scene.json) next to XP.npy or in its place.  None
         when it is not there (the caller then streams the materialised patches, as the reference does): the cube is
-        NOT rebuilt from XP.npy -- that gather touches every page of a ~20 GB file to recover 0.25 % of it."""
-        import os
+        NOT rebuilt from XP.npy -- that gather touches every page of a ~20 GB file to recover 0.25 % of it.  The scene
+        shape comes from scene.json when there is one (then any scene is taken), else from ``_SCENES``."""
         from cmlpl_amd.infer import CubeSource
         if self.setindex != 'wholeset':
             raise ValueError("cube_source() is for the 'wholeset'")
@@ -66,7 +132,10 @@ class HSIDataSet(data.Dataset):
         if not os.path.exists(path):
             return None
         cube = np.load(path, mmap_mode='r')
-        if scene is None and dataID is not None:
+        meta = _scene_meta(self.root)
+        if scene is None and meta is not None:
+            scene = (int(meta['rows']), int(meta['cols']))
+        elif scene is None and dataID is not None:
             scene = _SCENES.get(int(dataID))
         if cube.ndim != 3 or (scene is not None and tuple(cube.shape[:2]) != tuple(scene)):
             return None

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CMLPL_ABI_VERSION 4
+#define CMLPL_ABI_VERSION 5
 #define CMLPL_FEAT_DIM 1024 /* tools/models.py:119 */
 #define CMLPL_CONV_CH 64    /* tools/models.py:102-107 */
 
@@ -452,6 +452,28 @@ size_t cmlpl_infer_workspace_bytes(const cmlpl_shape* shape, int n);
 int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
                      int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
                      float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
+ * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
+ * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the
+ * kernels), bands <= 256, pixels >= 2.  Two calls with the host between them:
+ *   cmlpl_scene_gram:    d_mean [bands] = mean over the pixels; d_gram [bands][bands] = (X - mean)^T (X - mean)
+ *                        (np.cov of the reference's PCANorm is d_gram / (pixels - 1));
+ *   -- the caller takes U = svd(d_gram / (pixels - 1))[0] on the host (the reference's LAPACK call, so its signs) --
+ *   cmlpl_scene_project: P = (X - mean) d_basis, d_basis = U[:, :n_pc] [bands][n_pc] row-major fp64;
+ *                        d_cube [pixels][n_pc] f32 = fp32((P - mean(P)) / std(P)) per component (featureNormalize(., 1),
+ *                        population std); d_spectra [pixels][bands] fp64 = (X - mean) / std(X) (optional: NULL = not
+ *                        written), std(X)_b = sqrt(d_gram[b][b] / pixels).
+ * Both products on v_mfma_f64_16x16x4_f64.  Deterministic: fixed pixel chunks, partials folded in a fixed order, no
+ * atomics -- the same scene gives a bit-identical cube on every run and device, whatever its dtype holds the values.
+ * Workspace: cmlpl_scene_workspace_bytes(pixels, bands, n_pc) covers both calls (0: a shape the calls do not take). */
+enum { CMLPL_SCENE_U16 = 0, CMLPL_SCENE_I16 = 1, CMLPL_SCENE_F32 = 2, CMLPL_SCENE_F64 = 3 };
+size_t cmlpl_scene_workspace_bytes(int64_t pixels, int bands, int n_pc);
+int cmlpl_scene_gram(const void* d_raw, int dtype, int64_t pixels, int bands, double* d_mean, double* d_gram,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+int cmlpl_scene_project(const void* d_raw, int dtype, int64_t pixels, int bands, const double* d_mean,
+                        const double* d_gram, const double* d_basis, int n_pc, float* d_cube, double* d_spectra,
+                        void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Caller-side row N4: tools.models.ContrastiveLoss (tools/models.py:14-39) -- NT-Xent over the
  * pairwise cosine similarity of the 2B normalised embeddings, forward + analytic backward.

@@ -11,7 +11,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMLPL_LIB") or os.path.join(HERE, "libcmlpl_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 NUM_TENSORS = 16
 NUM_LIVE = 10
 
@@ -39,7 +39,7 @@ EXPORTS = (
 
 KERNEL_NAMES = ("augment", "conv0_fwd", "conv1_fwd", "conv2_fwd", "spe_fwd", "head_fwd", "loss", "head_bwd",
                 "cls_wgrad", "spe_wgrad", "conv2_dgrad", "conv2_wgrad", "conv2_wred", "conv1_dgrad", "conv1_wgrad",
-                "conv1_wred", "conv0_wgrad", "adam", "pack", "loss_graph", "loss_fin", "loss_dfeat")
+                "conv1_wred", "conv0_wgrad", "adam", "pack", "loss_graph", "loss_fin", "loss_dfeat", "cube_feed")
 
 
 class CmlplLibraryError(RuntimeError):
@@ -77,7 +77,10 @@ class Shard(C.Structure):
 class Batch(C.Structure):
     _fields_ = [("d_xpl", C.c_void_p), ("d_xl", C.c_void_p), ("d_xpu", C.c_void_p), ("d_xu", C.c_void_p),
                 ("d_labels", C.c_void_p), ("noise8", C.POINTER(C.c_void_p)), ("bt", C.c_int32), ("btu", C.c_int32),
-                ("d_lab_idx", C.c_void_p), ("d_unl_idx", C.c_void_p)]
+                ("d_lab_idx", C.c_void_p), ("d_unl_idx", C.c_void_p),
+                # ABI 6: the cube-fed batch (d_cube set: d_xpl / d_xpu null, windows gathered from the scene in the step)
+                ("d_cube", C.c_void_p), ("cube_rows", C.c_int32), ("cube_cols", C.c_int32),
+                ("d_lab_pix", C.c_void_p), ("d_unl_pix", C.c_void_p)]
 
 
 class Dyn(C.Structure):
@@ -128,6 +131,8 @@ class StepIO(C.Structure):
         ("adam_t", C.c_int64), ("seed", C.c_uint64), ("step", C.c_uint64),
         ("apply_update", C.c_int32), ("reserved", C.c_int32),
         ("d_lab_idx", C.c_void_p), ("d_unl_idx", C.c_void_p), ("d_dyn_table", C.c_void_p), ("d_dyn_cursor", C.c_void_p),
+        ("d_cube", C.c_void_p), ("cube_rows", C.c_int32), ("cube_cols", C.c_int32),       # ABI 6, as in Batch
+        ("d_lab_pix", C.c_void_p), ("d_unl_pix", C.c_void_p),
     ]
 
 

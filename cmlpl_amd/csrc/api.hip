@@ -487,8 +487,14 @@ int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
 bool need_xn_copy(const Dims& d, int rows) {
   return !(conv3_fused_ok(d.H, d.W, d.C, rows) && conv3_fused_bwd_ok(d.H, d.W, d.C, rows));
 }
-bool check_batch(const cmlpl_batch* b) {
-  return b && b->bt >= 1 && b->btu >= 1 && b->d_xpl && b->d_xl && b->d_xpu && b->d_xu;
+// 0, or the error of a malformed batch.  Split-fed (d_cube null): the four row buffers.  Cube-fed (ABI 6): the scene, its
+// two pixel lists and NO window buffers; a square window no larger than the scene that fits the gather's LDS tile.
+int check_batch(const Dims& d, const cmlpl_batch* b) {
+  if (!b || b->bt < 1 || b->btu < 1 || !b->d_xl || !b->d_xu) return CMLPL_E_ARG;
+  if (b->d_cube == nullptr) return (b->d_xpl && b->d_xpu) ? 0 : CMLPL_E_ARG;
+  if (b->d_xpl || b->d_xpu || !b->d_lab_pix || !b->d_unl_pix || b->cube_rows < 1 || b->cube_cols < 1) return CMLPL_E_ARG;
+  if (d.H != d.W || b->cube_rows < d.H || b->cube_cols < d.W || cube_feed_lds(d.C, d.W) > LDS_MAX) return CMLPL_E_SHAPE;
+  return 0;
 }
 }  // namespace
 
@@ -503,9 +509,10 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
   // in two parts (the sharded step) the spectral part forms the embeddings itself: early_feat
   const bool early_feat = parts != 3;
-  if (!hp || !check_batch(batch) || !d_params || !d_workspace || ((parts & 2) && (!d_packed || !d_logits)) ||
+  if (!hp || !d_params || !d_workspace || ((parts & 2) && (!d_packed || !d_logits)) ||
       ((parts & 1 || !early_feat) && !d_feat))
     return CMLPL_E_ARG;
+  if (int brc = check_batch(d, batch)) return brc;
   if (d_labels_f && !batch->d_labels) return CMLPL_E_ARG;
   if (hp->dropout_p < 0.f || hp->dropout_p >= 1.f) return CMLPL_E_ARG;
   const int n = batch->bt + batch->btu;
@@ -526,7 +533,9 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
   // (general path: the augmentation of the patches rides in conv0's launch where conv0a_fwd_kernel takes the window; it
   //  leaves the augmented rows in sw.xn like the fused forward does)
   const bool c0a = copy && !conv3_fused_ok(d.H, d.W, d.C, 2 * n) && conv0a_ok(d.C, d.HW);
-  const int which = ((parts & 2) && copy && !c0a ? 1 : 0) | ((parts & 1) && !spe_fused ? 2 : 0);
+  // (cube-fed batch: the patches' augmented rows come from the gather launch below, whatever the path)
+  const bool cube = batch->d_cube != nullptr;
+  const int which = ((parts & 2) && copy && !c0a && !cube ? 1 : 0) | ((parts & 1) && !spe_fused ? 2 : 0);
   if (!(parts & 1)) d_labels_f = nullptr;     // (the labels travel with the spectral part)
   const RowSel sel = batch_sel(batch, dyn);
   if (which &&
@@ -539,6 +548,20 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
     xspec.lab[i] = batch->d_xl; xspec.unl[i] = batch->d_xu;
     xspec.nz_lab[i] = batch->noise8 ? batch->noise8[2 * i + 1] : nullptr;
     xspec.nz_unl[i] = batch->noise8 ? batch->noise8[4 + 2 * i + 1] : nullptr;
+  }
+  if (cube) {
+    // the windows are gathered from the scene and augmented into sw.xn -- the rows the backward reads -- and the forward
+    // runs on them as plain rows by batch row (no noise, no index lists: both are spent) without writing them again
+    if ((parts & 2) &&
+        (rc = TIMED(CMLPL_K_CUBE_FEED, chk(launch_cube_feed(batch->d_cube, batch->cube_rows, batch->cube_cols, d.C, d.W,
+                                  (const long long*)batch->d_lab_pix, (const long long*)batch->d_unl_pix, batch->bt,
+                                  batch->btu, lab0, unl_base, batch->noise8, hp->noise_sigma, seed, step, sw.xn, &sel,
+                                  st))))) return rc;
+    return fwd_core(d, L, 2, n, d_params, L.param_total, d_packed,
+                    xsrc_plain(sw.xn, 2, n, (long long)d.C * d.HW, seed, step, shard, dyn),
+                    spe_fused ? &xspec : nullptr, sw.sn, (const long long*)batch->d_labels, d_labels_f, sw.xn, sw.sn,
+                    nullptr, d_dropmask, hp->dropout_p, train, seed, step, shard, d_logits, d_feat, nw, st, nullptr, parts,
+                    early_feat);
   }
   // (fused per-sample kernels: the forward leaves the rows it saw in sw.xn for cmlpl_backward, which lands them by DMA)
   return fwd_core(d, L, 2, n, d_params, L.param_total, d_packed, xsrc_raw(batch, hp->noise_sigma, seed, step, shard, dyn),
@@ -608,8 +631,9 @@ int backward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl
   Dims d;
   cmlpl_layout_t L;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
-  if (!hp || !check_batch(batch) || !d_params || !d_packed || !d_dlogits || ((parts & 2) && !d_grads) || !d_workspace)
+  if (!hp || !d_params || !d_packed || !d_dlogits || ((parts & 2) && !d_grads) || !d_workspace)
     return CMLPL_E_ARG;
+  if (int brc = check_batch(d, batch)) return brc;
   const int n = batch->bt + batch->btu;
   NetWs nw;
   if (!carve_net(d, 2, n, (char*)d_workspace, &nw)) return CMLPL_E_SHAPE;
@@ -854,7 +878,8 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
   dyn.table = io->d_dyn_table; dyn.cursor = io->d_dyn_cursor;
   const cmlpl_shard sh = {io->bt, io->btu, 0, io->bt, 0, io->btu};
   const cmlpl_batch batch = {io->d_xpl, io->d_xl, io->d_xpu, io->d_xu, io->d_labels, io->noise8, io->bt, io->btu,
-                             io->d_lab_idx, io->d_unl_idx};
+                             io->d_lab_idx, io->d_unl_idx, io->d_cube, io->cube_rows, io->cube_cols, io->d_lab_pix,
+                             io->d_unl_pix};
   if ((rc = forward_impl(shape, hp, &batch, &sh, io->d_params, io->d_packed, io->d_dropmask, train, io->seed,
                          io->step, io->d_logits, io->d_feat, nullptr, io->d_workspace, io->workspace_bytes, stream, dyn)))
     return rc;

@@ -89,6 +89,13 @@ hipError_t launch_dist_unpack(const float* recv_f, const float* recv_z, int W, i
 hipError_t launch_extract_patches(const float* cube, int rows, int cols, int C, int w, const long long* idx, int n,
                                   float* out, hipStream_t st);
 
+// ---- cube_feed.hip: augmented patch rows of both networks gathered from the scene cube (the cube-fed step)
+size_t cube_feed_lds(int C, int w);
+hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w, const long long* lab_pix,
+                            const long long* unl_pix, int bt, int btu, int lab0, int unl_base,
+                            const float* const* noise8, float sigma, uint64_t seed, uint64_t step, float* xn,
+                            const RowSel* sel, hipStream_t st);
+
 // ---- conv3x3.hip
 hipError_t launch_pack_weights(int nets, const float* params, long long pstride, const PackInfo& pi, float* packed,
                                hipStream_t st);

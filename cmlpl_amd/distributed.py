@@ -339,6 +339,18 @@ def drive_step(engine, comm, *fwd_args, **fwd_kw) -> None:
     assert not pending, f"exchanges never waited for: {sorted(pending)}"
 
 
+def _fill_batch(b, XPl, Xl, Y, XPu, Xu, cube=None, lab_pix=None, unl_pix=None) -> None:
+    """the row sources of a cmlpl_batch record: the window tensors, or (cube-fed) the scene and its two pixel lists"""
+    b.d_xl, b.d_xu, b.d_labels = Xl.data_ptr(), Xu.data_ptr(), Y.data_ptr()
+    if cube is None:
+        b.d_xpl, b.d_xpu = XPl.data_ptr(), XPu.data_ptr()
+        b.d_cube, b.d_lab_pix, b.d_unl_pix, b.cube_rows, b.cube_cols = None, None, None, 0, 0
+    else:
+        b.d_xpl, b.d_xpu = None, None
+        b.d_cube, b.d_lab_pix, b.d_unl_pix = cube.data_ptr(), lab_pix.data_ptr(), unl_pix.data_ptr()
+        b.cube_rows, b.cube_cols = cube.shape[0], cube.shape[1]
+
+
 class DistTrainEngine(TrainEngine):
     """TrainEngine whose step is sharded by sample over ``comm.world`` ranks.  Batch sizes given to
     the constructor are PER RANK (the largest shard a step may bring); banks are sized from the global
@@ -485,7 +497,7 @@ class DistTrainEngine(TrainEngine):
 
     # ------------------------------------------------------------------ stages (no communication inside)
     def _begin_step(self, XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise=None, dropmask=None, apply_update=True,
-                    lab_idx=None, unl_idx=None):
+                    lab_idx=None, unl_idx=None, cube=None, lab_pix=None, unl_pix=None):
         """checks, the shard's views, and what changes from step to step written into the kept ctypes cells"""
         s = self.shape
         g = self._graph() if self._graph is not None else None
@@ -493,7 +505,14 @@ class DistTrainEngine(TrainEngine):
             raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them (or program() anew) "
                                "before an eager step")
         # (lab_idx / unl_idx: THIS rank's rows as indices into the resident splits, see TrainEngine.step)
-        bt_l, btu_l = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        # (cube / lab_pix / unl_pix: the cube-fed step, XPl = XPu = None -- see TrainEngine.step)
+        cube_fed = cube is not None or lab_pix is not None or unl_pix is not None
+        if cube_fed:
+            if XPl is not None or XPu is not None:
+                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
+            bt_l, btu_l = self._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx)
+        else:
+            bt_l, btu_l = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
         if btu_l > self.btu_max:
             raise ValueError(f"shard {bt_l}+{btu_l} outside the engine's capacity {self.bt_max}+{self.btu_max} per rank")
         if self.Q < (bt_l + btu_l) * self.world:
@@ -513,7 +532,7 @@ class DistTrainEngine(TrainEngine):
             self._stage_args()
         c = self._cells
         b = c["batch"]          # (updated in place: the stage calls hold a reference to this record)
-        b.d_xpl, b.d_xl, b.d_xpu, b.d_xu, b.d_labels = XPl.data_ptr(), Xl.data_ptr(), XPu.data_ptr(), Xu.data_ptr(), Y.data_ptr()
+        _fill_batch(b, XPl, Xl, Y, XPu, Xu, cube, lab_pix, unl_pix)
         b.noise8, b.bt, b.btu = noise8, bt_l, btu_l
         b.d_lab_idx = None if lab_idx is None else lab_idx.data_ptr()
         b.d_unl_idx = None if unl_idx is None else unl_idx.data_ptr()
@@ -524,7 +543,8 @@ class DistTrainEngine(TrainEngine):
         c["adam_t"].value = self.adam_t + 1
         c["scal"].value = self.scalar_hist.data_ptr() + 64 * self._cur_row       # this step's row of the logging ring
         self._banks()           # (the record's pointers: ptr[] of this step)
-        self._ctx = dict(apply_update=apply_update, keep=(keep, XPl, Xl, Y, XPu, Xu, noise, lab_idx, unl_idx, dropmask))
+        self._ctx = dict(apply_update=apply_update, keep=(keep, XPl, Xl, Y, XPu, Xu, noise, lab_idx, unl_idx, dropmask,
+                                                          cube, lab_pix, unl_pix))
 
     def stage_spectral(self, *args, **kw):
         self._begin_step(*args, **kw)
@@ -599,16 +619,19 @@ class DistTrainEngine(TrainEngine):
 
     # ------------------------------------------------------------------ the step
     def step(self, XPl, Xl, Y, XPu, Xu, epoch: int, batch_index: int, noise: Optional[Sequence[torch.Tensor]] = None,
-             dropmask: Optional[torch.Tensor] = None, apply_update: bool = True, lab_idx=None, unl_idx=None) -> None:
+             dropmask: Optional[torch.Tensor] = None, apply_update: bool = True, lab_idx=None, unl_idx=None,
+             cube=None, lab_pix=None, unl_pix=None) -> None:
         """Per-rank inputs: this rank's bt/W labelled and btu/W unlabelled rows (noise / dropmask, when given,
-        are this rank's slices too) -- or, with lab_idx / unl_idx, the resident splits and this rank's row indices."""
+        are this rank's slices too) -- or, with lab_idx / unl_idx, the resident splits and this rank's row indices.
+        cube / lab_pix / unl_pix (XPl = XPu = None): the cube-fed step, as TrainEngine.step."""
         coll = self._native_comm()
         if coll is False:           # a communicator only Python can drive (torch.distributed, the tests' stand-ins)
             drive_step(self, self.comm, XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise, dropmask, apply_update,
-                       lab_idx=lab_idx, unl_idx=unl_idx)
+                       lab_idx=lab_idx, unl_idx=unl_idx, cube=cube, lab_pix=lab_pix, unl_pix=unl_pix)
             return
         # the whole step as ONE C call: stages and collectives enqueued back to back (cmlpl_dist_step, csrc/dist.hip)
-        self._begin_step(XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise, dropmask, apply_update, lab_idx=lab_idx, unl_idx=unl_idx)
+        self._begin_step(XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise, dropmask, apply_update, lab_idx=lab_idx, unl_idx=unl_idx,
+                         cube=cube, lab_pix=lab_pix, unl_pix=unl_pix)
         io, a, c = self._step_io()
         io.batch, io.banks = c["batch"], self._c_banks
         a.step, a.adam_t, a.d_dropmask = c["step"].value, c["adam_t"].value, c["dm"].value
@@ -647,11 +670,13 @@ class DistTrainEngine(TrainEngine):
             self._io = (io, _lib.DistStepArgs())
         return self._io[0], self._io[1], self._cells
 
-    def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024) -> "DistStepGraph":
+    def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
+                cube=None, lab_pix=None, unl_pix=None) -> "DistStepGraph":
         """The sharded step as FIVE captured graphs, one per stage, with the four collectives eager between them
         (cmlpl_dist_stage_graph_create); ``bt`` / ``btu`` are THIS rank's rows, ``lab_idx`` / ``unl_idx`` the resident
-        index buffers the step offsets point into.  See DistStepGraph."""
-        return DistStepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity)
+        index buffers the step offsets point into.  Cube-fed with cube / lab_pix / unl_pix (XPl = XPu = None).  See
+        DistStepGraph."""
+        return DistStepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix)
 
     def outputs(self, gathered_logits=None):
         """(logits, feat) of the GLOBAL batch of the last step, [2][n_g][..], in global row order [labelled of all
@@ -701,7 +726,8 @@ class DistStepGraph:
     launches and four torch.distributed calls instead of seven marshalled stage calls (scripts/dist_overhead.py).
     Bit-identical to the eager sharded step."""
 
-    def __init__(self, eng: "DistTrainEngine", XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024):
+    def __init__(self, eng: "DistTrainEngine", XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
+                 cube=None, lab_pix=None, unl_pix=None):
         import numpy as np
         self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
         if lab_idx is None or unl_idx is None:
@@ -713,11 +739,16 @@ class DistStepGraph:
             raise ValueError("index buffers shorter than one shard")
         if eng.step_count == 0:
             raise RuntimeError("run one eager DistTrainEngine.step() before capturing (kernel attributes are set lazily)")
-        eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
-        TrainEngine.check_index_range(lab_idx, XPl.shape[0], "lab_idx")
-        TrainEngine.check_index_range(unl_idx, XPu.shape[0], "unl_idx")
+        if cube is not None or lab_pix is not None or unl_pix is not None:
+            if XPl is not None or XPu is not None:
+                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
+            eng._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx[:bt], unl_idx[:btu])
+        else:
+            eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
+        TrainEngine.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
+        TrainEngine.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
         eng._bind(self.bt, self.btu)
-        self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
         self.n_lab_idx, self.n_unl_idx = int(lab_idx.shape[0]), int(unl_idx.shape[0])
         dev = eng.device
         self.table = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8, device=dev)
@@ -728,8 +759,9 @@ class DistStepGraph:
         st = eng._stream()
         eng._ensure_packed(st)
         io = _lib.DistIO()
-        io.batch = _lib.Batch(XPl.data_ptr(), Xl.data_ptr(), XPu.data_ptr(), Xu.data_ptr(), Y.data_ptr(), None, self.bt, self.btu,
-                              lab_idx.data_ptr(), unl_idx.data_ptr())
+        _fill_batch(io.batch, XPl, Xl, Y, XPu, Xu, cube, lab_pix, unl_pix)
+        io.batch.noise8, io.batch.bt, io.batch.btu = None, self.bt, self.btu
+        io.batch.d_lab_idx, io.batch.d_unl_idx = lab_idx.data_ptr(), unl_idx.data_ptr()
         io.shard = eng.cshard
         io.gathered = eng._gathered()
         io.banks = eng._banks()
@@ -759,9 +791,9 @@ class DistStepGraph:
 
     def validate_indices(self) -> None:
         """range check of the two index buffers (synchronising): after the caller re-filled them in place"""
-        XPl, _, _, XPu, _, lab_idx, unl_idx = self._keep
-        TrainEngine.check_index_range(lab_idx, XPl.shape[0], "lab_idx")
-        TrainEngine.check_index_range(unl_idx, XPu.shape[0], "unl_idx")
+        _, Xl, _, _, Xu, lab_idx, unl_idx = self._keep[:7]
+        TrainEngine.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
+        TrainEngine.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
 
     def program(self, steps) -> None:
         """as StepGraph.program: (epoch, batch_index, lab_off, unl_off) of the next replays, offsets = this rank's"""

@@ -45,6 +45,7 @@ class TrainEngine:
     reference literal 256 (``hp.bank_step``) -- see DESIGN.md "memory bank".
     """
     takes_indices = True      # step(..., lab_idx=, unl_idx=): batches as row indices into the resident splits
+    takes_cube = True         # step(None, Xl, Y, None, Xu, ..., cube=, lab_pix=, unl_pix=): windows gathered from the scene
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
@@ -91,6 +92,7 @@ class TrainEngine:
         self._io = _lib.StepIO()
         self._fill_state(self._io)
         self._checked = None
+        self._checked_cube = None
         self._graph = None          # weak reference to the StepGraph that has programmed replays (see step())
 
     @property
@@ -193,6 +195,45 @@ class TrainEngine:
             self._checked = (id(XPl), id(Xl), id(Y), id(XPu), id(Xu), XPl.data_ptr(), XPu.data_ptr(), XPl.shape[0], XPu.shape[0])
         return bt, btu
 
+    def _check_cube_rows(self, cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx):
+        """Shapes of a CUBE-FED batch: the resident scene [rows][cols][C], the spectra / labels of the splits (or of the
+        batch) and one scene pixel per split row.  The pixel lists are range-checked here ONCE per array (a
+        synchronising min / max; the gather follows them without a bounds check), not per step."""
+        s = self.shape
+        if cube is None or lab_pix is None or unl_pix is None:
+            raise ValueError("a cube-fed step needs cube, lab_pix and unl_pix")
+        key = (id(cube), id(Xl), id(Y), id(Xu), id(lab_pix), id(unl_pix), cube.data_ptr(), lab_pix.data_ptr(),
+               unl_pix.data_ptr(), tuple(cube.shape), Xl.shape[0], Xu.shape[0])
+        if key != self._checked_cube:
+            if s.H != s.W:
+                raise ValueError(f"cube-fed windows are square, the shape has {s.H} x {s.W}")
+            if cube.dim() != 3 or cube.dtype != torch.float32 or not cube.is_contiguous() or not cube.is_cuda:
+                raise ValueError("cube: need a contiguous float32 cuda tensor [rows][cols][C]")
+            rows, cols, ch = cube.shape
+            if ch != s.C:
+                raise ValueError(f"cube: {ch} channels, the shape has C = {s.C}")
+            if rows < s.H or cols < s.W:
+                raise ValueError(f"cube: scene {rows} x {cols} smaller than the {s.H} x {s.W} window")
+            nl, nu = Xl.shape[0], Xu.shape[0]
+            _chk_f32(Xl, (nl, s.bands), "Xl"); _chk_f32(Xu, (nu, s.bands), "Xu")
+            if Y.dtype != torch.int64 or tuple(Y.shape) != (nl,) or not Y.is_cuda:
+                raise ValueError("Y: need int64 cuda tensor, one label per labelled row")
+            for name, t, n in (("lab_pix", lab_pix, nl), ("unl_pix", unl_pix, nu)):
+                if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"{name}: need a contiguous int64 cuda vector, one scene pixel per split row ({n})")
+                self.check_index_range(t, rows * cols, name)
+            self._checked_cube = key
+        if (lab_idx is None) != (unl_idx is None):
+            raise ValueError("lab_idx and unl_idx come together")
+        for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
+            if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError(f"{name}: need a contiguous int64 cuda vector")
+        bt = Xl.shape[0] if lab_idx is None else lab_idx.shape[0]
+        btu = Xu.shape[0] if unl_idx is None else unl_idx.shape[0]
+        if bt < 1 or btu < 1 or bt > self.bt_max or bt + btu > self.n_max:
+            raise ValueError(f"batch {bt}+{btu} outside the engine's capacity {self.bt_max}+{self.btu_max}")
+        return bt, btu
+
     @staticmethod
     def check_index_range(idx: torch.Tensor, rows: int, name: str = "index") -> None:
         """Every entry of an index list inside [0, rows): the kernels follow the indices without a bounds check, so a
@@ -205,9 +246,15 @@ class TrainEngine:
         if lo < 0 or hi >= rows:
             raise ValueError(f"{name}: entries span [{lo}, {hi}], the resident split has {rows} rows")
 
-    def _fill_io(self, io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu):
-        io.d_xpl, io.d_xl, io.d_labels = XPl.data_ptr(), Xl.data_ptr(), Y.data_ptr()
-        io.d_xpu, io.d_xu = XPu.data_ptr(), Xu.data_ptr()
+    def _fill_io(self, io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube=None, lab_pix=None, unl_pix=None):
+        io.d_xl, io.d_labels, io.d_xu = Xl.data_ptr(), Y.data_ptr(), Xu.data_ptr()
+        if cube is None:
+            io.d_xpl, io.d_xpu = XPl.data_ptr(), XPu.data_ptr()
+            io.d_cube, io.d_lab_pix, io.d_unl_pix, io.cube_rows, io.cube_cols = None, None, None, 0, 0
+        else:
+            io.d_xpl, io.d_xpu = None, None
+            io.d_cube, io.d_lab_pix, io.d_unl_pix = cube.data_ptr(), lab_pix.data_ptr(), unl_pix.data_ptr()
+            io.cube_rows, io.cube_cols = cube.shape[0], cube.shape[1]
         io.d_lab_idx = None if lab_idx is None else lab_idx.data_ptr()
         io.d_unl_idx = None if unl_idx is None else unl_idx.data_ptr()
         io.bt, io.btu = bt, btu
@@ -237,7 +284,9 @@ class TrainEngine:
     def step(self, XPl: torch.Tensor, Xl: torch.Tensor, Y: torch.Tensor, XPu: torch.Tensor, Xu: torch.Tensor,
              epoch: int, batch_index: int, noise: Optional[Sequence[torch.Tensor]] = None,
              dropmask: Optional[torch.Tensor] = None, apply_update: bool = True,
-             lab_idx: Optional[torch.Tensor] = None, unl_idx: Optional[torch.Tensor] = None) -> None:
+             lab_idx: Optional[torch.Tensor] = None, unl_idx: Optional[torch.Tensor] = None,
+             cube: Optional[torch.Tensor] = None, lab_pix: Optional[torch.Tensor] = None,
+             unl_pix: Optional[torch.Tensor] = None) -> None:
         """One training step; asynchronous.  Results land in ``self.scalars`` (device),
         ``self.logits`` / ``self.feat`` ([2][n][..]) and ``self.grads``.
 
@@ -246,6 +295,10 @@ class TrainEngine:
         lab_idx / unl_idx : None -> XPl .. Xu ARE the batch; or int64 row numbers: XPl / Xl / Y (XPu / Xu) are then the
                    whole resident labelled (unlabelled) split and batch row s is its row lab_idx[s] (unl_idx[s]) --
                    no gathered copy of the batch is made (noise / dropmask stay indexed by batch row)
+        cube / lab_pix / unl_pix : the CUBE-FED step -- XPl and XPu are None: no window tensor exists.  ``cube`` is the
+                   resident scene [rows][cols][C]; the patch row of a batch row is the H x W window (mirror index of
+                   ExtractPatches) of scene pixel lab_pix[r] (unl_pix[r]), r = the split row Xl / Y (Xu) are read at.
+                   Bit-identical to the step on ``extract_patches(cube, pix)``.
         """
         s = self.shape
         g = self._graph() if self._graph is not None else None
@@ -253,15 +306,20 @@ class TrainEngine:
             # the remaining replays were programmed from the state BEFORE this step (counters, bank pointers, Adam step)
             raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them (or program() anew) "
                                "before an eager step")
-        bt, btu = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        if cube is not None or lab_pix is not None or unl_pix is not None:
+            if XPl is not None or XPu is not None:
+                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
+            bt, btu = self._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx)
+        else:
+            bt, btu = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
         if _CHECK_INDICES and lab_idx is not None:
-            self.check_index_range(lab_idx, XPl.shape[0], "lab_idx")
-            self.check_index_range(unl_idx, XPu.shape[0], "unl_idx")
+            self.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
+            self.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
         n = bt + btu
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._ensure_packed(stream)
         io = self._io
-        self._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu)
+        self._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube, lab_pix, unl_pix)
         io.noise8, io.d_dropmask = None, None
         keep = None
         if noise is not None:
@@ -287,10 +345,12 @@ class TrainEngine:
                    self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
         self._advance(n, apply_update)
 
-    def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024) -> "StepGraph":
+    def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
+                cube=None, lab_pix=None, unl_pix=None) -> "StepGraph":
         """The step captured ONCE as a hipGraph over the resident splits and two index buffers (lab_idx / unl_idx: the
-        epoch's permutations, re-filled in place by the caller); see StepGraph."""
-        return StepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity)
+        epoch's permutations, re-filled in place by the caller); see StepGraph.  Cube-fed (cube / lab_pix / unl_pix
+        given, XPl = XPu = None): over the resident scene instead of the window tensors."""
+        return StepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix)
 
     def outputs(self):
         """(logits [2][n][K], feat [2][n][1024]) of the last step."""
@@ -343,7 +403,8 @@ class StepGraph:
     from the state before it).
     """
 
-    def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024):
+    def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
+                 cube=None, lab_pix=None, unl_pix=None):
         import numpy as np
         self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
         if lab_idx is None or unl_idx is None:
@@ -353,8 +414,13 @@ class StepGraph:
         for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
             if t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
                 raise ValueError(f"{name}: need a contiguous int64 cuda vector")
-        eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
-        self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        if cube is not None or lab_pix is not None or unl_pix is not None:
+            if XPl is not None or XPu is not None:
+                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
+            eng._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx[:bt], unl_idx[:btu])
+        else:
+            eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
+        self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
         self.validate_indices()
         self.n_lab_idx, self.n_unl_idx = int(lab_idx.shape[0]), int(unl_idx.shape[0])
         dev = eng.device
@@ -368,7 +434,7 @@ class StepGraph:
         eng._ensure_packed(stream)
         io = _lib.StepIO()
         eng._fill_state(io)
-        eng._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, self.bt, self.btu)
+        eng._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, self.bt, self.btu, cube, lab_pix, unl_pix)
         io.d_scalars = eng.scalar_hist.data_ptr()          # ring base: the row comes from the table
         io.apply_update = 1
         io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
@@ -388,9 +454,9 @@ class StepGraph:
     def validate_indices(self) -> None:
         """Range check of the two index buffers (synchronising): at capture, and whenever the caller has re-filled them
         in place and wants the check (the kernels follow the indices blindly)."""
-        XPl, _, _, XPu, _, lab_idx, unl_idx = self._keep
-        TrainEngine.check_index_range(lab_idx, XPl.shape[0], "lab_idx")
-        TrainEngine.check_index_range(unl_idx, XPu.shape[0], "unl_idx")
+        _, Xl, _, _, Xu, lab_idx, unl_idx = self._keep[:7]
+        TrainEngine.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
+        TrainEngine.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
 
     def program(self, steps) -> None:
         """``steps``: (epoch, batch_index, lab_off, unl_off) of the next replays, in order.  Fills the table from the

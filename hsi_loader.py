@@ -5,7 +5,9 @@ serves N(0,1) patches of any window shape when the datasets are not on disk (the
 ``device_arrays()`` hands the whole split to the GPU once: the training driver keeps it resident in
 HBM and gathers batches by index there instead of copying 24.6 MB over PCIe per step.
 A directory that this repository's ``sample_generation.py`` wrote has no XP.npy but ``cube.npy`` + ``scene.json``: the
-windows are then cut from the cube (``CubeWindows``), with the same item tuples."""
+windows are then cut from the cube (``CubeWindows``), with the same item tuples.  ``scene_arrays()`` hands such a split
+to the GPU WITHOUT its windows -- spectra, labels and one scene pixel per row -- for the cube-fed training step, which
+gathers the windows from the resident cube (``scene_cube``) itself."""
 import json
 import os
 
@@ -118,13 +120,32 @@ class HSIDataSet(data.Dataset):
         Y = None if self.Y is None else torch.from_numpy(np.asarray(self.Y, dtype=np.int64)).to(device)
         return XP, X, Y
 
-    def cube_source(self, device, scene=None, dataID=None):
+    @property
+    def scene_cube(self):
+        """the scene [rows, cols, C] the split's windows are cut from (cube.npy, memory-mapped); None for a directory
+        with a materialised XP.npy"""
+        return self.XP.cube if isinstance(self.XP, CubeWindows) else None
+
+    def scene_arrays(self, device):
+        """(X, Y, pix) on ``device`` for the cube-fed step: row i of the split is the window ``CubeWindows.cut(pix[i])``
+        of ``scene_cube`` with spectrum X[i] and label Y[i] -- the items of ``__getitem__``, tiled / truncated alike --
+        and no window is cut.  Needs a split that came from cube.npy."""
+        if not isinstance(self.XP, CubeWindows):
+            raise ValueError(f"{self.root}: the split was read from XP.npy; scene_arrays() needs cube.npy + scene.json "
+                             "(this repository's sample_generation.py)")
+        X = torch.from_numpy(np.ascontiguousarray(self.X, dtype=np.float32)).to(device)
+        Y = None if self.Y is None else torch.from_numpy(np.asarray(self.Y, dtype=np.int64)).to(device)
+        return X, Y, torch.from_numpy(np.ascontiguousarray(self.XP.idx)).to(device)
+
+    def cube_source(self, device, scene=None, dataID=None, resident_cube=None):
         """The 'wholeset' as the scene it was cut from, for whole-image inference without the materialised patches
         (tools.hyper_tools.test_whole): ``cube.npy`` ([rows, cols, C], the z-scored / PCA'd scene the patches were cut
         from: this repository's sample_generation.py writes it, with scene.json) next to XP.npy or in its place.  None
         when it is not there (the caller then streams the materialised patches, as the reference does): the cube is
         NOT rebuilt from XP.npy -- that gather touches every page of a ~20 GB file to recover 0.25 % of it.  The scene
-        shape comes from scene.json when there is one (then any scene is taken), else from ``_SCENES``."""
+        shape comes from scene.json when there is one (then any scene is taken), else from ``_SCENES``.
+        ``resident_cube``: the same cube.npy already on ``device`` (a cube-fed training run keeps it there): used in
+        place of a second upload."""
         from cmlpl_amd.infer import CubeSource
         if self.setindex != 'wholeset':
             raise ValueError("cube_source() is for the 'wholeset'")
@@ -139,7 +160,10 @@ class HSIDataSet(data.Dataset):
             scene = _SCENES.get(int(dataID))
         if cube.ndim != 3 or (scene is not None and tuple(cube.shape[:2]) != tuple(scene)):
             return None
-        cube = torch.from_numpy(np.ascontiguousarray(cube, dtype=np.float32)).to(device)
+        if resident_cube is not None and tuple(resident_cube.shape) == tuple(cube.shape):
+            cube = resident_cube
+        else:
+            cube = torch.from_numpy(np.ascontiguousarray(cube, dtype=np.float32)).to(device)
         X = torch.from_numpy(np.ascontiguousarray(self.X, dtype=np.float32)).to(device)
         if cube.shape[0] * cube.shape[1] != X.shape[0]:
             return None
@@ -147,29 +171,52 @@ class HSIDataSet(data.Dataset):
 
 
 class SyntheticHSIDataSet(data.Dataset):
-    """Seeded stand-in with the same item tuples; class-dependent mean so that training has signal."""
+    """Seeded stand-in with the same item tuples; class-dependent mean so that training has signal.
+    ``scene`` (a ``SyntheticScene``): the split is then ``length`` seeded pixels of that scene -- windows cut from its
+    cube as ``HSIDataSet`` cuts them from cube.npy, spectra and labels the pixels' own -- and ``scene_arrays()`` serves
+    the cube-fed step."""
 
-    def __init__(self, shape, length, setindex='label', seed=1088, separable=1.0):
+    def __init__(self, shape, length, setindex='label', seed=1088, separable=1.0, scene=None):
         C, H, W, bands, K = shape
         g = torch.Generator().manual_seed(seed)
+        self.setindex, self.scene = setindex, scene
+        if scene is not None:
+            if H != W or scene.cube.shape[2] != C or scene.X.shape[1] != bands:
+                raise ValueError("the scene does not carry this shape's windows")
+            self.pix = torch.randint(0, len(scene), (length,), generator=g)
+            self.Y, self.X = scene.Y[self.pix], scene.X[self.pix]
+            self.XP = CubeWindows(scene.cube.numpy(), H, self.pix.numpy())
+            return
         proto_g = torch.Generator().manual_seed(4242)
         self.Y = torch.randint(0, K, (length,), generator=g)
         proto_p = torch.randn(K, C, 1, 1, generator=proto_g) * separable
         proto_x = torch.randn(K, bands, generator=proto_g) * separable
         self.XP = torch.randn(length, C, H, W, generator=g) + proto_p[self.Y]
         self.X = torch.randn(length, bands, generator=g) + proto_x[self.Y]
-        self.setindex = setindex
 
     def __len__(self):
         return len(self.X)
 
     def __getitem__(self, index):
+        XP = self.XP[index] if self.scene is not None else self.XP[index].numpy()
         if self.setindex == 'wholeset':
-            return self.XP[index].numpy(), self.X[index].numpy()
-        return self.XP[index].numpy(), self.X[index].numpy(), int(self.Y[index])
+            return XP, self.X[index].numpy()
+        return XP, self.X[index].numpy(), int(self.Y[index])
 
     def device_arrays(self, device):
+        if self.scene is not None:
+            return self.XP.device_tensor(device), self.X.to(device), self.Y.to(device)
         return self.XP.to(device), self.X.to(device), self.Y.to(device)
+
+    @property
+    def scene_cube(self):
+        return None if self.scene is None else self.scene.cube
+
+    def scene_arrays(self, device):
+        """(X, Y, pix) on ``device``, as ``HSIDataSet.scene_arrays``; needs the ``scene`` the split was drawn from"""
+        if self.scene is None:
+            raise ValueError("scene_arrays() needs a split drawn from a SyntheticScene (scene=)")
+        return self.X.to(device), self.Y.to(device), self.pix.to(device)
 
 
 class SyntheticScene:
@@ -196,6 +243,8 @@ class SyntheticScene:
     def __len__(self):
         return self.rows * self.cols
 
-    def cube_source(self, device):
+    def cube_source(self, device, resident_cube=None):
+        """``resident_cube``: this scene's cube already on ``device`` (a cube-fed training run keeps it there)"""
         from cmlpl_amd.infer import CubeSource
-        return CubeSource(self.cube.to(device).contiguous(), self.X.to(device).contiguous())
+        cube = resident_cube if resident_cube is not None else self.cube.to(device).contiguous()
+        return CubeSource(cube, self.X.to(device).contiguous())

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CMLPL_ABI_VERSION 5
+#define CMLPL_ABI_VERSION 6
 #define CMLPL_FEAT_DIM 1024 /* tools/models.py:119 */
 #define CMLPL_CONV_CH 64    /* tools/models.py:102-107 */
 
@@ -161,6 +161,19 @@ typedef struct cmlpl_batch {
    * the resident split lies, no gathered copy of the batch exists.  NULL = rows 0 .. bt-1 / 0 .. btu-1 as before.
    * (The explicit noise tensors and dropout masks of parity mode stay indexed by batch row.) */
   const int64_t* d_lab_idx; const int64_t* d_unl_idx;
+  /* ABI 6 -- the CUBE-FED batch: no window tensor exists.  d_cube [cube_rows][cube_cols][C] f32 is the resident scene
+   * (band-last, what cmlpl_scene_project / cmlpl_extract_patches / cmlpl_infer_cube read); the patch row of labelled
+   * batch row s is the H x W window (H == W), through the mirror index of MirrowCut / ExtractPatches
+   * (tools/hyper_tools.py:35-55, :226-243), of scene pixel d_lab_pix[r], r = d_lab_idx[s] (or s when d_lab_idx is NULL)
+   * -- the SAME split row r that d_xl / d_labels are read at; unlabelled rows likewise through d_unl_pix.  One gather
+   * launch in front of the forward forms the augmented rows of both networks from the cube (same noise counters: a
+   * cube-fed step is bit-identical to the step on cmlpl_extract_patches' windows).
+   *   d_cube == NULL: the batch is read from d_xpl / d_xpu as before (the three fields below are ignored).
+   *   d_cube != NULL: d_xpl and d_xpu must be NULL, d_lab_pix / d_unl_pix are required (row-major pixel indices in
+   *   [0, cube_rows * cube_cols): the kernels follow them without a bounds check), cube_rows, cube_cols >= the window.
+   * Otherwise CMLPL_E_ARG / CMLPL_E_SHAPE (H != W, scene smaller than the window, window too large for LDS). */
+  const float* d_cube; int32_t cube_rows, cube_cols;
+  const int64_t* d_lab_pix; const int64_t* d_unl_pix;
 } cmlpl_batch;
 
 /* One step's scalars in DEVICE memory (ABI 3): what changes from step to step, for a step captured ONCE in a hipGraph
@@ -346,6 +359,9 @@ typedef struct cmlpl_step_io {
   /* ABI 3 */
   const int64_t* d_lab_idx; const int64_t* d_unl_idx;   /* as in cmlpl_batch; NULL = consecutive rows */
   const cmlpl_dyn* d_dyn_table; int32_t* d_dyn_cursor;   /* NULL = the by-value fields above are used  */
+  /* ABI 6 */
+  const float* d_cube; int32_t cube_rows, cube_cols;     /* as in cmlpl_batch; d_cube NULL = d_xpl / d_xpu are read */
+  const int64_t* d_lab_pix; const int64_t* d_unl_pix;
 } cmlpl_step_io;
 
 int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io,
@@ -369,7 +385,7 @@ int cmlpl_step_graph_destroy(void* graph);
  * d_unl_idx: this rank's slice starts at the row's lab_off / unl_off); in-kernel random streams only.  Launch / destroy a
  * stage's graph with cmlpl_step_graph_launch / cmlpl_step_graph_destroy. */
 typedef struct cmlpl_dist_io {
-  cmlpl_batch batch;            /* this rank's rows (bt, btu PER RANK), by index                                   */
+  cmlpl_batch batch;            /* this rank's rows (bt, btu PER RANK), by index (ABI 6: split-fed or cube-fed)     */
   cmlpl_shard shard;            /* this rank's place in the global batch                                           */
   cmlpl_gathered gathered;      /* the gathered embeddings / labels and this rank's logits                          */
   cmlpl_banks banks;            /* (ptr[] unused: the table carries the pointers)                                  */
@@ -562,7 +578,7 @@ enum {
   CMLPL_K_HEAD_FWD, CMLPL_K_LOSS, CMLPL_K_HEAD_BWD, CMLPL_K_CLS_WGRAD, CMLPL_K_SPE_WGRAD,
   CMLPL_K_CONV2_DGRAD, CMLPL_K_CONV2_WGRAD, CMLPL_K_CONV2_WRED, CMLPL_K_CONV1_DGRAD, CMLPL_K_CONV1_WGRAD,
   CMLPL_K_CONV1_WRED, CMLPL_K_CONV0_WGRAD, CMLPL_K_ADAM, CMLPL_K_PACK, CMLPL_K_LOSS2, CMLPL_K_LOSS_FIN,
-  CMLPL_K_LOSS_DFEAT, CMLPL_K_COUNT
+  CMLPL_K_LOSS_DFEAT, CMLPL_K_CUBE_FEED /* ABI 6: the cube-fed step's gather + augment launch */, CMLPL_K_COUNT
 };
 int cmlpl_timing_begin(uint32_t kernel_mask, int max_launches);
 int cmlpl_timing_end(double* ms_sum /*[CMLPL_K_COUNT]*/, int64_t* launches /*[CMLPL_K_COUNT]*/);

@@ -15,6 +15,9 @@ Differences from the reference that are deliberate, MI355X-first choices:
   * the five logged scalars of every step (loss_hist, train.py:136,274-278) are written by the step into a
     device-side ring and read back once per ``print_per_batches`` steps, not five times a step; the printed line
     is the mean over that window, as in train.py:281-289.
+  * ``--windows cube``: no window tensor at all -- the scene cube (cube.npy, 50 MB for PaviaU) is uploaded once and every
+    step, eager or replayed, on one or several GPUs, gathers its windows from it (the cube-fed step of cmlpl_amd); the
+    default ``--windows split`` cuts each split's windows once and keeps them resident (2 x 960 MB at the defaults).
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -82,13 +85,16 @@ def main(args, make_engine=None, device=None):
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
     torch.manual_seed(1088)                                         # seed_torch(), train.py:50-58
+    cube_fed = args.windows == 'cube'
     if args.synthetic:
         shape = SYNTH[args.synthetic]
         num_classes, num_features = shape[4], shape[3]
-        labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1)
-        unlabeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'unlabel', seed=2)
+        # (--windows cube / --synthetic_scene: both splits are seeded pixels of ONE synthetic scene, the evaluation's)
+        from_scene = cube_fed or args.synthetic_scene
+        whole = SyntheticScene(shape, 64, 64, seed=3) if (from_scene or not args.no_eval) else None   # a 64 x 64 scene cube, every pixel a test pixel
+        labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=whole if from_scene else None)
+        unlabeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'unlabel', seed=2, scene=whole if from_scene else None)
         if not args.no_eval:
-            whole = SyntheticScene(shape, 64, 64, seed=3)                  # a 64 x 64 scene cube, every pixel a test pixel
             Y_test, test_array = whole.Y.numpy(), np.arange(len(whole))
     else:
         num_classes, num_features = DATASETS[int(args.dataID)]
@@ -120,8 +126,21 @@ def main(args, make_engine=None, device=None):
     eng.init_params_default(1088)
 
     gen = torch.Generator().manual_seed(1088)                        # same permutations on every rank
-    lab_loader = DeviceLoader(labeled.device_arrays(device), bt, gen)
-    unl_loader = DeviceLoader(unlabeled.device_arrays(device), btu, gen)
+    cube_kw = {}
+    if cube_fed:
+        # the scene goes to the GPU ONCE; a split is its spectra, labels and one scene pixel per row -- no windows
+        if not getattr(eng, "takes_cube", False):
+            raise SystemExit("--windows cube: this engine has no cube-fed step")
+        if labeled.scene_cube is None or unlabeled.scene_cube is None:
+            raise SystemExit("--windows cube needs cube.npy + scene.json in the dataset directory (sample_generation.py)")
+        cube_dev = torch.from_numpy(np.ascontiguousarray(labeled.scene_cube, dtype=np.float32)).to(device)
+        (Xl_, Yl_, lab_pix), (Xu_, Yu_, unl_pix) = labeled.scene_arrays(device), unlabeled.scene_arrays(device)
+        lab_loader = DeviceLoader((None, Xl_, Yl_), bt, gen)
+        unl_loader = DeviceLoader((None, Xu_, Yu_), btu, gen)
+        cube_kw = dict(cube=cube_dev, lab_pix=lab_pix, unl_pix=unl_pix)
+    else:
+        lab_loader = DeviceLoader(labeled.device_arrays(device), bt, gen)
+        unl_loader = DeviceLoader(unlabeled.device_arrays(device), btu, gen)
     num_batches = min(len(lab_loader), len(unl_loader))              # train.py:134
     num_steps = args.num_epochs * num_batches                        # train.py:135
     loss_hist = np.zeros((num_steps, 5))                             # train.py:136
@@ -160,7 +179,7 @@ def main(args, make_engine=None, device=None):
             elif by_index:
                 eng.step(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X, epoch, batch_index,
                          lab_idx=lab_loader.perm[lo + r * bl:lo + (r + 1) * bl],
-                         unl_idx=unl_loader.perm[uo + r * bul:uo + (r + 1) * bul])
+                         unl_idx=unl_loader.perm[uo + r * bul:uo + (r + 1) * bul], **cube_kw)
             else:
                 XPl, Xl, Yl = (t[r * bl:(r + 1) * bl].contiguous() for t in lab_loader.rows(lo, ls))
                 XPu, Xu, _ = (t[r * bul:(r + 1) * bul].contiguous() for t in unl_loader.rows(uo, us))
@@ -169,7 +188,7 @@ def main(args, make_engine=None, device=None):
                 # the first step ran eagerly (it sets the kernels' attributes); capture now and hand the rest of this
                 # epoch's full batches to the graph
                 graph = eng.capture(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X,
-                                    lab_loader.perm, unl_loader.perm, gbt, gbtu, capacity=max(num_batches, 1))
+                                    lab_loader.perm, unl_loader.perm, gbt, gbtu, capacity=max(num_batches, 1), **cube_kw)
                 rest = [(epoch, bi, lo2 + rank * gbt, uo2 + rank * gbtu) for bi, ((lo2, ls2), (uo2, us2)) in enumerate(batches)
                         if bi > batch_index and ls2 == bt and us2 == btu]
                 if rest:
@@ -198,6 +217,8 @@ def main(args, make_engine=None, device=None):
                   (steps - steps_warm, t_end - t_warm, (t_end - t_warm) / (steps - steps_warm) * 1e3))
         if args.save_loss_hist:
             np.save(args.save_loss_hist, loss_hist)
+        if args.report_memory and device.type == "cuda":
+            print('peak device memory: %d bytes' % torch.cuda.max_memory_allocated(device))
     if rank == 0 and not args.no_eval:
         # whole-image inference + accuracy (train.py:291-306).  The scene stays in HBM as its cube and the forward gathers
         # the windows itself (cmlpl_infer_cube): no 19.9 GB patch tensor, no DataLoader (train.py:291-294 streams the
@@ -208,7 +229,10 @@ def main(args, make_engine=None, device=None):
         t_src = time.time()
         source = None
         if infer_supported(NetShape(*shape)):
-            source = whole.cube_source(device) if args.synthetic else whole.cube_source(device, dataID=args.dataID)
+            # (a cube-fed run evaluates on the cube it trained from: it is resident already)
+            res = cube_kw.get("cube")
+            source = whole.cube_source(device, resident_cube=res) if args.synthetic else \
+                whole.cube_source(device, dataID=args.dataID, resident_cube=res)
         if source is None:
             if args.synthetic:      # (cut the scene's windows on the device, then the reference's loader path)
                 from cmlpl_amd.patches import extract_patches
@@ -270,6 +294,14 @@ def build_parser():
     parser.add_argument('--graph', action='store_true',
                         help='capture the training step once as a hipGraph and replay it (several GPUs: the sharded '
                              'step as seven stage graphs, its collectives eager between them)')
+    parser.add_argument('--windows', choices=('split', 'cube'), default='split',
+                        help="where a step's patch windows come from: 'split' cuts every window of both splits once and "
+                             "keeps them resident (2 x 960 MB at the defaults); 'cube' uploads the scene cube once and "
+                             "every step gathers its windows from it (needs cube.npy + scene.json, or --synthetic)")
+    parser.add_argument('--synthetic_scene', action='store_true',
+                        help='--synthetic: draw both splits from one seeded synthetic scene (implied by --windows cube)')
+    parser.add_argument('--report_memory', action='store_true',
+                        help="print the process's peak allocated device memory after the last step")
     return parser
 
 

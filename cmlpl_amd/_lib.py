@@ -35,6 +35,7 @@ EXPORTS = (
     "cmlpl_debug_reload_switches", "cmlpl_forward_spectral", "cmlpl_forward_spatial", "cmlpl_backward_data",
     "cmlpl_backward_weights", "cmlpl_dist_step", "cmlpl_rccl_bind", "cmlpl_rccl_unbind", "cmlpl_debug_two_piece",
     "cmlpl_scene_workspace_bytes", "cmlpl_scene_gram", "cmlpl_scene_project",
+    "cmlpl_eval_workspace_bytes", "cmlpl_infer_pixels", "cmlpl_confusion",      # added after ABI 6, no bump (include/cmlpl.h)
 )
 
 KERNEL_NAMES = ("augment", "conv0_fwd", "conv1_fwd", "conv2_fwd", "spe_fwd", "head_fwd", "loss", "head_bwd",
@@ -230,6 +231,10 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_infer_workspace_bytes.argtypes = [vp, i32]
     lib.cmlpl_infer_workspace_bytes.restype = C.c_size_t
     lib.cmlpl_infer_cube.argtypes = [vp, vp, vp, vp, i32, i32, vp, C.c_int64, i32, vp, vp, vp, C.c_size_t, vp]
+    lib.cmlpl_eval_workspace_bytes.argtypes = [SP, i32, i32]
+    lib.cmlpl_eval_workspace_bytes.restype = sz
+    lib.cmlpl_infer_pixels.argtypes = [SP, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.cmlpl_confusion.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]
@@ -265,7 +270,7 @@ def load(path: str = LIB_PATH):
     for s in EXPORTS[1:]:
         if hasattr(lib, s) and s not in ("cmlpl_workspace_bytes", "cmlpl_loss_workspace_bytes", "cmlpl_ntxent_workspace_bytes",
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
-                     "cmlpl_scene_workspace_bytes"):
+                     "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

@@ -1056,6 +1056,43 @@ int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const floa
                                 d_params + L.param_off[3], t, (long long*)d_labels, st));
 }
 
+size_t cmlpl_eval_workspace_bytes(const cmlpl_shape* shape, int nets, int n) {
+  Dims d;
+  if (!make_dims(shape, &d) || n < 1 || nets < 1 || nets > 2 || !conv3_infer_ok(d.H, d.W, d.C, d.K)) return 0;   // 0: not a shape cmlpl_infer_pixels takes
+  return up256((size_t)nets * n * 1024 * 4);                // y = relu(feat_spe(spectrum)) [nets][n][1024]
+}
+
+int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                       const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                       const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                       int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream) {
+  Dims d;
+  cmlpl_layout_t L;
+  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
+  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_pix || !d_labels || !d_workspace || n < 1 || nets < 1 ||
+      nets > 2 || rows < 1 || cols < 1 || rows < d.H / 2 || cols < d.W / 2 ||
+      (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
+    return CMLPL_E_ARG;
+  if (!conv3_infer_ok(d.H, d.W, d.C, d.K)) return CMLPL_E_SHAPE;
+  if ((int64_t)rows * cols * d.C >= (1LL << 31)) return CMLPL_E_ARG;          // (the gather's 32-bit offsets)
+  if (cmlpl_eval_workspace_bytes(shape, nets, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* y = (float*)d_workspace;
+  int rc;
+  // spectral branch of the list's items, both networks from the same rows (canonical weights)
+  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, d_spectra, d_params + L.param_off[6], d_params + L.param_off[7],
+                               param_stride, y, st, (const long long*)d_spec_row, 0)))) return rc;
+  FwdTail t;
+  memset(&t, 0, sizeof(t));
+  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
+  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
+  t.y = y; t.logits = d_logits; t.K = d.K;
+  const InferNets nn = {nets, (long long)param_stride, (long long)packed_stride, (const long long*)d_pix};
+  return chk(launch_conv3_infer(n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
+                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
+                                d_params + L.param_off[3], t, (long long*)d_labels, st, &nn));
+}
+
 size_t cmlpl_ntxent_workspace_bytes(int B, int D) { return (B < 1 || D < 1) ? 0 : ntxent_ws_floats(B, D) * 4; }
 
 int cmlpl_ntxent_fwd_bwd(const float* d_emb_i, const float* d_emb_j, int B, int D, float temperature, float* d_loss,

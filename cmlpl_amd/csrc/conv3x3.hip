@@ -176,7 +176,7 @@ struct Conv3Args {
   const float* dlogits; const float* dfeat; const float* hmask;   // hmask: dropout multiplier rows or null
   const float* ynrm; const uint8_t* m2in; const float* w2d; long long w2d_ns;
   float* dy; float* dp2out; float* dp1out;
-  // INFER (forward, TAIL == 2): whole-image inference straight from the scene cube (tools/hyper_tools.py:226-243,416-437):
+  // INFER (forward, TAIL == 2; TAIL == 3 by pixel list): whole-image inference straight from the scene cube (tools/hyper_tools.py:226-243,416-437):
   // sample s is pixel pix0 + s (row-major) of the band-last cube [crows][ccols][C]; its H x W window is gathered through
   // the mirror index of ExtractPatches while the slab chunks are staged -- no patch tensor exists; the argmax goes to
   // labels_out[s] (logits optional)
@@ -195,6 +195,10 @@ struct Conv3Args {
   // workgroup leaves its sample's largest magnitude (float bits) of a0, p1 (forward) and of conv1's / conv2's masked
   // up-sampled pooled gradients (backward) -- plain stores, every slot rewritten every step; null = not collected
   uint32_t* hstat;
+  // INFER by pixel list (cmlpl_infer_pixels), null = the range from pix0: sample s is scene pixel pix[s] -- any order,
+  // repeats allowed; labels_out / logits / yin are [net][n] rows as in the training forward (grid.y = networks).
+  // (last member: no other field's kernel-argument offset moves)
+  const long long* pix;
 };
 
 // x / d == umulhi(x, ceil(2^32 / d)) for x d < 2^32 (every index here is below 2^16); d = 1 is flagged by 0
@@ -933,7 +937,7 @@ struct Conv3Ctx {
 
 // NW = waves of the workgroup: 4 (every MODE), or 8 for the per-sample kernels (MODE >= 2) when one workgroup has a CU
 // to itself (see ks_unit); NT = its threads, TPW = M tiles per wave in the tap loop.
-template <int MODE, int NW = 4, int TPW = 8 / NW, bool CUBE = false, bool H2X = false>
+template <int MODE, int NW = 4, int TPW = 8 / NW, int CUBE = 0 /* 1: pixels pix0 + s, 2: pixels pix[s] */, bool H2X = false>
 __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int lut_entries, Conv3Ctx& c,
                                             const float* dp_lds = nullptr, const uint32_t* mpre = nullptr) {
   constexpr int NT = 64 * NW;
@@ -1059,7 +1063,14 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
       // pixel (the cube is band-last), found through the mirror index of ExtractPatches; cofs = that pixel's float offset
       int cofs[TPW];
       if constexpr (CUBE) {
-        const long long pix = a.pix0 + s0;
+        // (one sample per workgroup: the list entry is a scalar load, as rowsel_index's.  A template flag and not a null
+        //  test: the contiguous kernel is the code it was)
+        long long pix = a.pix0 + s0;
+        if constexpr (CUBE == 2) {  // (an index outside the scene is the caller's error -- checked where a list is registered; clamped, so that it cannot read outside the cube)
+          const long long last = (long long)a.crows * a.ccols - 1;
+          pix = uni64(a.pix[s0]);
+          pix = pix < 0 ? 0 : (pix > last ? last : pix);
+        }
         const int pr = (int)(pix / a.ccols), pc = (int)(pix - (long long)pr * a.ccols), hwin = W >> 1;
         const int magicp = (65536 + W - 1) / W;
 #pragma unroll
@@ -2401,7 +2412,7 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
   constexpr int KMT = NW * TPW / 2;        // pixel tiles of the per-sample kernels
   constexpr int LUTN = (MODE >= 2) ? KMT * 32 : MTW * NW * 32;
   constexpr bool BIG = (KMT == 8);         // the generalised tail / head (final maps up to 12 pooled pixels)
-  constexpr bool INFER = (MODE == 2 && TAIL == 2);   // forward from the scene cube, eval, argmax out: nothing kept for a backward
+  constexpr bool INFER = (MODE == 2 && TAIL >= 2);   // forward from the scene cube, eval, argmax out: nothing kept for a backward (TAIL == 3: by pixel list)
   if constexpr (INFER) { if (wg_infer_sample(a) < 0) return; }
   if (CMLPL_ABL == 26) return;             // ablation: the launch itself (grid, LDS allocation, end of kernel) and nothing else
   Conv3Ctx c;
@@ -2412,7 +2423,7 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
     if constexpr (BIG) dp_lds = conv3_bwd_head_g(a, smem, mpre);
     else dp_lds = conv3_bwd_head<NW>(a, smem, mpre);
   }
-  conv3_stage<MODE, NW, TPW, INFER, H2X>(a, smem, LUTN, c, dp_lds, mpre);
+  conv3_stage<MODE, NW, TPW, INFER ? TAIL - 1 : 0, H2X>(a, smem, LUTN, c, dp_lds, mpre);
   STAMPG(MODE & 1, 1);
   const int tid = c.tid, lane = c.lane, l31 = c.l31, hh = c.hh, wave = c.wave, net = c.net, s0 = c.s0;
   const int HW = c.HW, PW = c.PW, S = c.S, PX = c.PX, npx = c.npx;
@@ -3263,8 +3274,9 @@ bool conv3_infer_ok(int H, int W, int C, int K) {
 
 hipError_t launch_conv3_infer(int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
                               const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
-                              long long* labels_out, hipStream_t st) {
-  if (!conv3_infer_ok(H, W, C, t.K) || n < 1 || !cube || !labels_out) return hipErrorInvalidValue;
+                              long long* labels_out, hipStream_t st, const InferNets* nn) {
+  const int nets = nn != nullptr ? nn->nets : 1;
+  if (!conv3_infer_ok(H, W, C, t.K) || n < 1 || !cube || !labels_out || nets < 1 || nets > 2) return hipErrorInvalidValue;
   if ((long long)crows * ccols * C >= (1LL << 31) || W / 2 > crows || W / 2 > ccols) return hipErrorInvalidValue;   // (32-bit offsets; one mirror fold)
   BigGeom bg;
   const bool big = conv3_big_fwd_ok(H, W, C, &bg);
@@ -3279,10 +3291,21 @@ hipError_t launch_conv3_infer(int n, int C, int H, int W, const float* cube, int
   a.w2f = t.w2f; a.b2 = t.b2; a.wc = t.wc; a.bc = t.bc; a.yin = t.y; a.logits = t.logits; a.K = t.K;
   a.train = 0; a.dropout_p = 0.f;
   a.cube = cube; a.crows = crows; a.ccols = ccols; a.pix0 = pix0; a.labels_out = labels_out;
+  if (nn != nullptr) {      // the networks' strides (every one of them 0 above: one network) and the pixel list
+    a.wpk_ns = nn->packed_ns; a.w0t_ns = nn->packed_ns; a.w2f_ns = nn->packed_ns;
+    a.bias_ns = nn->param_ns; a.b0_ns = nn->param_ns; a.p_ns = nn->param_ns;
+    a.pix = nn->pix;
+  }
   static DevOnce attr_once;
-  hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<2, 1, 2>, conv3x3_kernel<2, 1, 2, 8, 2>);
+  hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<2, 1, 2>, conv3x3_kernel<2, 1, 2, 8, 2>, conv3x3_kernel<2, 1, 3>,
+                                conv3x3_kernel<2, 1, 3, 8, 2>);
   if (e != hipSuccess) return e;
-  const dim3 grid(8 * ((n + 7) / 8), 1);
+  const dim3 grid(8 * ((n + 7) / 8), nets);
+  if (a.pix != nullptr) {       // TAIL == 3: the same kernels reading the list
+    if (big) hipLaunchKernelGGL((conv3x3_kernel<2, 1, 3, 8, 2>), grid, dim3(512), conv3_big_fwd_lds(bg, C), st, a);
+    else hipLaunchKernelGGL((conv3x3_kernel<2, 1, 3>), grid, dim3(256), lds_small, st, a);
+    return hipGetLastError();
+  }
   if (big) hipLaunchKernelGGL((conv3x3_kernel<2, 1, 2, 8, 2>), grid, dim3(512), conv3_big_fwd_lds(bg, C), st, a);
   else hipLaunchKernelGGL((conv3x3_kernel<2, 1, 2>), grid, dim3(256), lds_small, st, a);
   return hipGetLastError();

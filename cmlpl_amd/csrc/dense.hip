@@ -15,20 +15,24 @@
 namespace cmlpl {
 
 // workgroup = 32 rows x 128 outputs; operands staged in LDS with odd row stride.
+// LIST: output row r is row rows[r] of `sn` (inference by pixel list); a template flag, so that the plain kernel is the code it was.
+template <bool LIST>
 __global__ __launch_bounds__(256) void spe_fwd_kernel(const float* __restrict__ sn, const float* __restrict__ w,
                                                       const float* __restrict__ b, long long pstride,
-                                                      float* __restrict__ y, int n, int bands) {
+                                                      float* __restrict__ y, int n, int bands,
+                                                      const long long* __restrict__ rows, long long sn_ns) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int net = blockIdx.z, r0 = blockIdx.x * 32, o0 = blockIdx.y * 128;
   const int BP = (bands + 2) | 1;                   // odd stride, >= bands+1 (zero pad for odd bands)
   float* As = smem;                                 // [32][BP]
   float* Bs = smem + 32 * BP;                       // [128][BP]
-  const float* S = sn + (long long)net * n * bands;
+  const float* S = sn + (long long)net * sn_ns;
   const float* W = w + (long long)net * pstride;
   staged_copy<8, float>(32 * BP, tid,
       [&](int i) { const int r = i / BP, k = i - r * BP; const bool ok = (k < bands) && (r0 + r < n);
-                   const float v = S[ok ? (long long)(r0 + r) * bands + k : 0]; return ok ? v : 0.f; },
+                   const long long row = (LIST && ok) ? rows[r0 + r] : (long long)(r0 + r);
+                   const float v = S[ok ? row * bands + k : 0]; return ok ? v : 0.f; },
       [&](int i, float v) { As[i] = v; });
   staged_copy<16, float>(128 * BP, tid,
       [&](int i) { const int o = i / BP, k = i - o * BP; const bool ok = k < bands;
@@ -51,17 +55,19 @@ __global__ __launch_bounds__(256) void spe_fwd_kernel(const float* __restrict__ 
 }
 
 hipError_t launch_spe_fwd(int nets, int n, int bands, const float* sn, const float* w, const float* b,
-                          long long pstride, float* y, hipStream_t st) {
+                          long long pstride, float* y, hipStream_t st, const long long* rows, long long sn_ns) {
   const int BP = (bands + 2) | 1;
   const size_t lds = (size_t)160 * BP * 4;
   if (lds > LDS_MAX) return hipErrorInvalidValue;
   static DevOnce attr_once;
   {
-    hipError_t e = ensure_max_lds(attr_once, spe_fwd_kernel);
+    hipError_t e = ensure_max_lds(attr_once, spe_fwd_kernel<false>, spe_fwd_kernel<true>);
     if (e != hipSuccess) return e;
   }
   dim3 grid((n + 31) / 32, FD / 128, nets);
-  hipLaunchKernelGGL(spe_fwd_kernel, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands);
+  const long long ns = sn_ns < 0 ? (long long)n * bands : sn_ns;
+  if (rows != nullptr) hipLaunchKernelGGL(spe_fwd_kernel<true>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns);
+  else hipLaunchKernelGGL(spe_fwd_kernel<false>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns);
   return hipGetLastError();
 }
 

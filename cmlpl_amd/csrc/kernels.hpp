@@ -125,9 +125,13 @@ hipError_t launch_conv3_fused(int nets, int n, int C, int H, int W, const XSrc& 
                               const float* bias, long long bias_ns, float* out, uint8_t* mask_out,
                               const FwdTail* tail /* or null */, hipStream_t st, float* xn_out = nullptr);
 bool conv3_infer_ok(int H, int W, int C, int K);
+// nn == null: one network, pixels pix0 .. pix0 + n - 1 (cmlpl_infer_cube).  Else (cmlpl_infer_pixels) `nets` networks in
+// grid.y -- their parameters / packed weights param_ns / packed_ns floats apart, t.y / t.logits / labels_out [nets][n] rows --
+// and, when pix is set, sample s = scene pixel pix[s].
+struct InferNets { int nets; long long param_ns, packed_ns; const long long* pix; };
 hipError_t launch_conv3_infer(int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
                               const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
-                              long long* labels_out, hipStream_t st);
+                              long long* labels_out, hipStream_t st, const InferNets* nn = nullptr);
 bool conv3_fused_bwd_ok(int H, int W, int C, int rows);
 // the head / conv2 part of the backward in the same per-sample workgroup: see conv3_bwd_head
 struct BwdHead {
@@ -184,8 +188,11 @@ bool spe_fused_ok(int bands);
 hipError_t launch_spe_fused(int nets, int n, int bands, const XSrc& xs, const float* w /* feat_spe.weight, canonical */,
                             const float* bias, long long p_ns, float* y, float* sn, const long long* labels,
                             float* labels_f, int bt, hipStream_t st);
+// rows != null: output row r is row rows[r] of `sn`; sn_ns: per-net stride of `sn` in floats (< 0: n * bands, a block per
+// network; 0: both networks read the same rows)
 hipError_t launch_spe_fwd(int nets, int n, int bands, const float* sn, const float* w, const float* b,
-                          long long pstride, float* y, hipStream_t st);
+                          long long pstride, float* y, hipStream_t st, const long long* rows = nullptr,
+                          long long sn_ns = -1);
 // feat = y / ||y||, ynorm = ||y|| in a launch of its own (bit-identical to the per-sample forward's tail); feat_ns: per-net stride of `feat`
 hipError_t launch_feat_norm(int nets, int n, const float* y, float* ynorm, float* feat, long long feat_ns, hipStream_t st);
 // C[b][i][j] = scale * sum_r A[b][r][i] * B[b][r][j]  (+ optional colsum of A into bias[b][i])

@@ -469,6 +469,40 @@ int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const floa
                      int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
                      float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Validation on a pixel list -- ADDED AFTER ABI 6 WITHOUT A VERSION BUMP: the three entry points below are pure
+ * additions (no struct changes size, no existing prototype changes, a binding finds them by symbol), and the version
+ * number is what callers built against ABI 6 compare; a binding that needs them checks that the symbols resolve (as
+ * cmlpl_amd/_lib.py does: a library without them is refused whole, not half-used).
+ *
+ * cmlpl_infer_pixels: cmlpl_infer_cube for a LIST of scene pixels and for both networks in one launch chain (the
+ * reference's per-epoch test_acc, tools/hyper_tools.py:372-413, needs the labelled test pixels only: 42,776 of PaviaU's
+ * 207,400).  Item i is scene pixel d_pix[i] (row-major index into d_cube [rows][cols][C]; any order, repeats allowed); its
+ * spectrum is row d_spec_row[i] of d_spectra [.][bands], or row i when d_spec_row is NULL (a split's compact rows).
+ * d_spec_row == d_pix with the whole scene's spectra reproduces cmlpl_infer_cube's addressing.  Networks: `nets` (1 or 2)
+ * flat parameter / packed-weight blocks param_stride / packed_stride floats apart (cmlpl_layout / cmlpl_pack_weights);
+ * d_labels [nets][n] int64, d_logits [nets][n][K] or NULL.  Each item is one workgroup's arithmetic on its own window and
+ * row: the results equal cmlpl_infer_cube's at the same pixels bit for bit, whatever the order of the list.
+ * The indices are DATA ON THE DEVICE: this call cannot check them without a synchronisation.  The caller checks their
+ * range once, where a list is set up (cmlpl_amd.evaluate.Evaluator does); the window gather clamps d_pix[i] into the
+ * scene, d_spec_row is used as it is.
+ * Workspace: cmlpl_eval_workspace_bytes(shape, nets, n), 0 for a shape this entry point does not take.
+ * Returns CMLPL_E_ARG (null pointer, n < 1, nets outside 1..2, rows / cols smaller than half a window, a stride shorter
+ * than a network), CMLPL_E_SHAPE (as cmlpl_infer_cube: more than 256 window pixels -- cmlpl_extract_patches takes the same
+ * list, cmlpl_basenet2_fwd the patches), CMLPL_E_WORKSPACE -- all before any launch.
+ *
+ * cmlpl_confusion: d_cm [nets][K][K] int64 += counts of (row = d_truth[i], column = d_pred[net][i]) over i < n; K <= 64.
+ * It ACCUMULATES (chunks of a list, the shares of several ranks): hipMemsetAsync starts a fresh matrix.  Items whose
+ * truth is outside 0 .. K - 1 are counted in d_ignored[0] (optional, accumulated too) and nowhere else.  Integer atomics:
+ * exact, and the same bytes on every run.
+ * Neither call synchronises or allocates: both can be captured in a graph. */
+size_t cmlpl_eval_workspace_bytes(const cmlpl_shape* shape, int nets, int n);
+int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                       const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                       const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                       int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream);
+int cmlpl_confusion(const int64_t* d_pred, int nets, const int64_t* d_truth, int n, int K, int64_t* d_cm,
+                    int64_t* d_ignored, void* stream);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the

@@ -18,6 +18,9 @@ Differences from the reference that are deliberate, MI355X-first choices:
   * ``--windows cube``: no window tensor at all -- the scene cube (cube.npy, 50 MB for PaviaU) is uploaded once and every
     step, eager or replayed, on one or several GPUs, gathers its windows from it (the cube-fed step of cmlpl_amd); the
     default ``--windows split`` cuts each split's windows once and keeps them resident (2 x 960 MB at the defaults).
+  * ``--eval_every N``: after every N-th epoch both networks are scored on the TEST split's pixels, on the device
+    (cmlpl_amd.evaluate.Evaluator: the list-fed eval forward from the scene cube, both networks in one call, the confusion
+    matrices counted there); one line per network with OA / AA / Kappa, the curve to ``--save_eval``.  Default 0: never.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -91,7 +94,7 @@ def main(args, make_engine=None, device=None):
         num_classes, num_features = shape[4], shape[3]
         # (--windows cube / --synthetic_scene: both splits are seeded pixels of ONE synthetic scene, the evaluation's)
         from_scene = cube_fed or args.synthetic_scene
-        whole = SyntheticScene(shape, 64, 64, seed=3) if (from_scene or not args.no_eval) else None   # a 64 x 64 scene cube, every pixel a test pixel
+        whole = SyntheticScene(shape, 64, 64, seed=3) if (from_scene or not args.no_eval or args.eval_every > 0) else None   # a 64 x 64 scene cube, every pixel a test pixel
         labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=whole if from_scene else None)
         unlabeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'unlabel', seed=2, scene=whole if from_scene else None)
         if not args.no_eval:
@@ -141,6 +144,23 @@ def main(args, make_engine=None, device=None):
     else:
         lab_loader = DeviceLoader(labeled.device_arrays(device), bt, gen)
         unl_loader = DeviceLoader(unlabeled.device_arrays(device), btu, gen)
+    evaluator, eval_log, eval_cms = None, [], []          # --eval_every: (epoch, [net][OA, AA, Kappa]) and the matrices
+    if args.eval_every > 0 and rank == 0:
+        # the test split registered once: its pixels, spectra and labels beside the resident cube (rank 0 evaluates, as
+        # after the last epoch; its own generators: no draw of the training streams is consumed)
+        from cmlpl_amd.evaluate import Evaluator
+        if args.synthetic:
+            cube_ev = cube_kw["cube"] if cube_fed else whole.cube.to(device).contiguous()
+            Xt, Yt = whole.X.to(device).contiguous(), whole.Y.to(device).contiguous()
+            pix_t = torch.arange(len(whole), dtype=torch.int64, device=device)
+        else:
+            test_split = HSIDataSet(int(args.dataID), 'test')
+            if test_split.scene_cube is None:
+                raise SystemExit("--eval_every needs cube.npy + scene.json in the dataset directory (sample_generation.py)")
+            cube_ev = cube_kw["cube"] if cube_fed else \
+                torch.from_numpy(np.ascontiguousarray(test_split.scene_cube, dtype=np.float32)).to(device)
+            Xt, Yt, pix_t = test_split.scene_arrays(device)
+        evaluator = Evaluator(NetShape(*shape), cube_ev, Xt, Yt, pix_t)
     num_batches = min(len(lab_loader), len(unl_loader))              # train.py:134
     num_steps = args.num_epochs * num_batches                        # train.py:135
     loss_hist = np.zeros((num_steps, 5))                             # train.py:136
@@ -204,6 +224,17 @@ def main(args, make_engine=None, device=None):
                                             np.mean(w[:, 0]), np.mean(w[:, 1]), np.mean(w[:, 2]), np.mean(w[:, 3]),
                                             np.mean(w[:, 4]) * 100))
         read_back()                   # rows of the epoch's tail (num_batches % print_per_batches steps)
+        if evaluator is not None and (epoch + 1) % args.eval_every == 0:
+            # between two steps (or replays), on their stream: launches + one read-back of nets x K x K integers
+            cms = evaluator.evaluate((eng, None)).cpu().numpy()
+            row = []
+            for net in range(2):
+                OA, Kappa, _, AA = evaluator.metrics(cms[net])
+                row.append((OA, AA, Kappa))
+                print('Epoch %d/%d: validation%s OA = %.2f AA = %.2f Kappa = %.2f' %
+                      (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
+            eval_log.append((epoch + 1, row))
+            eval_cms.append(cms)
         if epoch == 0:                # (the read-back has drained the device) what follows runs on warm kernels
             t_warm, steps_warm = time.time(), eng.step_count
     if device.type == "cuda":
@@ -219,6 +250,14 @@ def main(args, make_engine=None, device=None):
             np.save(args.save_loss_hist, loss_hist)
         if args.report_memory and device.type == "cuda":
             print('peak device memory: %d bytes' % torch.cuda.max_memory_allocated(device))
+    if rank == 0 and eval_log:
+        curve = np.array([r for _, r in eval_log])                    # [evaluations][nets][OA, AA, Kappa]
+        epochs = np.array([e for e, _ in eval_log])
+        for net in range(2):
+            best = int(np.argmax(curve[:, net, 0]))                   # (the first of equal bests)
+            print('best validation%s: epoch %d OA = %.2f' % ('' if net == 0 else '1', epochs[best], curve[best, net, 0] * 100))
+        if args.save_eval:
+            np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms))
     if rank == 0 and not args.no_eval:
         # whole-image inference + accuracy (train.py:291-306).  The scene stays in HBM as its cube and the forward gathers
         # the windows itself (cmlpl_infer_cube): no 19.9 GB patch tensor, no DataLoader (train.py:291-294 streams the
@@ -257,6 +296,11 @@ def main(args, make_engine=None, device=None):
             print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
             print('producerA%s:' % tag, producerA * 100)
             print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
+            if eval_log and eval_log[-1][0] == args.num_epochs:
+                # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
+                same = eval_log[-1][1][net][0] == OA
+                print('validation check%s: matrix OA %s whole-image OA (%.6f / %.6f)' %
+                      (tag, '==' if same else '!=', eval_log[-1][1][net][0] * 100, OA * 100))
     if world > 1 and make_engine is None:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -300,6 +344,12 @@ def build_parser():
                              "every step gathers its windows from it (needs cube.npy + scene.json, or --synthetic)")
     parser.add_argument('--synthetic_scene', action='store_true',
                         help='--synthetic: draw both splits from one seeded synthetic scene (implied by --windows cube)')
+    parser.add_argument('--eval_every', type=int, default=0,
+                        help='score both networks on the test split after every N-th epoch, on the device (0: never); '
+                             'real data needs cube.npy + scene.json')
+    parser.add_argument('--save_eval', default=None,
+                        help='--eval_every: write the curve [evaluations][nets][OA, AA, Kappa], its epochs and the '
+                             'confusion matrices as .npz')
     parser.add_argument('--report_memory', action='store_true',
                         help="print the process's peak allocated device memory after the last step")
     return parser

@@ -36,6 +36,7 @@ EXPORTS = (
     "cmlpl_backward_weights", "cmlpl_dist_step", "cmlpl_rccl_bind", "cmlpl_rccl_unbind", "cmlpl_debug_two_piece",
     "cmlpl_scene_workspace_bytes", "cmlpl_scene_gram", "cmlpl_scene_project",
     "cmlpl_eval_workspace_bytes", "cmlpl_infer_pixels", "cmlpl_confusion",      # added after ABI 6, no bump (include/cmlpl.h)
+    "cmlpl_packed_flag_offset",
 )
 
 KERNEL_NAMES = ("augment", "conv0_fwd", "conv1_fwd", "conv2_fwd", "spe_fwd", "head_fwd", "loss", "head_bwd",
@@ -235,6 +236,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_eval_workspace_bytes.restype = sz
     lib.cmlpl_infer_pixels.argtypes = [SP, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.cmlpl_confusion.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    lib.cmlpl_packed_flag_offset.argtypes = [SP, C.POINTER(i64)]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

@@ -172,6 +172,14 @@ int cmlpl_layout(const cmlpl_shape* shape, cmlpl_layout_t* out) {
   return 0;
 }
 
+int cmlpl_packed_flag_offset(const cmlpl_shape* shape, int64_t* off_floats) {
+  Dims d;
+  if (!off_floats) return CMLPL_E_ARG;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  *off_floats = pack_off_h2flag(d.C, d.bands);
+  return 0;
+}
+
 size_t cmlpl_workspace_bytes(const cmlpl_shape* shape, int nets, int n, int bank_rows) {
   Dims d;
   if (!make_dims(shape, &d) || nets < 1 || nets > 2 || n < 1) return 0;

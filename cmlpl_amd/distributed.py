@@ -441,6 +441,10 @@ class DistTrainEngine(TrainEngine):
         self._io = None             # cmlpl_dist_step's records (see _step_io)
 
     # ------------------------------------------------------------------ helpers
+    def _set_seed(self) -> None:
+        self._args = None           # (the stage calls' argument tuples and cmlpl_dist_step's record carry the seed)
+        self._io = None
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -777,6 +781,7 @@ class DistStepGraph:
         io.seed = eng.seed
         io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
         self._io = io
+        eng._captured = True
         cap = torch.cuda.Stream(device=dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
         self.handles = {}

@@ -94,6 +94,9 @@ class TrainEngine:
         self._checked = None
         self._checked_cube = None
         self._graph = None          # weak reference to the StepGraph that has programmed replays (see step())
+        self._captured = False      # a StepGraph of this engine exists: its kernels' arguments hold the seed
+        self._flag_off = None       # offset of the range flag words inside a network's packed block (asked of the library)
+        self._saved_flags = None    # load_checkpoint_state: flag words to OR back in behind the next full pack
 
     @property
     def scalars(self) -> torch.Tensor:
@@ -131,12 +134,7 @@ class TrainEngine:
         self._packed_dirty = True
 
     def state_dict(self, net: int) -> "OrderedDict[str, torch.Tensor]":
-        order = ["conv0", "conv1", "conv2", "feat_spe", "feat_ss", "feat_ss2", "feat_ss3", "classifier"]
-        out = OrderedDict()
-        for mod in order:                      # registration order of tools/models.py:102-127
-            for leaf in ("weight", "bias"):
-                out[f"{mod}.{leaf}"] = self.view(self.params, net, f"{mod}.{leaf}").detach().clone()
-        return out
+        return OrderedDict((k, self.view(self.params, net, k).detach().clone()) for k in self.state_dict_keys())
 
     def grad(self, net: int, key: str) -> torch.Tensor:
         return self.view(self.grads, net, key)
@@ -161,6 +159,99 @@ class TrainEngine:
                        self.lib.cmlpl_pack_weights(C.byref(self.cshape), 2, _ptr(self.params), self.P,
                                                    _ptr(self.packed), stream))
             self._packed_dirty = False
+            if self._saved_flags is not None:
+                # the full pack after load_checkpoint_state: it has just set the range flag words anew from the current
+                # weights; a flag the saved run had raised earlier (sticky until a full pack) is OR-ed back in
+                self._flag_words().bitwise_or_(self._saved_flags)
+                self._saved_flags = None
+
+    # ------------------------------------------------------------------ checkpoints (cmlpl_amd/checkpoint.py)
+    def _flag_words(self) -> torch.Tensor:
+        """the two-piece range flag words of both networks, [2][16] int32: a view of the tail of ``packed``"""
+        if self._flag_off is None:
+            off = C.c_int64()
+            _lib.check("cmlpl_packed_flag_offset", self.lib.cmlpl_packed_flag_offset(C.byref(self.cshape), C.byref(off)))
+            self._flag_off = int(off.value)
+        return self.packed[:, self._flag_off:].view(torch.int32)
+
+    def _refuse_pending(self, what: str) -> None:
+        g = self._graph() if self._graph is not None else None
+        if g is not None and g.pending > 0:
+            # the programmed rows were formed from counters and bank pointers the replays have yet to catch up with
+            raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them before {what}")
+
+    def identity(self) -> Dict[str, object]:
+        """what a checkpoint must agree with to be loaded here (batch capacities GLOBAL: a sharded engine's are per rank)"""
+        from .checkpoint import make_identity
+        W = getattr(self, "world", 1)
+        return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
+                             self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION)
+
+    def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
+        """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
+        scratch; ``packed`` is derived, but for its range flag words), as a dict of tensors and plain values --
+        ``cmlpl_amd.checkpoint.save`` writes it, ``load_checkpoint_state`` takes it back.  Host copies by default (one
+        synchronisation); ``on_device``: stream-ordered device copies and NO synchronisation (train.py --save_best keeps
+        the best-validated state this way), into the tensors of ``into`` -- an earlier on-device state of this engine --
+        when given.  Raises while programmed graph replays are pending."""
+        self._refuse_pending("checkpoint_state()")
+        self._ensure_packed(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))   # (flag words of THESE weights)
+        src = dict(params=self.params, m=self.m, v=self.v, bank_feats=self.bank_feats, bank_probs=self.bank_probs,
+                   range_flags=self._flag_words())
+        for net, key in enumerate(("Base", "Base1")):
+            src[key] = OrderedDict((k, self.view(self.params, net, k)) for k in self.state_dict_keys())
+        if into is not None:
+            st = into
+            for k, t in src.items():
+                if isinstance(t, dict):
+                    for kk, tt in t.items():
+                        st[k][kk].copy_(tt)
+                else:
+                    st[k].copy_(t)
+        else:
+            take = (lambda t: t.detach().clone()) if on_device else (lambda t: t.detach().cpu())
+            st = {k: (OrderedDict((kk, take(tt)) for kk, tt in t.items()) if isinstance(t, dict) else take(t))
+                  for k, t in src.items()}
+        st.update(ptr=[int(self.ptr[0]), int(self.ptr[1])], adam_t=int(self.adam_t), step_count=int(self.step_count),
+                  seed=int(self.seed), identity=self.identity())
+        return st
+
+    def load_checkpoint_state(self, state: dict) -> None:
+        """Continue from ``state`` (``checkpoint_state()``, or a file through ``cmlpl_amd.checkpoint.load``): copied INTO
+        the engine's tensors (a captured graph holds their addresses).  ValueError naming every field of the identity
+        record that differs (``cmlpl_amd.checkpoint.check_identity``).  The packed weights are rebuilt by the next step's
+        full pack, behind which the saved range flag words are OR-ed back in.  Raises while replays are pending."""
+        from .checkpoint import check_identity
+        self._refuse_pending("load_checkpoint_state()")
+        check_identity(state["identity"], self.identity())
+        flags = state["range_flags"]
+        if tuple(flags.shape) != tuple(self._flag_words().shape) or flags.dtype != torch.int32:
+            raise ValueError(f"range_flags: need int32 {tuple(self._flag_words().shape)}, the checkpoint has "
+                             f"{flags.dtype} {tuple(flags.shape)}")
+        for name in ("params", "m", "v", "bank_feats", "bank_probs"):
+            dst, t = getattr(self, name), state[name]
+            if tuple(t.shape) != tuple(dst.shape) or t.dtype != dst.dtype:
+                raise ValueError(f"{name}: need {dst.dtype} {tuple(dst.shape)}, the checkpoint has {t.dtype} {tuple(t.shape)}")
+        for name in ("params", "m", "v", "bank_feats", "bank_probs"):
+            getattr(self, name).copy_(state[name])
+        self.ptr = [int(state["ptr"][0]), int(state["ptr"][1])]
+        if int(state["seed"]) != self.seed:
+            if self._captured:
+                raise ValueError(f"seed: file {int(state['seed'])}, here {self.seed} -- and a step of this engine has been "
+                                 "captured with its own (load before capturing, or construct the engine with the file's seed)")
+            self.seed = int(state["seed"])
+            self._set_seed()
+        self.adam_t, self.step_count = int(state["adam_t"]), int(state["step_count"])
+        self._saved_flags = flags.to(self.device).clone()
+        self._packed_dirty = True
+
+    def _set_seed(self) -> None:
+        self._io.seed = self.seed
+
+    def state_dict_keys(self):
+        """the 16 keys in the registration order of tools/models.py:102-127"""
+        order = ["conv0", "conv1", "conv2", "feat_spe", "feat_ss", "feat_ss2", "feat_ss3", "classifier"]
+        return [f"{mod}.{leaf}" for mod in order for leaf in ("weight", "bias")]
 
     # ------------------------------------------------------------------ the step
     def _check_rows(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx):
@@ -439,6 +530,7 @@ class StepGraph:
         io.apply_update = 1
         io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
         self._io = io
+        eng._captured = True
         # the launchers set their kernels' LDS attributes on first use, which must not happen inside a capture
         if eng.step_count == 0:
             raise RuntimeError("run one eager TrainEngine.step() before capturing (kernel attributes are set lazily)")

@@ -503,6 +503,14 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
 int cmlpl_confusion(const int64_t* d_pred, int nets, const int64_t* d_truth, int n, int K, int64_t* d_cm,
                     int64_t* d_ignored, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- where the two-piece RANGE FLAG words of one network lie inside
+ * its packed block: *off_floats = their offset in floats from the block's start; they run to packed_total (16 floats =
+ * 64 bytes, word 0 carries the flag).  A full pack (cmlpl_pack_weights) zeroes them and raises them anew from the
+ * current weights; the Adam step's incremental re-pack only ever raises them.  A checkpoint therefore saves these
+ * words and ORs them back in behind the full pack that follows a load (cmlpl_amd/checkpoint.py), or a resumed run
+ * could take other convolution loops than the run it continues.  Host arithmetic only; CMLPL_E_ARG / CMLPL_E_SHAPE. */
+int cmlpl_packed_flag_offset(const cmlpl_shape* shape, int64_t* off_floats);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the

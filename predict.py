@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Classify a scene with a trained pair of networks: the third stage after ``sample_generation.py`` and ``train.py``.
+
+    python train.py --dataID 1 --save_ckpt run.ckpt
+    python predict.py --ckpt run.ckpt --dataID 1 --out labels.npy
+
+The window shape and the class count come from the checkpoint (cmlpl_amd.checkpoint); the scene is the dataset
+directory's ``cube.npy`` + ``scene.json`` (``HSIDataSet(.., 'wholeset').cube_source``), labelled on the device by
+``cmlpl_infer_cube`` through ``tools.hyper_tools.test_whole`` -- the end-of-run evaluation of ``train.py``
+(``train.evaluate_whole``), without a training engine.  ``--out`` receives the int64 label map [rows * cols]
+(``--net both``: [2][rows * cols]); when the directory has ``test_array.npy`` / ``Y.npy`` the ``Result:`` / ``producerA`` /
+``AA`` lines of ``train.py`` are printed.  ``--synthetic SHAPE`` labels the seeded synthetic scene that
+``train.py --synthetic`` evaluates on (datasets are not shipped)."""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from cmlpl_amd import checkpoint
+from hsi_loader import HSIDataSet, SyntheticScene
+from train import DATASETS, SYNTH, evaluate_whole
+
+
+def main(args, device=None):
+    if device is None:
+        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+        torch.cuda.set_device(device)
+    ck = checkpoint.load(args.ckpt)
+    s, hp = ck["identity"]["shape"], ck["identity"]["hp"]
+    shape = (s["C"], s["H"], s["W"], s["bands"], s["K"])
+    test_array = Y_test = None
+    if args.synthetic:
+        if tuple(SYNTH[args.synthetic]) != shape:
+            raise SystemExit("--synthetic %s has shape %s, the checkpoint's networks take %s" %
+                             (args.synthetic, SYNTH[args.synthetic], shape))
+        whole = SyntheticScene(shape, 64, 64, seed=3)            # the scene train.py --synthetic evaluates on
+        Y_test, test_array = whole.Y.numpy(), np.arange(len(whole))
+    else:
+        if DATASETS[int(args.dataID)] != (shape[4], shape[3]):
+            raise SystemExit("--dataID %d has %d classes / %d bands, the checkpoint's networks take %d / %d" %
+                             (args.dataID, *DATASETS[int(args.dataID)], shape[4], shape[3]))
+        whole = HSIDataSet(int(args.dataID), 'wholeset')
+        if os.path.exists(whole.root + 'test_array.npy') and os.path.exists(whole.root + 'Y.npy'):
+            test_array = np.load(whole.root + 'test_array.npy')
+            Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
+    which = [0, 1] if args.net == 'both' else [int(args.net)]
+    preds = evaluate_whole(shape, whole, [(k, ck["Base" if k == 0 else "Base1"]) for k in which], device,
+                           synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"],
+                           val_batch_size=args.val_batch_size, test_array=test_array, Y_test=Y_test)
+    labels = np.stack([preds[k] for k in which]).astype(np.int64)
+    labels = labels if args.net == 'both' else labels[0]
+    if args.out:
+        np.save(args.out, labels)
+    return labels
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument('--ckpt', required=True, help='a checkpoint of train.py --save_ckpt / --save_best')
+    parser.add_argument('--dataID', type=int, default=1)
+    parser.add_argument('--net', choices=('0', '1', 'both'), default='0', help='Base (0), Base1 (1) or both')
+    parser.add_argument('--out', default=None, help='write the int64 label map as .npy ([rows*cols]; both: [2][rows*cols])')
+    parser.add_argument('--val_batch_size', type=int, default=512,
+                        help='batch of the loader fall-back (a dataset directory without cube.npy)')
+    parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
+                        help="label the seeded synthetic scene of this shape (train.py --synthetic's evaluation scene)")
+    return parser
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

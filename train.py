@@ -79,6 +79,77 @@ def shard_plan(bt, btu, world):
     return bt_l, btu_l
 
 
+RUN_FLAGS = ("lr", "num_epochs", "thr", "alpha", "queue_batch", "temperature", "dropout", "noise",
+             "labeled_batch_size", "unlabeled_batch_size", "num_unlabel")
+
+
+def run_record(args, hp, shape, from_scene):
+    """what two legs of one run (--resume) must agree on: the hyper-parameter flags (--num_epochs too: the threshold
+    schedule adap_thr(epoch) divides by it), the batch sizes and the data.  --graph, --windows, --eval_every,
+    --print_per_batches and the number of GPUs may differ."""
+    rec = {k: getattr(args, k) for k in RUN_FLAGS}
+    rec.update(shape=[int(v) for v in shape], data=("synthetic %s%s" % (args.synthetic, " scene" if from_scene else ""))
+               if args.synthetic else "dataID %d" % int(args.dataID))
+    return rec
+
+
+def run_differences(saved, mine):
+    return ["%s: file %r, here %r" % (k, saved.get(k), mine[k]) for k in mine if saved.get(k) != mine[k]]
+
+
+def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
+                   test_array=None, Y_test=None, resident_cube=None, last_eval=None):
+    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index, state_dict)]: the end of a
+    training run, and all of predict.py.  Returns {network index: int64 label per scene pixel}.
+    The scene stays in HBM as its cube and the forward gathers the windows itself (cmlpl_infer_cube): no 19.9 GB patch
+    tensor, no DataLoader (train.py:291-294 streams the materialised patches).  Window shapes the per-sample forward does
+    not take, or a dataset directory without the cube, fall back to the loader.  The source is built ONCE for all
+    networks, and its load time is printed (the reference's "inference time" includes streaming the data).
+    ``test_array`` / ``Y_test``: the labelled test pixels and their classes -- the ``Result:`` lines are printed when
+    they are given.  ``resident_cube``: the scene already on the device (a cube-fed run evaluates on the cube it trained
+    from).  ``last_eval``: the [net][OA, AA, Kappa] row of --eval_every when it scored the same parameters."""
+    from cmlpl_amd.infer import infer_supported
+    num_features, num_classes = shape[3], shape[4]
+    t_src = time.time()
+    source = None
+    if infer_supported(NetShape(*shape)):
+        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
+            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
+    if source is None:
+        if synthetic:      # (cut the scene's windows on the device, then the reference's loader path)
+            from cmlpl_amd.patches import extract_patches
+            cs = whole.cube_source(device)
+            XPw = extract_patches(cs.cube, torch.arange(len(whole), device=device), shape[1]).cpu()
+            source = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(XPw, whole.X),
+                                                 batch_size=val_batch_size, shuffle=False)
+        else:
+            source = torch.utils.data.DataLoader(whole, batch_size=val_batch_size, shuffle=False)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    print('evaluation source ready in %.3f s' % (time.time() - t_src))
+    preds = {}
+    for net, sd in nets:
+        model = BaseNet2(num_features=num_features, dropout=dropout, num_classes=num_classes,
+                         in_channels=shape[0], window=shape[1]).to(device)
+        model.load_state_dict(sd)
+        t1 = time.time()
+        pred = preds[net] = test_whole(model, source, print_per_batches=10 ** 9)
+        print('inference time == %.3f s' % (time.time() - t1))
+        if test_array is None:
+            continue
+        OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
+        tag = '' if net == 0 else '1'
+        print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
+        print('producerA%s:' % tag, producerA * 100)
+        print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
+        if last_eval is not None:
+            # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
+            same = last_eval[net][0] == OA
+            print('validation check%s: matrix OA %s whole-image OA (%.6f / %.6f)' %
+                  (tag, '==' if same else '!=', last_eval[net][0] * 100, OA * 100))
+    return preds
+
+
 def main(args, make_engine=None, device=None):
     """``make_engine`` / ``device`` are test hooks (tests/test_train_loop_gloo.py runs this loop as two gloo ranks
     on CPU around a stand-in engine); the product path leaves them None."""
@@ -100,6 +171,7 @@ def main(args, make_engine=None, device=None):
         if not args.no_eval:
             Y_test, test_array = whole.Y.numpy(), np.arange(len(whole))
     else:
+        from_scene = False
         num_classes, num_features = DATASETS[int(args.dataID)]
         labeled = HSIDataSet(int(args.dataID), 'label', max_iters=args.num_unlabel)
         unlabeled = HSIDataSet(int(args.dataID), 'unlabel', max_iters=args.num_unlabel, num_unlabel=args.num_unlabel)
@@ -129,6 +201,24 @@ def main(args, make_engine=None, device=None):
     eng.init_params_default(1088)
 
     gen = torch.Generator().manual_seed(1088)                        # same permutations on every rank
+    if args.save_best and args.eval_every <= 0:
+        raise SystemExit("--save_best keeps the best-VALIDATED epoch: it needs --eval_every")
+    if args.ckpt_every > 0 and not args.save_ckpt:
+        raise SystemExit("--ckpt_every needs --save_ckpt PATH")
+    resumed = None
+    if args.resume:
+        # every rank reads the same file (the state is replicated); what the file was trained with must be what this
+        # run would train with -- the engine checks its own identity record, the flags are compared here
+        from cmlpl_amd import checkpoint
+        resumed = checkpoint.load(args.resume)
+        diff = run_differences(resumed["extra"].get("run", {}), run_record(args, hp, shape, from_scene))
+        if diff:
+            raise SystemExit("--resume %s: this run differs from the one that wrote the file -- %s" % (args.resume, "; ".join(diff)))
+        try:
+            eng.load_checkpoint_state(resumed)
+        except ValueError as e:
+            raise SystemExit("--resume %s: %s" % (args.resume, e))
+        gen.set_state(resumed["extra"]["gen_state"])
     cube_kw = {}
     if cube_fed:
         # the scene goes to the GPU ONCE; a split is its spectra, labels and one scene pixel per row -- no windows
@@ -164,7 +254,32 @@ def main(args, make_engine=None, device=None):
     num_batches = min(len(lab_loader), len(unl_loader))              # train.py:134
     num_steps = args.num_epochs * num_batches                        # train.py:135
     loss_hist = np.zeros((num_steps, 5))                             # train.py:136
-    index_i = -1
+    start_epoch = 0
+    if resumed is not None:
+        ex = resumed["extra"]
+        start_epoch = int(ex["epoch"])
+        if ex["num_batches"] != num_batches or start_epoch > args.num_epochs:
+            raise SystemExit("--resume %s: the file has %d epochs of %d steps, this run %d epochs of %d" %
+                             (args.resume, start_epoch, ex["num_batches"], args.num_epochs, num_batches))
+        done = start_epoch * num_batches
+        loss_hist[:done] = ex["loss_hist"].numpy()
+        if evaluator is not None:      # (the curve so far: a leg without --eval_every leaves a gap, not an error)
+            eval_log = [(int(e), [[float(v) for v in net] for net in row]) for e, row in zip(ex["eval_epochs"], ex["eval_curve"].tolist())]
+            eval_cms = [cm for cm in ex["eval_cms"].numpy()]
+    index_i = start_epoch * num_batches - 1
+    best_oa, best_state, best_extra = None, None, None               # --save_best
+    if eval_log:
+        best_oa = max(row[0][0] for _, row in eval_log)
+
+    def run_extra(epochs_done):
+        """what this driver adds to a checkpoint written after ``epochs_done`` epochs"""
+        done = epochs_done * num_batches
+        return dict(epoch=epochs_done, num_batches=num_batches, loss_hist=torch.from_numpy(loss_hist[:done].copy()),
+                    eval_epochs=[e for e, _ in eval_log],
+                    eval_curve=torch.tensor([r for _, r in eval_log], dtype=torch.float64).reshape(len(eval_log), 2, 3),
+                    eval_cms=torch.from_numpy(np.stack(eval_cms)) if eval_cms else torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64),
+                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items()},
+                    run=run_record(args, hp, shape, from_scene), world=world)
     pending = []                      # loss_hist rows of the steps run since the last read-back of the device ring
 
     def read_back():
@@ -178,8 +293,9 @@ def main(args, make_engine=None, device=None):
     gbt, gbtu = bt // world, btu // world                              # rows of a replayed step on this rank
     graph = None
     t_start = time.time()
-    t_warm, steps_warm = t_start, 0
-    for epoch in range(args.num_epochs):                             # train.py:146
+    steps_before = eng.step_count                                    # (--resume: the steps of the earlier legs)
+    t_warm, steps_warm = t_start, steps_before
+    for epoch in range(start_epoch, args.num_epochs):                # train.py:146
         batches = list(zip(lab_loader, unl_loader))                  # (offset, size) pairs; draws this epoch's permutations
         if use_graph and graph is not None:
             # the whole epoch's per-step scalars go to the device table at once; full batches are replays
@@ -235,19 +351,33 @@ def main(args, make_engine=None, device=None):
                       (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
             eval_log.append((epoch + 1, row))
             eval_cms.append(cms)
-        if epoch == 0:                # (the read-back has drained the device) what follows runs on warm kernels
+            if args.save_best and (best_oa is None or row[0][0] > best_oa):
+                # network 0's best validation so far (the first of equals): the state is copied on the device, behind
+                # the step that produced it on the stream -- no synchronisation, no file until the run is over
+                best_oa = row[0][0]
+                best_state = eng.checkpoint_state(on_device=True, into=best_state)
+                best_extra = run_extra(epoch + 1)
+        if rank == 0 and args.save_ckpt and (epoch + 1 == args.num_epochs or
+                                             (args.ckpt_every > 0 and (epoch + 1) % args.ckpt_every == 0)):
+            # an epoch boundary: every row is read back, no replay is pending
+            from cmlpl_amd import checkpoint
+            checkpoint.save(args.save_ckpt.replace('{epoch}', str(epoch + 1)), eng.checkpoint_state(), run_extra(epoch + 1))
+        if epoch == start_epoch:      # (the read-back has drained the device) what follows runs on warm kernels
             t_warm, steps_warm = time.time(), eng.step_count
     if device.type == "cuda":
         torch.cuda.synchronize()
     if rank == 0:
         steps = eng.step_count
         t_end = time.time()
-        print('training: %d steps in %.3f s' % (steps, t_end - t_start))
+        print('training: %d steps in %.3f s' % (steps - steps_before, t_end - t_start))
         if steps > steps_warm:        # the first epoch carries the one-time loading of the kernels
             print('after the first epoch: %d steps in %.3f s = %.4f ms/step' %
                   (steps - steps_warm, t_end - t_warm, (t_end - t_warm) / (steps - steps_warm) * 1e3))
         if args.save_loss_hist:
             np.save(args.save_loss_hist, loss_hist)
+        if best_state is not None:
+            from cmlpl_amd import checkpoint
+            checkpoint.save(args.save_best, best_state, best_extra)
         if args.report_memory and device.type == "cuda":
             print('peak device memory: %d bytes' % torch.cuda.max_memory_allocated(device))
     if rank == 0 and eval_log:
@@ -259,48 +389,10 @@ def main(args, make_engine=None, device=None):
         if args.save_eval:
             np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms))
     if rank == 0 and not args.no_eval:
-        # whole-image inference + accuracy (train.py:291-306).  The scene stays in HBM as its cube and the forward gathers
-        # the windows itself (cmlpl_infer_cube): no 19.9 GB patch tensor, no DataLoader (train.py:291-294 streams the
-        # materialised patches).  Window shapes the per-sample forward does not take, or a dataset directory without the
-        # cube, fall back to the loader.  The source is built ONCE for both networks, and its load time is printed
-        # (the reference's "inference time" includes streaming the data).
-        from cmlpl_amd.infer import infer_supported
-        t_src = time.time()
-        source = None
-        if infer_supported(NetShape(*shape)):
-            # (a cube-fed run evaluates on the cube it trained from: it is resident already)
-            res = cube_kw.get("cube")
-            source = whole.cube_source(device, resident_cube=res) if args.synthetic else \
-                whole.cube_source(device, dataID=args.dataID, resident_cube=res)
-        if source is None:
-            if args.synthetic:      # (cut the scene's windows on the device, then the reference's loader path)
-                from cmlpl_amd.patches import extract_patches
-                cs = whole.cube_source(device)
-                XPw = extract_patches(cs.cube, torch.arange(len(whole), device=device), shape[1]).cpu()
-                source = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(XPw, whole.X),
-                                                     batch_size=args.val_batch_size, shuffle=False)
-            else:
-                source = torch.utils.data.DataLoader(whole, batch_size=args.val_batch_size, shuffle=False)
-        if device.type == "cuda":
-            torch.cuda.synchronize()
-        print('evaluation source ready in %.3f s' % (time.time() - t_src))
-        for net in range(2):
-            model = BaseNet2(num_features=num_features, dropout=args.dropout, num_classes=num_classes,
-                             in_channels=shape[0], window=shape[1]).to(device)
-            model.load_state_dict(eng.state_dict(net))
-            t1 = time.time()
-            pred = test_whole(model, source, print_per_batches=10 ** 9)
-            OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
-            tag = '' if net == 0 else '1'
-            print('inference time == %.3f s' % (time.time() - t1))
-            print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
-            print('producerA%s:' % tag, producerA * 100)
-            print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
-            if eval_log and eval_log[-1][0] == args.num_epochs:
-                # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
-                same = eval_log[-1][1][net][0] == OA
-                print('validation check%s: matrix OA %s whole-image OA (%.6f / %.6f)' %
-                      (tag, '==' if same else '!=', eval_log[-1][1][net][0] * 100, OA * 100))
+        evaluate_whole(shape, whole, [(net, eng.state_dict(net)) for net in range(2)], device, synthetic=args.synthetic,
+                       dataID=args.dataID, dropout=args.dropout, val_batch_size=args.val_batch_size,
+                       test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"),
+                       last_eval=eval_log[-1][1] if eval_log and eval_log[-1][0] == args.num_epochs else None)
     if world > 1 and make_engine is None:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -350,6 +442,19 @@ def build_parser():
     parser.add_argument('--save_eval', default=None,
                         help='--eval_every: write the curve [evaluations][nets][OA, AA, Kappa], its epochs and the '
                              'confusion matrices as .npz')
+    parser.add_argument('--save_ckpt', default=None, metavar='PATH',
+                        help='write a checkpoint (cmlpl_amd.checkpoint: both networks, Adam state, banks, counters) after '
+                             'the last epoch; {epoch} in PATH is replaced by the 1-based epoch just finished')
+    parser.add_argument('--ckpt_every', type=int, default=0, metavar='N',
+                        help='--save_ckpt: also after every N-th epoch (0: only the last).  A save copies the state to the '
+                             'host and writes a 28 MB file: 12.8 ms at the B2 defaults on one MI355X, about the wall time '
+                             'of an EPOCH there (13.5 ms) -- every epoch doubles a run, every tenth adds a tenth')
+    parser.add_argument('--resume', default=None, metavar='PATH',
+                        help='load a checkpoint and continue with the epoch after it, up to --num_epochs (the hyper-parameter '
+                             'flags must be those of the file; --graph, --windows, --eval_every and the GPU count may differ)')
+    parser.add_argument('--save_best', default=None, metavar='PATH',
+                        help="--eval_every: keep the state of network 0's best-validated epoch (copied on the device when "
+                             "it is scored) and write it as a checkpoint after training")
     parser.add_argument('--report_memory', action='store_true',
                         help="print the process's peak allocated device memory after the last step")
     return parser

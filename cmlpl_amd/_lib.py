@@ -37,11 +37,13 @@ EXPORTS = (
     "cmlpl_scene_workspace_bytes", "cmlpl_scene_gram", "cmlpl_scene_project",
     "cmlpl_eval_workspace_bytes", "cmlpl_infer_pixels", "cmlpl_confusion",      # added after ABI 6, no bump (include/cmlpl.h)
     "cmlpl_packed_flag_offset",
+    "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
 )
+METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
 KERNEL_NAMES = ("augment", "conv0_fwd", "conv1_fwd", "conv2_fwd", "spe_fwd", "head_fwd", "loss", "head_bwd",
                 "cls_wgrad", "spe_wgrad", "conv2_dgrad", "conv2_wgrad", "conv2_wred", "conv1_dgrad", "conv1_wgrad",
-                "conv1_wred", "conv0_wgrad", "adam", "pack", "loss_graph", "loss_fin", "loss_dfeat", "cube_feed")
+                "conv1_wred", "conv0_wgrad", "adam", "pack", "loss_graph", "loss_fin", "loss_dfeat", "cube_feed", "cps_loss")
 
 
 class CmlplLibraryError(RuntimeError):
@@ -237,6 +239,9 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_infer_pixels.argtypes = [SP, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.cmlpl_confusion.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     lib.cmlpl_packed_flag_offset.argtypes = [SP, C.POINTER(i64)]
+    lib.cmlpl_cps_loss_workspace_bytes.argtypes = [SP, i32, i32]
+    lib.cmlpl_cps_loss_workspace_bytes.restype = sz
+    lib.cmlpl_cps_loss_fwd_bwd.argtypes = [SP, i32, i32, vp, vp, HP, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]
@@ -272,7 +277,7 @@ def load(path: str = LIB_PATH):
     for s in EXPORTS[1:]:
         if hasattr(lib, s) and s not in ("cmlpl_workspace_bytes", "cmlpl_loss_workspace_bytes", "cmlpl_ntxent_workspace_bytes",
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
-                     "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes"):
+                     "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

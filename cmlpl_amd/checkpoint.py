@@ -30,19 +30,31 @@ class CheckpointError(RuntimeError):
     """a file that is not a checkpoint of this format"""
 
 
-def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_hash: str, abi: int) -> Dict[str, Any]:
-    """the record ``check_identity`` compares: plain dicts and numbers (``NetShape`` / ``HyperParams`` by field)"""
+def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_hash: str, abi: int,
+                  method: str = "cmlpl") -> Dict[str, Any]:
+    """the record ``check_identity`` compares: plain dicts and numbers (``NetShape`` / ``HyperParams`` by field).  The
+    training ``method`` is part of it; a CMLPL record carries no ``method`` key (what it held before there was a second
+    method: such files still load, and a record without the key reads as ``cmlpl``)."""
     from dataclasses import asdict
-    return dict(shape={k: int(v) for k, v in asdict(shape).items()},
-                hp={k: (int(v) if isinstance(v, int) and not isinstance(v, bool) else float(v)) for k, v in asdict(hp).items()},
-                bt=int(bt_global), btu=int(btu_global), Q=int(Q), source_hash=str(source_hash), abi=int(abi))
+    rec = dict(shape={k: int(v) for k, v in asdict(shape).items()},
+               hp={k: (int(v) if isinstance(v, int) and not isinstance(v, bool) else float(v)) for k, v in asdict(hp).items()},
+               bt=int(bt_global), btu=int(btu_global), Q=int(Q), source_hash=str(source_hash), abi=int(abi))
+    if method != "cmlpl":
+        rec["method"] = str(method)
+    return rec
+
+
+def identity_method(rec: Dict[str, Any]) -> str:
+    return str(rec.get("method", "cmlpl"))
 
 
 def identity_differences(saved: Dict[str, Any], mine: Dict[str, Any]) -> List[str]:
-    """every field of the two identity records that differs, as ``name: file X, here Y`` (``shape.C``, ``hp.lr``, ``bt``,
-    ``btu``, ``Q``, ``abi``); ``source_hash`` is not among them (another build of the same ABI computes the same step up
+    """every field of the two identity records that differs, as ``name: file X, here Y`` (``method``, ``shape.C``, ``hp.lr``,
+    ``bt``, ``btu``, ``Q``, ``abi``); ``source_hash`` is not among them (another build of the same ABI computes the same step up
     to what its kernels changed: ``check_identity`` warns)."""
     out = []
+    if identity_method(saved) != identity_method(mine):
+        out.append(f"method: file {identity_method(saved)!r}, here {identity_method(mine)!r}")
     for group in ("shape", "hp"):
         a, b = saved.get(group, {}), mine.get(group, {})
         for k in sorted(set(a) | set(b)):

@@ -824,6 +824,40 @@ int cmlpl_loss_fwd_bwd(const cmlpl_shape* shape, int bt, int btu, const float* d
                    d_dfeat, d_probs, d_workspace, workspace_bytes, stream, nullptr);
 }
 
+}  // extern "C"
+namespace {
+// the CPS loss block (cps_loss.hip); sel: labels by index / device-side logging row
+int cps_loss_impl(const cmlpl_shape* shape, int bt, int btu, const float* d_logits, const int64_t* d_labels,
+                  const cmlpl_hparams* hp, float* d_scalars, float* d_dlogits, int64_t* d_pseudo, void* d_workspace,
+                  size_t workspace_bytes, void* stream, const RowSel* sel) {
+  Dims d;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  if (bt < 1 || btu < 1 || !d_logits || !d_labels || !hp || !d_scalars || !d_dlogits || !d_pseudo || !d_workspace)
+    return CMLPL_E_ARG;
+  if (cps_loss_ws_floats(bt, btu) * 4 > workspace_bytes) return CMLPL_E_WORKSPACE;
+  CpsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.logits = d_logits; a.labels = (const long long*)d_labels;
+  if (sel != nullptr) a.sel = *sel;
+  a.bt = bt; a.btu = btu; a.K = d.K; a.w = hp->w_mutual;
+  a.dlogits = d_dlogits; a.scalars = d_scalars; a.pseudo = (long long*)d_pseudo;
+  hipStream_t st = (hipStream_t)stream;
+  return TIMED(CMLPL_K_CPS_LOSS, chk(launch_cps_loss(a, (float*)d_workspace, st)));
+}
+}  // namespace
+extern "C" {
+size_t cmlpl_cps_loss_workspace_bytes(const cmlpl_shape* shape, int bt, int btu) {
+  Dims d;
+  if (!make_dims(shape, &d) || bt < 1 || btu < 1) return 0;
+  return cps_loss_ws_floats(bt, btu) * 4;
+}
+int cmlpl_cps_loss_fwd_bwd(const cmlpl_shape* shape, int bt, int btu, const float* d_logits, const int64_t* d_labels,
+                           const cmlpl_hparams* hp, float* d_scalars, float* d_dlogits, int64_t* d_pseudo,
+                           void* d_workspace, size_t workspace_bytes, void* stream) {
+  return cps_loss_impl(shape, bt, btu, d_logits, d_labels, hp, d_scalars, d_dlogits, d_pseudo, d_workspace,
+                       workspace_bytes, stream, nullptr);
+}
+
 int cmlpl_dist_unpack(const cmlpl_shape* shape, int world, int bt_local, int btu_local, const float* d_gathered_feat,
                       const float* d_gathered_logits, float* d_logits_g, float* d_feat_g, int64_t* d_labels_g, void* stream) {
   Dims d;
@@ -873,6 +907,8 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
       !io->d_packed || !io->d_logits || !io->d_feat || !io->d_scalars || !io->d_labels)
     return CMLPL_E_ARG;
   if (io->apply_update && (!io->d_m || !io->d_v)) return CMLPL_E_ARG;
+  if (io->reserved != CMLPL_METHOD_CMLPL && io->reserved != CMLPL_METHOD_CPS) return CMLPL_E_ARG;
+  const bool cps = io->reserved == CMLPL_METHOD_CPS;
   const int n = io->bt + io->btu;
   NetWs nw;
   if (!carve_net(d, 2, n, (char*)io->d_workspace, &nw)) return CMLPL_E_SHAPE;
@@ -892,12 +928,19 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
                          io->step, io->d_logits, io->d_feat, nullptr, io->d_workspace, io->workspace_bytes, stream, dyn)))
     return rc;
   const RowSel sel = batch_sel(&batch, dyn);
-  if ((rc = loss_both(shape, io->bt, io->btu, io->d_logits, io->d_feat, io->d_labels, &io->banks,
+  if (cps) {
+    // the CPS loss block: one launch; its pseudo-labels take the front of the (otherwise unused) probability region,
+    // its row table the loss workspace; no embedding gradient exists, so the backward runs with d_dfeat = null
+    if ((rc = cps_loss_impl(shape, io->bt, io->btu, io->d_logits, io->d_labels, hp, io->d_scalars, sw.dlogits,
+                            (int64_t*)sw.probs, sw.loss,
+                            loss_ws_floats(n, n, n, d.K, io->banks.Q > n ? io->banks.Q : n) * 4, stream, &sel)))
+      return rc;
+  } else if ((rc = loss_both(shape, io->bt, io->btu, io->d_logits, io->d_feat, io->d_labels, &io->banks,
                       io->smooth, io->adap_mask, hp, io->d_scalars, sw.dlogits, sw.dfeat, sw.probs, sw.loss,
                       loss_ws_floats(n, n, n, d.K, io->banks.Q > n ? io->banks.Q : n) * 4, stream, &sel)))
     return rc;
   if ((rc = backward_impl(shape, hp, &batch, &sh, io->d_params, io->d_packed, io->d_dropmask, train, io->seed,
-                          io->step, sw.dlogits, sw.dfeat, io->d_grads, L.param_total, io->d_workspace,
+                          io->step, sw.dlogits, cps ? nullptr : sw.dfeat, io->d_grads, L.param_total, io->d_workspace,
                           io->workspace_bytes, stream, dyn, io->d_dyn_cursor))) return rc;
   if (io->apply_update)   // (device-side scalars: the by-value step count is not used, any valid one will do)
     return adam_impl(shape, 2, io->d_params, L.param_total, io->d_grads, L.param_total, io->d_m, io->d_v,
@@ -1255,6 +1298,12 @@ int cmlpl_debug_region(const cmlpl_shape* shape, int nets, int n, const char* na
     if (!strcmp(t.nm, name)) { *byte_offset = (size_t)((const char*)t.p - base); *bytes = t.b; return 0; }
   if (!strcmp(name, "xn") && nets == 2) {   // the step's augmented patch rows [2][n][C*H*W] (cmlpl_forward keeps them for cmlpl_backward)
     *byte_offset = w.bytes; *bytes = (size_t)2 * n * d.C * d.HW * 4;
+    return 0;
+  }
+  if (!strcmp(name, "cps_pseudo") && nets == 2) {   // a CPS step's pseudo-labels: int64 [2][btu] at the region's start (n covers them)
+    StepWs sw;
+    carve_step(d, n, n, base + w.bytes, &sw);
+    *byte_offset = (size_t)((const char*)sw.probs - base); *bytes = (size_t)2 * n * 8;
     return 0;
   }
   return CMLPL_E_ARG;

@@ -320,6 +320,17 @@ hipError_t loss_prepare_capture();   // kernel attributes a captured step may ne
 hipError_t launch_loss_graph(const LossArgs& a, hipStream_t st);
 hipError_t launch_loss_dfeat(const LossArgs& a, hipStream_t st);
 
+// ---- cps_loss.hip  (the loss block of the cross-pseudo-supervision baseline, reference trian_CPS.py:234-258)
+struct CpsArgs {
+  const float* logits; const long long* labels;   // [2][bt+btu][K]; [bt] through sel (labels by index)
+  RowSel sel;                                     // + device-side step scalars: the logging row
+  int bt, btu, K; float w;                        // w: weight of the cross loss (hp->w_mutual)
+  float* dlogits; float* scalars; long long* pseudo;   // [2][bt+btu][K]; [16] (ring base under replay); [2][btu]
+  float* rowloss; int* ticket;                    // workspace (set by launch_cps_loss)
+};
+size_t cps_loss_ws_floats(int bt, int btu);
+hipError_t launch_cps_loss(const CpsArgs& a, float* ws, hipStream_t st);
+
 // ---- ntxent.hip
 size_t ntxent_ws_floats(int B, int D);
 hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T, float* loss, float* gi, float* gj,

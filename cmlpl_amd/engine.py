@@ -23,6 +23,14 @@ _CHECK_INDICES = os.environ.get("CMLPL_CHECK_INDICES", "0") not in ("", "0")
 
 SCALAR_NAMES = ("ctr_s", "total_s", "cls_s", "con_s", "acc", "total_w", "cls_w", "con_w", "ctr_w",
                 "n_mask_w", "n_mask_s", "n_pos", "n_neg")
+METHODS = tuple(_lib.METHODS)       # "cmlpl" (reference train.py), "cps" (reference trian_CPS.py)
+CPS_W_CROSS = 0.1                   # weight of the cross loss, the literal of trian_CPS.py:245,248
+
+
+def check_method(method: str) -> str:
+    if method not in _lib.METHODS:
+        raise ValueError(f"method {method!r}: one of {', '.join(METHODS)}")
+    return method
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -43,17 +51,26 @@ class TrainEngine:
     (``queue_size = 5 * labeled_batch_size * 2``).  Bank writes wrap modulo the bank
     size where the reference's slice-assign would raise; the pointer advance is the
     reference literal 256 (``hp.bank_step``) -- see DESIGN.md "memory bank".
+
+    ``method="cps"``: the cross-pseudo-supervision baseline (reference trian_CPS.py) on the same two networks -- the
+    step is forward -> CPS loss (one launch) -> backward -> Adam; the banks stay allocated and untouched, ``epoch`` /
+    ``batch_index`` of ``step`` play no part, ``hp.w_mutual`` is set to the reference's cross-loss weight 0.1, and
+    ``loss_row`` / ``loss_window`` give the reference's row ``[con, total, cls, con, acc]`` (trian_CPS.py:254-258).
     """
     takes_indices = True      # step(..., lab_idx=, unl_idx=): batches as row indices into the resident splits
     takes_cube = True         # step(None, Xl, Y, None, Xu, ..., cube=, lab_pix=, unl_pix=): windows gathered from the scene
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
-                 hist_rows: int = 1):
+                 hist_rows: int = 1, method: str = "cmlpl"):
+        self.method = check_method(method)
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("cmlpl_amd.TrainEngine needs a GPU (no CPU fallback)")
         self.shape, self.hp = shape, hp or HyperParams()
+        if self.method == "cps":
+            import dataclasses
+            self.hp = dataclasses.replace(self.hp, w_mutual=CPS_W_CROSS)
         self.device = torch.device(device)
         self.bt_max, self.btu_max = int(labeled_batch_size), int(unlabeled_batch_size)
         self.n_max = self.bt_max + self.btu_max
@@ -185,7 +202,7 @@ class TrainEngine:
         from .checkpoint import make_identity
         W = getattr(self, "world", 1)
         return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
-                             self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION)
+                             self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method)
 
     def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
         """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
@@ -361,12 +378,14 @@ class TrainEngine:
         io.d_logits, io.d_feat = self.logits.data_ptr(), self.feat.data_ptr()
         io.d_workspace, io.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         io.seed = self.seed
+        io.reserved = _lib.METHODS[self.method]        # cmlpl_step_io.reserved: the method (0 = CMLPL)
 
     def _advance(self, n, apply_update=True):
         """host copy of the step bookkeeping: bank pointers (train.py:234,237 -- ptr1 follows ptr0, reference quirk
         kept), Adam step, step counter"""
-        p0 = (self.ptr[0] + self.hp.bank_step) % self.Q
-        self.ptr = [p0, (p0 + self.hp.bank_step) % self.Q]
+        if self.method == "cmlpl":        # (CPS has no memory bank: its pointers stay where they are)
+            p0 = (self.ptr[0] + self.hp.bank_step) % self.Q
+            self.ptr = [p0, (p0 + self.hp.bank_step) % self.Q]
         if apply_update:
             self.adam_t += 1
         self.step_count += 1
@@ -435,6 +454,7 @@ class TrainEngine:
         _lib.check("cmlpl_train_step",
                    self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
         self._advance(n, apply_update)
+        self._last_btu = btu
 
     def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
                 cube=None, lab_pix=None, unl_pix=None) -> "StepGraph":
@@ -465,8 +485,20 @@ class TrainEngine:
         return dict(zip(SCALAR_NAMES, vals))
 
     def loss_row(self):
-        """[loss_contrast, total_loss, cls_loss, con_loss, acc] -- loss_hist row, train.py:274-278."""
-        return self.scalars[:5].tolist()
+        """[loss_contrast, total_loss, cls_loss, con_loss, acc] -- loss_hist row, train.py:274-278.  CPS: the row of
+        trian_CPS.py:254-258, whose column 0 repeats the cross loss."""
+        row = self.scalars[:5].tolist()
+        if self.method == "cps":
+            row[0] = row[3]
+        return row
+
+    def pseudo_labels(self) -> torch.Tensor:
+        """CPS: the hard labels of the last step, int64 [2][btu] = (Base's targets = argmax of Base1's logits, Base1's
+        targets = argmax of Base's) -- a view of the workspace (trian_CPS.py:238-239)."""
+        if self.method != "cps":
+            raise RuntimeError("pseudo_labels(): a CPS engine's output")
+        btu = self._last_btu
+        return self.debug_region("cps_pseudo", torch.int64)[: 2 * btu].view(2, btu)
 
     def loss_window(self, k: int):
         """loss_hist[index_i-k+1 : index_i+1] (train.py:285-289) as a float64 numpy array [k,5]: the rows of the
@@ -475,7 +507,10 @@ class TrainEngine:
             raise ValueError(f"window of {k} steps not held (hist_rows={self.hist_rows}, steps={self.step_count})")
         idx = [(self.step_count - k + j) % self.hist_rows for j in range(k)]
         rows = self.scalar_hist[torch.tensor(idx, device=self.device)]
-        return self._reduce_rows(rows)[:, :5].double().cpu().numpy()
+        out = self._reduce_rows(rows)[:, :5].double().cpu().numpy()
+        if self.method == "cps":
+            out[:, 0] = out[:, 3]          # trian_CPS.py:254: column 0 repeats the cross loss
+        return out
 
     def _reduce_rows(self, rows: torch.Tensor) -> torch.Tensor:
         return rows
@@ -606,6 +641,7 @@ class StepGraph:
         _lib.check("cmlpl_step_graph_launch", eng.lib.cmlpl_step_graph_launch(self.handle, stream))
         eng._cur_row = eng.step_count % eng.hist_rows
         eng._advance(self.bt + self.btu, True)
+        eng._last_btu = self.btu
         self.pending -= 1
 
     def close(self) -> None:

@@ -355,7 +355,8 @@ typedef struct cmlpl_step_io {
   int64_t adam_t;               /* 1-based                                               */
   uint64_t seed, step;          /* key / counter of the in-kernel random streams         */
   int32_t apply_update;         /* 0 = stop after the gradients                          */
-  int32_t reserved;
+  int32_t reserved;             /* the training METHOD (named after ABI 6, no bump: every earlier caller passes 0):
+                                   CMLPL_METHOD_CMLPL = 0, CMLPL_METHOD_CPS = 1 -- see cmlpl_cps_loss_fwd_bwd     */
   /* ABI 3 */
   const int64_t* d_lab_idx; const int64_t* d_unl_idx;   /* as in cmlpl_batch; NULL = consecutive rows */
   const cmlpl_dyn* d_dyn_table; int32_t* d_dyn_cursor;   /* NULL = the by-value fields above are used  */
@@ -511,6 +512,34 @@ int cmlpl_confusion(const int64_t* d_pred, int nets, const int64_t* d_truth, int
  * could take other convolution loops than the run it continues.  Host arithmetic only; CMLPL_E_ARG / CMLPL_E_SHAPE. */
 int cmlpl_packed_flag_offset(const cmlpl_shape* shape, int64_t* off_floats);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- the CROSS-PSEUDO-SUPERVISION baseline (reference trian_CPS.py:
+ * the same two BaseNet2, augmentation, dropout and Adam; only the loss block differs, :234-250).
+ *
+ * cmlpl_cps_loss_fwd_bwd: that loss block alone, forward + analytic backward, ONE kernel launch (behind a 4-byte memset).
+ *   d_logits [2][n][K]: net 0 = Base ("s"), net 1 = Base1 ("w"); rows [0,bt) labelled, [bt,n) unlabelled; d_labels [bt]
+ *   labelled row   : cls = CE(z, Y), dz = (softmax(z) - onehot(Y)) / bt                                    (:234-235)
+ *   unlabelled row : t_s = argmax z_w, t_w = argmax z_s -- torch.max's rule as in cmlpl_infer_cube: first maximum, a NaN
+ *                    counts as the maximum and the first NaN wins (:238-239); con_s = mean CE(z_s, t_s), con_w = mean
+ *                    CE(z_w, t_w); dz_s = w (softmax(z_s) - onehot(t_s)) / btu, dz_w likewise, w = hp->w_mutual (the
+ *                    reference's literal is 0.1, :245,248: cmlpl_amd.TrainEngine(method="cps") sets it)
+ *   outputs        : d_dlogits [2][n][K]; d_pseudo int64 [2][btu] = {t_s, t_w};
+ *                    d_scalars[16] in the slots of cmlpl_loss_fwd_bwd = {0, total_s, cls_s, con_s, acc, total_w, cls_w,
+ *                    con_w, 0, btu, btu, 0, 0, AGREE, 0, 0}: total = cls + w con, acc = share of labelled rows net 1
+ *                    gets right (:258), AGREE = number of unlabelled rows with t_s == t_w.
+ *   No memory bank, no threshold, no contrastive term and NO gradient into the embedding: the backward of a CPS step
+ *   takes d_dfeat = NULL (cmlpl_backward's "may be NULL = zero").  The scalar sums are folded in a fixed order (no float
+ *   atomics): the same bytes on every run and under graph replay.
+ * The whole step (cmlpl_train_step / cmlpl_step_graph_create with cmlpl_step_io.reserved = CMLPL_METHOD_CPS): forward ->
+ *   this loss -> backward (d_dfeat NULL) -> Adam.  io->banks are neither read nor written (only banks.Q sizes the
+ *   workspace as before), smooth / adap_mask are ignored, d_feat is still written by the forward; under replay the
+ *   logging row and the Adam scalars come from the cmlpl_dyn table as for CMLPL.  The step's pseudo-labels lie in the
+ *   workspace: cmlpl_debug_region(shape, 2, n, "cps_pseudo").  Another value of `reserved`: CMLPL_E_ARG. */
+enum { CMLPL_METHOD_CMLPL = 0, CMLPL_METHOD_CPS = 1 };
+size_t cmlpl_cps_loss_workspace_bytes(const cmlpl_shape* shape, int bt, int btu);
+int cmlpl_cps_loss_fwd_bwd(const cmlpl_shape* shape, int bt, int btu, const float* d_logits, const int64_t* d_labels,
+                           const cmlpl_hparams* hp, float* d_scalars, float* d_dlogits, int64_t* d_pseudo,
+                           void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the
@@ -620,7 +649,8 @@ enum {
   CMLPL_K_HEAD_FWD, CMLPL_K_LOSS, CMLPL_K_HEAD_BWD, CMLPL_K_CLS_WGRAD, CMLPL_K_SPE_WGRAD,
   CMLPL_K_CONV2_DGRAD, CMLPL_K_CONV2_WGRAD, CMLPL_K_CONV2_WRED, CMLPL_K_CONV1_DGRAD, CMLPL_K_CONV1_WGRAD,
   CMLPL_K_CONV1_WRED, CMLPL_K_CONV0_WGRAD, CMLPL_K_ADAM, CMLPL_K_PACK, CMLPL_K_LOSS2, CMLPL_K_LOSS_FIN,
-  CMLPL_K_LOSS_DFEAT, CMLPL_K_CUBE_FEED /* ABI 6: the cube-fed step's gather + augment launch */, CMLPL_K_COUNT
+  CMLPL_K_LOSS_DFEAT, CMLPL_K_CUBE_FEED /* ABI 6: the cube-fed step's gather + augment launch */,
+  CMLPL_K_CPS_LOSS /* after ABI 6: the CPS loss launch */, CMLPL_K_COUNT
 };
 int cmlpl_timing_begin(uint32_t kernel_mask, int max_launches);
 int cmlpl_timing_end(double* ms_sum /*[CMLPL_K_COUNT]*/, int64_t* launches /*[CMLPL_K_COUNT]*/);

@@ -21,6 +21,9 @@ Differences from the reference that are deliberate, MI355X-first choices:
   * ``--eval_every N``: after every N-th epoch both networks are scored on the TEST split's pixels, on the device
     (cmlpl_amd.evaluate.Evaluator: the list-fed eval forward from the scene cube, both networks in one call, the confusion
     matrices counted there); one line per network with OA / AA / Kappa, the curve to ``--save_eval``.  Default 0: never.
+  * ``--method cps``: the cross-pseudo-supervision baseline of the reference's ``trian_CPS.py`` instead of CMLPL, on the
+    same two networks, loaders, evaluation and checkpoints (one GPU; ``trian_CPS.py`` here presets it).  The printed
+    line is the shared one: for CPS ``loss_contrast`` repeats ``con_loss`` (trian_CPS.py:254).
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -88,9 +91,15 @@ def run_record(args, hp, shape, from_scene):
     schedule adap_thr(epoch) divides by it), the batch sizes and the data.  --graph, --windows, --eval_every,
     --print_per_batches and the number of GPUs may differ."""
     rec = {k: getattr(args, k) for k in RUN_FLAGS}
+    if run_method(args) != "cmlpl":       # (a CMLPL run's record is what it was before there was a second method)
+        rec["method"] = run_method(args)
     rec.update(shape=[int(v) for v in shape], data=("synthetic %s%s" % (args.synthetic, " scene" if from_scene else ""))
                if args.synthetic else "dataID %d" % int(args.dataID))
     return rec
+
+
+def run_method(args):
+    return getattr(args, "method", "cmlpl")
 
 
 def run_differences(saved, mine):
@@ -155,6 +164,10 @@ def main(args, make_engine=None, device=None):
     on CPU around a stand-in engine); the product path leaves them None."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    method = run_method(args)
+    if method != "cmlpl" and world > 1:      # before any device or communicator work
+        raise SystemExit(f"--method {method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
+                         f"{world} ranks)")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -197,7 +210,7 @@ def main(args, make_engine=None, device=None):
         eng = DistTrainEngine(NetShape(*shape), bt // world, btu // world, hp, device=device, seed=1088, hist_rows=ppb)
     else:
         from cmlpl_amd import TrainEngine
-        eng = TrainEngine(NetShape(*shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb)
+        eng = TrainEngine(NetShape(*shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=method)
     eng.init_params_default(1088)
 
     gen = torch.Generator().manual_seed(1088)                        # same permutations on every rank
@@ -211,6 +224,10 @@ def main(args, make_engine=None, device=None):
         # run would train with -- the engine checks its own identity record, the flags are compared here
         from cmlpl_amd import checkpoint
         resumed = checkpoint.load(args.resume)
+        file_method = checkpoint.identity_method(resumed["identity"])
+        if file_method != method:
+            raise SystemExit("--resume %s: the file was written by --method %s, this run is --method %s" %
+                             (args.resume, file_method, method))
         diff = run_differences(resumed["extra"].get("run", {}), run_record(args, hp, shape, from_scene))
         if diff:
             raise SystemExit("--resume %s: this run differs from the one that wrote the file -- %s" % (args.resume, "; ".join(diff)))
@@ -278,7 +295,7 @@ def main(args, make_engine=None, device=None):
                     eval_epochs=[e for e, _ in eval_log],
                     eval_curve=torch.tensor([r for _, r in eval_log], dtype=torch.float64).reshape(len(eval_log), 2, 3),
                     eval_cms=torch.from_numpy(np.stack(eval_cms)) if eval_cms else torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64),
-                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items()},
+                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items() if not (k == 'method' and v == 'cmlpl')},
                     run=run_record(args, hp, shape, from_scene), world=world)
     pending = []                      # loss_hist rows of the steps run since the last read-back of the device ring
 
@@ -423,6 +440,10 @@ def build_parser():
     parser.add_argument('--noise', type=float, default=0.5)
     parser.add_argument('--m', type=int, default=5, help='number of stochastic augmentations')
     # this build
+    parser.add_argument('--method', choices=('cmlpl', 'cps'), default='cmlpl',
+                        help="the training method: 'cmlpl' (the reference's train.py) or 'cps', the cross-pseudo-supervision "
+                             "baseline of its trian_CPS.py (labelled CE + 0.1 x each network's CE against the other's "
+                             "hard label; one GPU)")
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

@@ -1331,4 +1331,14 @@ int cmlpl_debug_two_piece(const cmlpl_shape* shape, int nets, int n) {
   return bits;
 }
 
+int cmlpl_debug_conv3_plan(const cmlpl_shape* shape, int nets, int n, int map, int mode, int* out3) {
+  Dims d;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  if (nets < 1 || nets > 2 || n < 1 || map < 0 || map > 1 || mode < 0 || mode > 1 || !out3) return CMLPL_E_ARG;
+  Conv3Plan pl;
+  if (!plan_conv3(mode, map ? d.H2 : d.H, map ? d.W2 : d.W, nets * n, &pl)) return CMLPL_E_SHAPE;
+  out3[0] = pl.S; out3[1] = pl.MTW; out3[2] = pl.nw;
+  return 0;
+}
+
 }  // extern "C"

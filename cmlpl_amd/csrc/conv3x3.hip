@@ -2991,7 +2991,9 @@ bool plan_conv3(int mode, int H, int W, int rows, Conv3Plan* p) {
     const double mfma = (double)per_cu * (split ? 0.25 : MTW);                     // tile-times on the busiest SIMD
     const double overhead = 0.45 * (double)waves_deep + (resident > 1 ? 0.0 : 0.15 * MTW);
     const double cost = mfma + overhead;
-    if (force_s ? (S == force_s) : (cost < best - 1e-9)) {
+    // (CMLPL_CONV3_S: the forced count, or -- on a map whose images or tiles do not fit that many -- the largest that
+    //  does: S only grows towards the break above, so the last one taken is it.  A 4 x 4 window holds 14, its 2 x 2 map 16.)
+    if (force_s ? (S <= force_s) : (cost < best - 1e-9)) {
       best = cost; p->S = S; p->MTW = split ? 0 : MTW; p->lds = lds; p->nw = 4; ok = true;
       // one sample per workgroup, one tile per wave, two workgroups per CU: the barrier-free tap loop (KSG)
       p->ks = (!split && S == 1 && MTW == 1 && resident >= 2 && switches().conv3_ks != 0) ? 1 : 0;

@@ -16,34 +16,42 @@ namespace cmlpl {
 
 // workgroup = 32 rows x 128 outputs; operands staged in LDS with odd row stride.
 // LIST: output row r is row rows[r] of `sn` (inference by pixel list); a template flag, so that the plain kernel is the code it was.
+// kc: bands per pass.  All of them (kc = bands) wherever the two operand tiles fit in LDS -- up to 253 bands, one pass, the
+// code it was; beyond, passes of kc = SPE_KC bands through the same tiles, the accumulators carried (the k-steps run in the
+// same order as in one pass).
+constexpr int SPE_KC = 252;    // even, and 160 rows x ((252 + 2) | 1) floats = 159.4 KiB
 template <bool LIST>
 __global__ __launch_bounds__(256) void spe_fwd_kernel(const float* __restrict__ sn, const float* __restrict__ w,
                                                       const float* __restrict__ b, long long pstride,
                                                       float* __restrict__ y, int n, int bands,
-                                                      const long long* __restrict__ rows, long long sn_ns) {
+                                                      const long long* __restrict__ rows, long long sn_ns, int kc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int net = blockIdx.z, r0 = blockIdx.x * 32, o0 = blockIdx.y * 128;
-  const int BP = (bands + 2) | 1;                   // odd stride, >= bands+1 (zero pad for odd bands)
+  const int BP = (kc + 2) | 1;                      // odd stride, >= kc+1 (zero pad for an odd band count)
   float* As = smem;                                 // [32][BP]
   float* Bs = smem + 32 * BP;                       // [128][BP]
   const float* S = sn + (long long)net * sn_ns;
   const float* W = w + (long long)net * pstride;
-  staged_copy<8, float>(32 * BP, tid,
-      [&](int i) { const int r = i / BP, k = i - r * BP; const bool ok = (k < bands) && (r0 + r < n);
-                   const long long row = (LIST && ok) ? rows[r0 + r] : (long long)(r0 + r);
-                   const float v = S[ok ? row * bands + k : 0]; return ok ? v : 0.f; },
-      [&](int i, float v) { As[i] = v; });
-  staged_copy<16, float>(128 * BP, tid,
-      [&](int i) { const int o = i / BP, k = i - o * BP; const bool ok = k < bands;
-                   const float v = W[(long long)(o0 + o) * bands + (ok ? k : 0)]; return ok ? v : 0.f; },
-      [&](int i, float v) { Bs[i] = v; });
-  __syncthreads();
   f32x16 acc = zero16();
   const float* ar = As + l31 * BP + hh;
   const float* br = Bs + (wave * 32 + l31) * BP + hh;
-  const int KK = (bands + 1) >> 1;
-  for (int kk = 0; kk < KK; ++kk) acc = mfma32(ar[2 * kk], br[2 * kk], acc);
+  for (int k0 = 0; k0 < bands; k0 += kc) {          // uniform; one pass up to 253 bands
+    const int kb = bands - k0 < kc ? bands - k0 : kc;
+    if (k0 > 0) __syncthreads();                    // every wave is done reading the previous pass's tiles
+    staged_copy<8, float>(32 * BP, tid,
+        [&](int i) { const int r = i / BP, k = i - r * BP; const bool ok = (k < kb) && (r0 + r < n);
+                     const long long row = (LIST && ok) ? rows[r0 + r] : (long long)(r0 + r);
+                     const float v = S[ok ? row * bands + k0 + k : 0]; return ok ? v : 0.f; },
+        [&](int i, float v) { As[i] = v; });
+    staged_copy<16, float>(128 * BP, tid,
+        [&](int i) { const int o = i / BP, k = i - o * BP; const bool ok = k < kb;
+                     const float v = W[(long long)(o0 + o) * bands + (ok ? k0 + k : 0)]; return ok ? v : 0.f; },
+        [&](int i, float v) { Bs[i] = v; });
+    __syncthreads();
+    const int KK = (kb + 1) >> 1;
+    for (int kk = 0; kk < KK; ++kk) acc = mfma32(ar[2 * kk], br[2 * kk], acc);
+  }
   const int o = o0 + wave * 32 + l31;
   const float bv = b[(long long)net * pstride + o];
   float* Y = y + (long long)net * n * FD;
@@ -56,7 +64,10 @@ __global__ __launch_bounds__(256) void spe_fwd_kernel(const float* __restrict__ 
 
 hipError_t launch_spe_fwd(int nets, int n, int bands, const float* sn, const float* w, const float* b,
                           long long pstride, float* y, hipStream_t st, const long long* rows, long long sn_ns) {
-  const int BP = (bands + 2) | 1;
+  if (bands < 1) return hipErrorInvalidValue;
+  // every band in one pass where the operand tiles fit (up to 253 bands); else passes of SPE_KC bands
+  const int kc = (size_t)160 * ((bands + 2) | 1) * 4 <= LDS_MAX ? bands : SPE_KC;
+  const int BP = (kc + 2) | 1;
   const size_t lds = (size_t)160 * BP * 4;
   if (lds > LDS_MAX) return hipErrorInvalidValue;
   static DevOnce attr_once;
@@ -66,8 +77,8 @@ hipError_t launch_spe_fwd(int nets, int n, int bands, const float* sn, const flo
   }
   dim3 grid((n + 31) / 32, FD / 128, nets);
   const long long ns = sn_ns < 0 ? (long long)n * bands : sn_ns;
-  if (rows != nullptr) hipLaunchKernelGGL(spe_fwd_kernel<true>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns);
-  else hipLaunchKernelGGL(spe_fwd_kernel<false>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns);
+  if (rows != nullptr) hipLaunchKernelGGL(spe_fwd_kernel<true>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns, kc);
+  else hipLaunchKernelGGL(spe_fwd_kernel<false>, grid, dim3(256), lds, st, sn, w, b, pstride, y, n, bands, rows, ns, kc);
   return hipGetLastError();
 }
 

@@ -236,7 +236,7 @@ struct Switches {
   int f16x2;                                                  // CMLPL_F16X2: 0 = conv1's tap loops of the four-tile per-sample kernels on three bf16 pieces like every other product (default 1: TWO fp16 pieces, three MFMAs per product, wherever the operands' ranges allow; 2 / 3: in the forward / the backward kernel only; 4: as 1, but an all-zero gradient image runs the loop instead of skipping it -- a measurement aid)
   int conv3_ks;                                               // CMLPL_CONV3_KS: 0 = the general 3x3 kernels always with LDS-staged tap weights (default 1: barrier-free loop at S = 1, one tile per wave)
   int ks8;                                                    // CMLPL_KS8: eight-wave per-sample workgroups never (0) / always (1) / when the grid fits the CUs (-1)
-  int conv3_s, conv0_dma, conv0_ps;                           // CMLPL_CONV3_S (0 = planner), CMLPL_CONV0_DMA (default 1), CMLPL_CONV0_PS (0 = planner)
+  int conv3_s, conv0_dma, conv0_ps;                           // CMLPL_CONV3_S (0 = planner; N = N samples per workgroup of the general 3x3 kernels, fewer on a map that cannot hold N), CMLPL_CONV0_DMA (default 1), CMLPL_CONV0_PS (0 = planner)
   int wgrad3_u, wgrad3_cspl, wgrad3_r, wgrad3_ru, wgrad3_rg, wgrad3_pg1, wgrad3_pg2, wgrad3_b3, wgrad3_pair;   // CMLPL_WGRAD3_*
   int pair_wide, pair_nbw, pair_mb, pair16, pair_tall;        // CMLPL_PAIR_WIDE / _TALL (-1 = planner), _NBW / _MB (0 = planner), CMLPL_PAIR16 (default 1)
   int dfeat_lds;                                              // CMLPL_DFEAT_LDS (-1 = wherever the operands allow, 0 = never)

@@ -75,11 +75,18 @@ class _BaseNet2Fn(torch.autograd.Function):
 
 class BaseNet2(nn.Module):
     """reference tools/models.py:97-152.  ``in_channels`` / ``window`` default to the reference
-    literals (60, 20); other values build the generalised net of SURVEY.md section 0."""
+    literals (60, 20); other values build the generalised net of SURVEY.md section 0.  ``window`` is the side of a
+    square window or an ``(H, W)`` pair (training forward / backward only: whole-image inference and the cube-fed
+    step take square windows and refuse another with CMLPL_E_SHAPE)."""
 
     def __init__(self, num_features=103, dropout=0, num_classes=0, in_channels=60, window=20):
         super().__init__()
-        H = W = int(window)
+        if isinstance(window, (tuple, list)):
+            if len(window) != 2:
+                raise ValueError(f"window: an integer or an (H, W) pair, got {window!r}")
+            H, W = int(window[0]), int(window[1])
+        else:
+            H = W = int(window)
         self.shape = NetShape(int(in_channels), H, W, int(num_features), int(num_classes))
         self.num_features, self.dropout, self.num_classes = num_features, dropout, num_classes
         # parameter containers only (never called): same names/shapes/default init as the reference

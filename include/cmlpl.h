@@ -678,6 +678,13 @@ int cmlpl_debug_reload_switches(void);
  * at run time.  Negative: CMLPL_E_*. */
 int cmlpl_debug_two_piece(const cmlpl_shape* shape, int nets, int n);
 
+/* Added after ABI 6, no bump (nothing existing moves).  Test aid: what the planner of the general 3x3 kernels decides, under the current switches, for one launch of a step on
+ * `nets` networks x n rows -- map 0: the window (conv1), 1: its pooled map (conv2); mode 0: forward, 1: data gradient.
+ * out3[0] = samples per workgroup, out3[1] = pixel tiles per wave (0: the one-tile kernel whose four waves split the
+ * channel halves), out3[2] = waves per workgroup.  The plan exists whether or not a fused per-sample kernel takes the
+ * launch instead.  Host arithmetic only.  CMLPL_E_ARG / CMLPL_E_SHAPE (no plan: the map does not fit). */
+int cmlpl_debug_conv3_plan(const cmlpl_shape* shape, int nets, int n, int map, int mode, int* out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,39 @@ def test_unfused_spectral_branch_passes_step_parity():
     _run(J_UNFSPE)
 
 
+_ENVELOPE = "tests/test_gpu_shape_envelope.py"
+FORCED_S = ("2", "3", "5", "16")
+J_FORCE_S = {s: _job("conv", f"conv3-s{s}", {"CMLPL_CONV3_S": s}, [_ENVELOPE, "-k", "forceS"]) for s in FORCED_S}
+
+
+@pytest.mark.parametrize("s", FORCED_S)
+def test_multi_sample_general_kernels_with_a_ragged_last_workgroup_pass_oracle_parity(s):
+    """CMLPL_CONV3_S: conv3x3_kernel<0 / 1, MTW> and the one-tile kernel with SEVERAL samples per workgroup -- what the
+    planner picks by itself only above 256 workgroups of a small map -- against the fp64 oracle on 4 x 4, 6 x 6 and 8 x 8
+    windows whose row counts are no multiple of the forced count (the `nvalid` clamp of the last workgroup); 16 is more
+    than a window's images fit in LDS, so conv1 runs with the most that do (14, 7 and 5) and the pooled maps with 16 and
+    14, one case with fewer rows than a workgroup holds.  The cases assert the plan they ran under."""
+    _run(J_FORCE_S[s])
+
+
+_B2_AND_WHOLE_SAMPLE = ["tests/test_gpu_ops.py", _ENVELOPE, "-k", "(forward_backward and B2) or fwdA"]
+J_NOTAIL = _job("conv", "tail-unfused", {"CMLPL_FUSE_TAIL": "0"}, _B2_AND_WHOLE_SAMPLE)
+J_NOBWD0 = _job("conv", "conv0-bwd-unfused", {"CMLPL_FUSE_CONV0_BWD": "0"}, _B2_AND_WHOLE_SAMPLE)
+
+
+def test_fused_conv0_conv1_with_the_general_tail_and_head_passes_parity():
+    """CMLPL_FUSE_TAIL=0 alone: launch_conv3_fused(..., tail = nullptr) + the general conv2 and head, and the fused conv1
+    data gradient + conv0 weight gradient behind the general head backward -- what 6 x 6, 7 x 7 and 8 x 16 windows take by
+    default -- at the headline shape and on every whole-sample case of the shape envelope (windows of more than 128
+    pixels fall to the general kernels: the eight-tile kernels exist with their tail only)"""
+    _run(J_NOTAIL)
+
+
+def test_general_backward_behind_the_fused_forward_passes_parity():
+    """CMLPL_FUSE_CONV0_BWD=0 alone: the whole-sample forward, then one backward launch per stage"""
+    _run(J_NOBWD0)
+
+
 J_B3ONLY = _job("conv", "three-piece-conv1", {"CMLPL_F16X2": "0"},
                 ["tests/test_gpu_ops.py", "tests/test_gpu_step.py", "-k", "(forward_backward and B2) or error_bound or b2_b256"])
 

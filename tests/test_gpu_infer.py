@@ -30,7 +30,10 @@ def _module(shape, seed, scale=1.0):
 
 @pytest.mark.parametrize("name,shape,rows,cols", [("B2", (103, 11, 11, 103, 9), 64, 48), ("B4", (200, 11, 11, 200, 16), 20, 24),
                                                   ("B5", (48, 15, 15, 48, 20), 24, 40), ("W8", (30, 8, 8, 30, 5), 16, 16),
-                                                  ("W12", (16, 12, 12, 16, 7), 14, 19), ("P", (60, 20, 20, 103, 9), 22, 26)])
+                                                  ("W12", (16, 12, 12, 16, 7), 14, 19), ("P", (60, 20, 20, 103, 9), 22, 26),
+                                                  # an even window of the four-tile kernel whose pooled map is odd (5 x 5), and
+                                                  # the eight-tile kernels with a 7 x 7 pooled map
+                                                  ("W10", (17, 10, 10, 17, 7), 13, 18), ("W14", (12, 14, 14, 12, 6), 15, 17)])
 def test_infer_cube_matches_the_oracle(name, shape, rows, cols):
     """labels equal the oracle's extract_patches -> basenet2_forward -> argmax wherever the top two logits are further
     apart than the logits tolerance; logits within 1e-4 (relative to the row's largest); every pixel of the scene, i.e.

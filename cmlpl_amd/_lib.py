@@ -38,7 +38,7 @@ EXPORTS = (
     "cmlpl_eval_workspace_bytes", "cmlpl_infer_pixels", "cmlpl_confusion",      # added after ABI 6, no bump (include/cmlpl.h)
     "cmlpl_packed_flag_offset",
     "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
-    "cmlpl_debug_conv3_plan",                                                    # added after ABI 6, no bump: a test aid
+    "cmlpl_debug_conv3_plan", "cmlpl_debug_route",                               # added after ABI 6, no bump: test aids
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
@@ -271,6 +271,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_rccl_unbind.argtypes = [C.POINTER(Collectives)]
     lib.cmlpl_debug_two_piece.argtypes = [SP, i32, i32]
     lib.cmlpl_debug_conv3_plan.argtypes = [SP, i32, i32, i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_route.argtypes = [SP, i32, i32, C.POINTER(i32)]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]

@@ -38,30 +38,22 @@ struct NetWs {
   size_t bytes;
 };
 
-// do ALL FOUR general 3x3 launches of a step (conv1 / conv2, forward / data gradient) take two-piece kernels?  Then each
-// leaves its samples' image maxima in the statistics table and the weight-gradient pair launch can scale by them.
-bool general_h2_stats(const Dims& d, int rows) {
-  return !conv3_fused_ok(d.H, d.W, d.C, rows) && !conv3_fused_bwd_ok(d.H, d.W, d.C, rows) &&
-         conv3_h2x_general(0, d.H, d.W, rows) && conv3_h2x_general(1, d.H, d.W, rows) &&
-         conv3_h2x_general(0, d.H2, d.W2, rows) && conv3_h2x_general(1, d.H2, d.W2, rows);
-}
+// which kernels a call on `nets` networks x n rows runs (kernels.hpp): computed once per entry point, read by everything below
+bool make_route(const Dims& d, int nets, int n, NetRoute* r) { return route_net(d.H, d.W, d.C, d.K, nets * n, r); }
 
 // per-net conv0 weight-gradient partials: one per sample when the fused data-gradient kernel produces them
-int conv0_partials(const Dims& d, int nets, int n) {
-  return conv3_fused_bwd_ok(d.H, d.W, d.C, nets * n) ? n : plan_conv0_wgrad_G(n, d.C, d.HW);
+int conv0_partials(const Dims& d, const NetRoute& r, int n) {
+  return r.conv0_partials_per_sample() ? n : plan_conv0_wgrad_G(n, d.C, d.HW);
 }
 
-bool carve_net(const Dims& d, int nets, int n, char* base, NetWs* w) {
+bool carve_net(const Dims& d, const NetRoute& r, int nets, int n, char* base, NetWs* w) {
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += up256(bytes); return p; };
   const size_t N = (size_t)nets * n;
   Wgrad3Plan w1, w2;
   bool wpair = false;
   if (!plan_wgrad3_both(nets, n, d.H, d.W, d.H2, d.W2, true, &w1, &w2, &wpair)) return false;
-  Conv3Plan c;
-  if (!plan_conv3(0, d.H, d.W, nets * n, &c) || !plan_conv3(1, d.H, d.W, nets * n, &c) ||
-      !plan_conv3(0, d.H2, d.W2, nets * n, &c) || !plan_conv3(1, d.H2, d.W2, nets * n, &c)) return false;
-  const int G0 = conv0_partials(d, nets, n);
+  const int G0 = conv0_partials(d, r, n);
   w->a0 = (float*)take(N * d.HW * 64 * 4);
   w->p1 = (float*)take(N * d.P2 * 64 * 4);
   w->m1 = (uint8_t*)take(N * d.P2 * 64);
@@ -183,8 +175,9 @@ int cmlpl_packed_flag_offset(const cmlpl_shape* shape, int64_t* off_floats) {
 size_t cmlpl_workspace_bytes(const cmlpl_shape* shape, int nets, int n, int bank_rows) {
   Dims d;
   if (!make_dims(shape, &d) || nets < 1 || nets > 2 || n < 1) return 0;
+  NetRoute r;
   NetWs nw;
-  if (!carve_net(d, nets, n, nullptr, &nw)) return 0;
+  if (!make_route(d, nets, n, &r) || !carve_net(d, r, nets, n, nullptr, &nw)) return 0;
   StepWs sw;
   carve_step(d, n, bank_rows, nullptr, &sw);
   return nw.bytes + sw.bytes + 256;
@@ -253,7 +246,7 @@ XSrc xsrc_raw(const cmlpl_batch* b, float sigma, uint64_t seed, uint64_t step, c
 }
 // parts: bit 0 = the spectral branch (feat_spe + ReLU; with early_feat also the L2 normalisation -> d_feat, ynorm),
 //        bit 1 = the convolution stack + head (-> d_logits; d_feat / ynorm too unless early_feat)
-int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
+int fwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
              const float* d_packed, const XSrc& xs, const XSrc* xspec, float* d_sn_out, const long long* d_labels, float* d_labels_f, const float* d_xn,
              const float* d_sn, const float* d_snT,
              const float* d_dropmask, float dropout_p, int train, uint64_t seed, uint64_t step,
@@ -261,7 +254,7 @@ int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
              float* xn_save = nullptr, int parts = 3, bool early_feat = false);
 // parts: bit 0 = the data-gradient chain + the 3x3 weight-gradient partials (needs d_dlogits; d_dfeat only when parts == 3),
 //        bit 1 = partial reduction + classifier / feat_spe weight gradients (parts == 2: dy first takes its d_dfeat part)
-int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
+int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
              const float* d_packed, const XSrc& xs, const float* d_xn, const float* d_sn, const float* d_dropmask,
              float dropout_p, int train, const float* d_dlogits, const float* d_dfeat, float* d_grads,
              int64_t grad_stride, const NetWs& w, hipStream_t st, int* dyn_cursor = nullptr, cmlpl_dyn* dyn_table = nullptr,
@@ -280,15 +273,16 @@ int cmlpl_basenet2_fwd(const cmlpl_shape* shape, int nets, int n, const float* d
       !d_workspace)
     return CMLPL_E_ARG;
   if (dropout_p < 0.f || dropout_p >= 1.f) return CMLPL_E_ARG;
+  NetRoute r;
   NetWs w;
-  if (!carve_net(d, nets, n, (char*)d_workspace, &w)) return CMLPL_E_SHAPE;
+  if (!make_route(d, nets, n, &r) || !carve_net(d, r, nets, n, (char*)d_workspace, &w)) return CMLPL_E_SHAPE;
   if (w.bytes > workspace_bytes) return CMLPL_E_WORKSPACE;
-  return fwd_core(d, L, nets, n, d_params, param_stride, d_packed,
+  return fwd_core(d, r, L, nets, n, d_params, param_stride, d_packed,
                   xsrc_plain(d_xn, nets, n, (long long)d.C * d.HW, seed, step, shard), nullptr, nullptr, nullptr, nullptr, d_xn, d_sn, d_snT, d_dropmask, dropout_p, train, seed, step, shard, d_logits, d_feat, w, (hipStream_t)stream);
 }
 
 namespace {
-int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
+int fwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
              const float* d_packed, const XSrc& xs, const XSrc* xspec, float* d_sn_out, const long long* d_labels, float* d_labels_f, const float* d_xn,
              const float* d_sn, const float* d_snT,
              const float* d_dropmask, float dropout_p, int train, uint64_t seed, uint64_t step,
@@ -316,7 +310,7 @@ int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
   if (!(parts & 2)) return 0;
   if (early_feat) d_feat = nullptr;           // the head skips its own normalisation
   if (shard && shard->nlab + shard->nunl != n) return CMLPL_E_ARG;
-  if (conv3_fused_tail_ok(d.H, d.W, d.C, nets * n, d.K)) {
+  if (r.fwd == ROUTE_A) {
     // the whole spatial forward + head of a sample in one workgroup: conv0 + conv1 + pool + conv2 + pool + flatten /
     // concat / dropout / classifier / L2-norm.  Needs the spectral branch output (launched above, same stream).
     FwdTail t;
@@ -327,20 +321,20 @@ int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
     t.w1h = d_packed + pack_off_h2(d.C, d.bands, 0); t.w1h_ns = pk_ns; t.h2flag = (const uint32_t*)(d_packed + pack_off_h2flag(d.C, d.bands));
     // every sample's largest |a0| / |p1| (this launch) and gradient operands (the backward's), for the two-piece
     // weight-gradient launch of the same step
-    if (conv3_h2x_both(d.H, d.W, d.C, nets * n, d.K)) t.hstat = w.hstat;
-    return TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3_fused(nets, n, d.C, d.H, d.W, xs, d_packed + pack_off_w0b3(d.C, d.bands),
+    if (r.stats) t.hstat = w.hstat;
+    return TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3_fused(r, nets, n, d.C, d.H, d.W, xs, d_packed + pack_off_w0b3(d.C, d.bands),
                                pk_ns, d_params + L.param_off[1], param_stride, w.a0, d_packed + pack_off_b3(d.C, d.bands, 0), pk_ns,
                                d_params + L.param_off[3], param_stride, w.p1, w.m1, &t, st, xn_save)));
   }
   // the general 3x3 launches on two fp16 pieces where their plans allow; when all four of a step do, each leaves its
-  // samples' image maxima for the two-piece weight gradient (general_h2_stats)
+  // samples' image maxima for the two-piece weight gradient (NetRoute::stats)
   const uint32_t* h2flag = (const uint32_t*)(d_packed + pack_off_h2flag(d.C, d.bands));
-  const bool gen_stats = general_h2_stats(d, nets * n);
-  if (conv3_fused_ok(d.H, d.W, d.C, nets * n)) {
+  uint32_t* const hstat = r.stats ? w.hstat : nullptr;
+  if (r.fwd == ROUTE_B) {
     // conv0 + conv1 in one launch, input rows taken where they lie and augmented in LDS: neither an augmented
     // copy of the input nor a0's round trip between the two convolutions touches HBM (a0 is still written once,
     // for the backward pass)
-    if ((rc = TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3_fused(nets, n, d.C, d.H, d.W, xs, d_packed + pack_off_w0b3(d.C, d.bands),
+    if ((rc = TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3_fused(r, nets, n, d.C, d.H, d.W, xs, d_packed + pack_off_w0b3(d.C, d.bands),
                                pk_ns, d_params + L.param_off[1], param_stride, w.a0, d_packed + pack_off_b3(d.C, d.bands, 0), pk_ns,
                                d_params + L.param_off[3], param_stride, w.p1, w.m1, nullptr, st, xn_save))))) return rc;
   } else {
@@ -354,13 +348,13 @@ int fwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
       if ((rc = TIMED(CMLPL_K_CONV0_FWD, chk(launch_conv0_fwd(nets, n, d.C, d.HW, d_xn, d_packed + pack_off_w0t(), pk_ns,
                                      d_params + L.param_off[1], param_stride, w.a0, st))))) return rc;
     }
-    const Conv3H2 h1 = {d_packed + pack_off_h2(d.C, d.bands, 0), pk_ns, h2flag, gen_stats ? w.hstat : nullptr, 0};
-    if ((rc = TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3(0, nets, n, d.H, d.W, w.a0, nullptr, d_packed + pack_off_b3(d.C, d.bands, 0),
-                               pk_ns, d_params + L.param_off[3], param_stride, w.p1, w.m1, st, &h1))))) return rc;
+    const Conv3H2 h1 = {d_packed + pack_off_h2(d.C, d.bands, 0), pk_ns, h2flag, hstat, 0};
+    if ((rc = TIMED(CMLPL_K_CONV1_FWD, chk(launch_conv3(r.plan[0], 0, nets, n, d.H, d.W, w.a0, nullptr, d_packed + pack_off_b3(d.C, d.bands, 0),
+                               pk_ns, d_params + L.param_off[3], param_stride, w.p1, w.m1, st, h1))))) return rc;
   }
-  const Conv3H2 h2 = {d_packed + pack_off_h2(d.C, d.bands, 2), pk_ns, h2flag, gen_stats ? w.hstat : nullptr, 1};
-  if ((rc = TIMED(CMLPL_K_CONV2_FWD, chk(launch_conv3(0, nets, n, d.H2, d.W2, w.p1, nullptr, d_packed + pack_off_b3(d.C, d.bands, 2),
-                             pk_ns, d_params + L.param_off[5], param_stride, w.p2, w.m2, st, &h2))))) return rc;
+  const Conv3H2 h2 = {d_packed + pack_off_h2(d.C, d.bands, 2), pk_ns, h2flag, hstat, 1};
+  if ((rc = TIMED(CMLPL_K_CONV2_FWD, chk(launch_conv3(r.plan[2], 0, nets, n, d.H2, d.W2, w.p1, nullptr, d_packed + pack_off_b3(d.C, d.bands, 2),
+                             pk_ns, d_params + L.param_off[5], param_stride, w.p2, w.m2, st, h2))))) return rc;
   const int nlab = shard ? shard->nlab : n, lab0 = shard ? shard->lab0 : 0;
   const int unl_base = shard ? shard->bt_g + shard->unl0 : n;
   return TIMED(CMLPL_K_HEAD_FWD, chk(launch_head_fwd(nets, n, d.P4, d.K, w.p2, w.y, d_dropmask, w.dropgen, dropout_p,
@@ -380,21 +374,23 @@ int cmlpl_basenet2_bwd(const cmlpl_shape* shape, int nets, int n, const float* d
   if (nets < 1 || nets > 2 || n < 1 || !d_params || !d_packed || !d_xn || !d_sn || !d_dlogits || !d_grads ||
       !d_workspace)
     return CMLPL_E_ARG;
+  NetRoute r;
   NetWs w;
-  if (!carve_net(d, nets, n, (char*)d_workspace, &w)) return CMLPL_E_SHAPE;
+  if (!make_route(d, nets, n, &r) || !carve_net(d, r, nets, n, (char*)d_workspace, &w)) return CMLPL_E_SHAPE;
   if (w.bytes > workspace_bytes) return CMLPL_E_WORKSPACE;
-  return bwd_core(d, L, nets, n, d_params, param_stride, d_packed,
+  return bwd_core(d, r, L, nets, n, d_params, param_stride, d_packed,
                   xsrc_plain(d_xn, nets, n, (long long)d.C * d.HW, 0, 0, nullptr), d_xn, d_sn, d_dropmask, dropout_p, train, d_dlogits, d_dfeat, d_grads, grad_stride, w, (hipStream_t)stream);
 }
 
 namespace {
-int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
+int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
              const float* d_packed, const XSrc& xs, const float* d_xn, const float* d_sn, const float* d_dropmask,
              float dropout_p, int train, const float* d_dlogits, const float* d_dfeat, float* d_grads,
              int64_t grad_stride, const NetWs& w, hipStream_t st, int* dyn_cursor, cmlpl_dyn* dyn_table, int parts) {
   const float* mask = (!train || dropout_p <= 0.f) ? nullptr : (d_dropmask ? d_dropmask : w.dropgen);
   int rc;
-  const bool fused_head = conv3_fused_head_ok(d.H, d.W, d.C, nets * n, d.K);
+  const bool fused_head = r.bwd == ROUTE_A;
+  uint32_t* const hstat = r.stats ? w.hstat : nullptr;
   // in two parts the head runs WITHOUT the feature gradients (dy is linear in them; launch_dy_fixup adds their share
   // in front of the feat_spe weight-gradient GEMM, bit-identically)
   const float* d_dfeat_head = (parts == 3) ? d_dfeat : nullptr;
@@ -427,15 +423,14 @@ int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
     hd.dy = w.dy; hd.dp2 = w.dp2; hd.dp1 = w.dp1; hd.K = d.K;
     hd.w1h = d_packed + pack_off_h2(d.C, d.bands, 1); hd.w1h_ns = L.packed_total;
     hd.h2flag = (const uint32_t*)(d_packed + pack_off_h2flag(d.C, d.bands));
-    const bool h2w = conv3_h2x_both(d.H, d.W, d.C, nets * n, d.K);
-    if (h2w) hd.hstat = w.hstat;
-    if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3_fused_bwd(nets, n, d.C, d.H, d.W, w.dp1, w.m1,
+    hd.hstat = hstat;
+    if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3_fused_bwd(r, nets, n, d.C, d.H, d.W, w.dp1, w.m1,
                                d_packed + pack_off_b3(d.C, d.bands, 1), L.packed_total, xs, w.part0,
                                (long long)n * conv0_partial_size(d.C), &hd, st))))) return rc;
     // conv1's and conv2's weight gradients: one launch where the pair kernel exists (timed as the conv1 kernel)
     bool merged = false;
     if ((rc = TIMED(CMLPL_K_CONV1_WGRAD, chk(launch_wgrad3_pair(nets, n, d.H, d.W, w.a0, w.dp1, w.m1, w.part1, d.H2, d.W2,
-                                  w.p1, w.dp2, w.m2, w.part2, &merged, st, h2w ? w.hstat : nullptr, hd.h2flag, L.packed_total))))) return rc;
+                                  w.p1, w.dp2, w.m2, w.part2, &merged, st, hstat, hd.h2flag, L.packed_total))))) return rc;
     (void)merged;
   } else {
     // General path (windows the per-sample kernels do not take: P 20x20, B5 15x15): one launch per stage.  Round 4:
@@ -446,29 +441,28 @@ int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
     if ((rc = TIMED(CMLPL_K_HEAD_BWD, chk(launch_head_bwd(nets, n, d.P4, d.K, d_dlogits, d_dfeat_head, mask,
                                   d_params + L.param_off[8], param_stride, w.y, w.ynorm, w.dy, w.dp2, st))))) return rc;
     const uint32_t* h2flag = (const uint32_t*)(d_packed + pack_off_h2flag(d.C, d.bands));
-    const bool gen_stats = general_h2_stats(d, nets * n);
-    const Conv3H2 h3 = {d_packed + pack_off_h2(d.C, d.bands, 3), L.packed_total, h2flag, gen_stats ? w.hstat : nullptr, 3};
-    if ((rc = TIMED(CMLPL_K_CONV2_DGRAD, chk(launch_conv3(1, nets, n, d.H2, d.W2, w.dp2, w.m2, d_packed + pack_off_b3(d.C, d.bands, 3),
-                               L.packed_total, nullptr, 0, w.dp1, nullptr, st, &h3))))) return rc;
+    const Conv3H2 h3 = {d_packed + pack_off_h2(d.C, d.bands, 3), L.packed_total, h2flag, hstat, 3};
+    if ((rc = TIMED(CMLPL_K_CONV2_DGRAD, chk(launch_conv3(r.plan[3], 1, nets, n, d.H2, d.W2, w.dp2, w.m2, d_packed + pack_off_b3(d.C, d.bands, 3),
+                               L.packed_total, nullptr, 0, w.dp1, nullptr, st, h3))))) return rc;
     // (round 6: conv1's data gradient in FRONT of the weight-gradient pair launch -- it leaves the maxima of conv1's
     //  gradient operand that the two-piece weight gradient scales by; neither reads what the other writes)
-    if (conv3_fused_bwd_ok(d.H, d.W, d.C, nets * n)) {
+    if (r.bwd == ROUTE_B) {
       // conv1 data gradient + conv0 weight gradient in one launch: da0 never goes to HBM
-      if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3_fused_bwd(nets, n, d.C, d.H, d.W, w.dp1, w.m1,
+      if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3_fused_bwd(r, nets, n, d.C, d.H, d.W, w.dp1, w.m1,
                                  d_packed + pack_off_b3(d.C, d.bands, 1), L.packed_total, xs, w.part0,
                                  (long long)n * conv0_partial_size(d.C), nullptr, st))))) return rc;
     } else {
       if (!d_xn) return CMLPL_E_ARG;
-      const Conv3H2 h1 = {d_packed + pack_off_h2(d.C, d.bands, 1), L.packed_total, h2flag, gen_stats ? w.hstat : nullptr, 2};
-      if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3(1, nets, n, d.H, d.W, w.dp1, w.m1, d_packed + pack_off_b3(d.C, d.bands, 1),
-                                 L.packed_total, nullptr, 0, w.da0, nullptr, st, &h1))))) return rc;
-      if ((rc = TIMED(CMLPL_K_CONV0_WGRAD, chk(launch_conv0_wgrad(nets, n, d.C, d.HW, d_xn, w.da0, w.part0, st, gen_stats ? w.hstat : nullptr, h2flag,
+      const Conv3H2 h1 = {d_packed + pack_off_h2(d.C, d.bands, 1), L.packed_total, h2flag, hstat, 2};
+      if ((rc = TIMED(CMLPL_K_CONV1_DGRAD, chk(launch_conv3(r.plan[1], 1, nets, n, d.H, d.W, w.dp1, w.m1, d_packed + pack_off_b3(d.C, d.bands, 1),
+                                 L.packed_total, nullptr, 0, w.da0, nullptr, st, h1))))) return rc;
+      if ((rc = TIMED(CMLPL_K_CONV0_WGRAD, chk(launch_conv0_wgrad(nets, n, d.C, d.HW, d_xn, w.da0, w.part0, st, hstat, h2flag,
                                                                          L.packed_total)))))
         return rc;
     }
     bool merged = false;
     if ((rc = TIMED(CMLPL_K_CONV1_WGRAD, chk(launch_wgrad3_pair(nets, n, d.H, d.W, w.a0, w.dp1, w.m1, w.part1, d.H2, d.W2,
-                                  w.p1, w.dp2, w.m2, w.part2, &merged, st, gen_stats ? w.hstat : nullptr, h2flag,
+                                  w.p1, w.dp2, w.m2, w.part2, &merged, st, hstat, h2flag,
                                   L.packed_total))))) return rc;
     (void)merged;
   }
@@ -485,16 +479,12 @@ int bwd_core(const Dims& d, const cmlpl_layout_t& L, int nets, int n, const floa
   if (!plan_wgrad3_both(nets, n, d.H, d.W, d.H2, d.W2, true, &wp1, &wp2, &wpair)) return CMLPL_E_SHAPE;
   reduce_table_add(rt, w.part1, wp1.G, PART3, 1, 64, d_grads + L.param_off[2], d_grads + L.param_off[3]);
   reduce_table_add(rt, w.part2, wp2.G, PART3, 1, 64, d_grads + L.param_off[4], d_grads + L.param_off[5]);
-  reduce_table_add(rt, w.part0, conv0_partials(d, nets, n), conv0_partial_size(d.C), 0, d.C,
+  reduce_table_add(rt, w.part0, conv0_partials(d, r, n), conv0_partial_size(d.C), 0, d.C,
                    d_grads + L.param_off[0], d_grads + L.param_off[1]);
   // the classifier / feat_spe weight-gradient GEMMs ride along (independent, short)
   return TIMED(CMLPL_K_CONV1_WRED, chk(launch_reduce_gemm(nets, rt, gw_cls, gw_spe, st)));
 }
 
-// does the step need an augmented copy of the patches in HBM?  (only when a conv0 pass falls back to the unfused kernels)
-bool need_xn_copy(const Dims& d, int rows) {
-  return !(conv3_fused_ok(d.H, d.W, d.C, rows) && conv3_fused_bwd_ok(d.H, d.W, d.C, rows));
-}
 // 0, or the error of a malformed batch.  Split-fed (d_cube null): the four row buffers.  Cube-fed (ABI 6): the scene, its
 // two pixel lists and NO window buffers; a square window no larger than the scene that fits the gather's LDS tile.
 int check_batch(const Dims& d, const cmlpl_batch* b) {
@@ -525,13 +515,15 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
   if (hp->dropout_p < 0.f || hp->dropout_p >= 1.f) return CMLPL_E_ARG;
   const int n = batch->bt + batch->btu;
   if (shard && (shard->nlab != batch->bt || shard->nunl != batch->btu)) return CMLPL_E_ARG;
+  NetRoute r;
   NetWs nw;
-  if (!carve_net(d, 2, n, (char*)d_workspace, &nw)) return CMLPL_E_SHAPE;
+  if (!make_route(d, 2, n, &r) || !carve_net(d, r, 2, n, (char*)d_workspace, &nw)) return CMLPL_E_SHAPE;
   StepWs sw;
   carve_step(d, n, n, (char*)d_workspace + nw.bytes, &sw);
   if (nw.bytes + ((char*)sw.dlogits - ((char*)d_workspace + nw.bytes)) > workspace_bytes) return CMLPL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const bool copy = need_xn_copy(d, 2 * n);
+  // does the step need an augmented copy of the patches in HBM?  (only when a conv0 pass falls back to the unfused kernels)
+  const bool copy = r.xn_copy();
   const int lab0 = shard ? shard->lab0 : 0, unl_base = shard ? shard->bt_g + shard->unl0 : batch->bt;
   int rc;
   // the augmentation launch remains only for what the fused kernels cannot take raw: the patches when a conv0 pass
@@ -540,7 +532,7 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
   const bool spe_fused = spe_fused_ok(d.bands);
   // (general path: the augmentation of the patches rides in conv0's launch where conv0a_fwd_kernel takes the window; it
   //  leaves the augmented rows in sw.xn like the fused forward does)
-  const bool c0a = copy && !conv3_fused_ok(d.H, d.W, d.C, 2 * n) && conv0a_ok(d.C, d.HW);
+  const bool c0a = r.fwd == ROUTE_C && conv0a_ok(d.C, d.HW);
   // (cube-fed batch: the patches' augmented rows come from the gather launch below, whatever the path)
   const bool cube = batch->d_cube != nullptr;
   const int which = ((parts & 2) && copy && !c0a && !cube ? 1 : 0) | ((parts & 1) && !spe_fused ? 2 : 0);
@@ -565,14 +557,14 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
                                   (const long long*)batch->d_lab_pix, (const long long*)batch->d_unl_pix, batch->bt,
                                   batch->btu, lab0, unl_base, batch->noise8, hp->noise_sigma, seed, step, sw.xn, &sel,
                                   st))))) return rc;
-    return fwd_core(d, L, 2, n, d_params, L.param_total, d_packed,
+    return fwd_core(d, r, L, 2, n, d_params, L.param_total, d_packed,
                     xsrc_plain(sw.xn, 2, n, (long long)d.C * d.HW, seed, step, shard, dyn),
                     spe_fused ? &xspec : nullptr, sw.sn, (const long long*)batch->d_labels, d_labels_f, sw.xn, sw.sn,
                     nullptr, d_dropmask, hp->dropout_p, train, seed, step, shard, d_logits, d_feat, nw, st, nullptr, parts,
                     early_feat);
   }
   // (fused per-sample kernels: the forward leaves the rows it saw in sw.xn for cmlpl_backward, which lands them by DMA)
-  return fwd_core(d, L, 2, n, d_params, L.param_total, d_packed, xsrc_raw(batch, hp->noise_sigma, seed, step, shard, dyn),
+  return fwd_core(d, r, L, 2, n, d_params, L.param_total, d_packed, xsrc_raw(batch, hp->noise_sigma, seed, step, shard, dyn),
                   spe_fused ? &xspec : nullptr, sw.sn, (const long long*)batch->d_labels, d_labels_f,
                   (copy && !c0a) ? sw.xn : nullptr, sw.sn, nullptr, d_dropmask, hp->dropout_p,
                   train, seed, step, shard, d_logits, d_feat, nw, st,
@@ -643,19 +635,20 @@ int backward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl
     return CMLPL_E_ARG;
   if (int brc = check_batch(d, batch)) return brc;
   const int n = batch->bt + batch->btu;
+  NetRoute r;
   NetWs nw;
-  if (!carve_net(d, 2, n, (char*)d_workspace, &nw)) return CMLPL_E_SHAPE;
+  if (!make_route(d, 2, n, &r) || !carve_net(d, r, 2, n, (char*)d_workspace, &nw)) return CMLPL_E_SHAPE;
   StepWs sw;
   carve_step(d, n, n, (char*)d_workspace + nw.bytes, &sw);
   if (nw.bytes + ((char*)sw.dlogits - ((char*)d_workspace + nw.bytes)) > workspace_bytes) return CMLPL_E_WORKSPACE;
-  const bool copy = need_xn_copy(d, 2 * n);
+  const bool copy = r.xn_copy();
   // the patches as the forward saw them: sw.xn holds them in [nets][n][C*HW] layout either way -- written by the fused
   // forward (augmented, or plain copies when no noise is added) or, when a conv0 pass fell back to the unfused kernels
   // (`copy`), by the augmentation launch.  The fused data gradient reads plain rows by batch row: it knows neither noise
   // nor index lists, so it must never be handed the raw batch (a 9x9 window at 128 + 128 rows plans an unfused forward
   // and a fused backward: with the raw rows conv0's weight gradient came from un-augmented rows 0..n-1 of the split).
   const XSrc xs = xsrc_plain(sw.xn, 2, n, (long long)d.C * d.HW, seed, step, shard, dyn);
-  return bwd_core(d, L, 2, n, d_params, L.param_total, d_packed, xs,
+  return bwd_core(d, r, L, 2, n, d_params, L.param_total, d_packed, xs,
                   copy ? sw.xn : nullptr, sw.sn, d_dropmask, hp->dropout_p, train, d_dlogits, d_dfeat, d_grads,
                   grad_stride, nw, (hipStream_t)stream, dyn_cursor, dyn_cursor ? (cmlpl_dyn*)dyn.table : nullptr, parts);
 }
@@ -910,8 +903,9 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
   if (io->reserved != CMLPL_METHOD_CMLPL && io->reserved != CMLPL_METHOD_CPS) return CMLPL_E_ARG;
   const bool cps = io->reserved == CMLPL_METHOD_CPS;
   const int n = io->bt + io->btu;
+  NetRoute r;
   NetWs nw;
-  if (!carve_net(d, 2, n, (char*)io->d_workspace, &nw)) return CMLPL_E_SHAPE;
+  if (!make_route(d, 2, n, &r) || !carve_net(d, r, 2, n, (char*)io->d_workspace, &nw)) return CMLPL_E_SHAPE;
   StepWs sw;
   carve_step(d, n, io->banks.Q, (char*)io->d_workspace + nw.bytes, &sw);
   if (nw.bytes + sw.bytes > io->workspace_bytes) return CMLPL_E_WORKSPACE;
@@ -1076,7 +1070,8 @@ int cmlpl_extract_patches(const float* d_cube, int rows, int cols, int C, int w,
 
 size_t cmlpl_infer_workspace_bytes(const cmlpl_shape* shape, int n) {
   Dims d;
-  if (!make_dims(shape, &d) || n < 1 || !conv3_infer_ok(d.H, d.W, d.C, d.K)) return 0;   // 0: not a shape cmlpl_infer_cube takes
+  Conv3Variant v;
+  if (!make_dims(shape, &d) || n < 1 || !route_infer(d.H, d.W, d.C, d.K, &v)) return 0;   // 0: not a shape cmlpl_infer_cube takes
   return up256((size_t)n * 1024 * 4);                       // y = relu(feat_spe(spectrum)) of the launch's pixels
 }
 
@@ -1089,7 +1084,8 @@ int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const floa
   if (!d_params || !d_packed || !d_cube || !d_spectra || !d_labels || !d_workspace || rows < 1 || cols < 1 || n < 1 ||
       pixel0 < 0 || pixel0 + n > (int64_t)rows * cols)
     return CMLPL_E_ARG;
-  if (!conv3_infer_ok(d.H, d.W, d.C, d.K)) return CMLPL_E_SHAPE;
+  Conv3Variant v;
+  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
   if (cmlpl_infer_workspace_bytes(shape, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   float* y = (float*)d_workspace;
@@ -1102,14 +1098,15 @@ int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const floa
   t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
   t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
   t.y = y; t.logits = d_logits; t.K = d.K;
-  return chk(launch_conv3_infer(n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
+  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
                                 d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
                                 d_params + L.param_off[3], t, (long long*)d_labels, st));
 }
 
 size_t cmlpl_eval_workspace_bytes(const cmlpl_shape* shape, int nets, int n) {
   Dims d;
-  if (!make_dims(shape, &d) || n < 1 || nets < 1 || nets > 2 || !conv3_infer_ok(d.H, d.W, d.C, d.K)) return 0;   // 0: not a shape cmlpl_infer_pixels takes
+  Conv3Variant v;
+  if (!make_dims(shape, &d) || n < 1 || nets < 1 || nets > 2 || !route_infer(d.H, d.W, d.C, d.K, &v)) return 0;   // 0: not a shape cmlpl_infer_pixels takes
   return up256((size_t)nets * n * 1024 * 4);                // y = relu(feat_spe(spectrum)) [nets][n][1024]
 }
 
@@ -1124,7 +1121,8 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
       nets > 2 || rows < 1 || cols < 1 || rows < d.H / 2 || cols < d.W / 2 ||
       (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
     return CMLPL_E_ARG;
-  if (!conv3_infer_ok(d.H, d.W, d.C, d.K)) return CMLPL_E_SHAPE;
+  Conv3Variant v;
+  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
   if ((int64_t)rows * cols * d.C >= (1LL << 31)) return CMLPL_E_ARG;          // (the gather's 32-bit offsets)
   if (cmlpl_eval_workspace_bytes(shape, nets, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -1139,7 +1137,7 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
   t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
   t.y = y; t.logits = d_logits; t.K = d.K;
   const InferNets nn = {nets, (long long)param_stride, (long long)packed_stride, (const long long*)d_pix};
-  return chk(launch_conv3_infer(n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
+  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
                                 d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
                                 d_params + L.param_off[3], t, (long long*)d_labels, st, &nn));
 }
@@ -1284,9 +1282,10 @@ int cmlpl_debug_region(const cmlpl_shape* shape, int nets, int n, const char* na
   Dims d;
   if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
   if (nets < 1 || nets > 2 || n < 1 || !name || !byte_offset || !bytes) return CMLPL_E_ARG;
+  NetRoute r;
   NetWs w;
   char* base = (char*)(uintptr_t)4096;   // fake base: only offsets are used
-  if (!carve_net(d, nets, n, base, &w)) return CMLPL_E_SHAPE;
+  if (!make_route(d, nets, n, &r) || !carve_net(d, r, nets, n, base, &w)) return CMLPL_E_SHAPE;
   const size_t N = (size_t)nets * n;
   struct { const char* nm; const void* p; size_t b; } tab[] = {
       {"a0", w.a0, N * d.HW * 256}, {"p1", w.p1, N * d.P2 * 256}, {"m1", w.m1, N * d.P2 * 64},
@@ -1317,27 +1316,38 @@ int cmlpl_debug_reload_switches(void) {
 int cmlpl_debug_two_piece(const cmlpl_shape* shape, int nets, int n) {
   Dims d;
   if (!make_dims(shape, &d) || nets < 1 || nets > 2 || n < 1) return CMLPL_E_SHAPE;
-  const int rows = nets * n, f = switches().f16x2;
-  int bits = 0;
-  if (conv3_fused_tail_ok(d.H, d.W, d.C, rows, d.K) && conv3_fused_head_ok(d.H, d.W, d.C, rows, d.K)) {   // the per-sample kernels
-    if (conv3_h2x_both(d.H, d.W, d.C, rows, d.K)) return 1 | 2 | 4;
-    return f == 2 ? 1 : f == 3 ? 2 : 0;    // (the switch's forward-only / backward-only modes: weight gradients on three pieces)
-  }
-  if (conv3_fused_ok(d.H, d.W, d.C, rows) || conv3_fused_bwd_ok(d.H, d.W, d.C, rows)) return 0;   // (mixed paths: switch-forced variants)
-  if (conv3_h2x_general(0, d.H, d.W, rows)) bits |= 1;
-  if (conv3_h2x_general(1, d.H, d.W, rows)) bits |= 2;
-  if (general_h2_stats(d, rows)) bits |= 4;
-  if (conv3_h2x_general(0, d.H2, d.W2, rows) && conv3_h2x_general(1, d.H2, d.W2, rows)) bits |= 8;
-  return bits;
+  NetRoute r;
+  make_route(d, nets, n, &r);           // (a map without a plan has no two-piece launch: nothing to refuse here)
+  const int f = switches().f16x2;
+  if (r.fwd == ROUTE_A && r.bwd == ROUTE_A)     // the per-sample kernels
+    return r.stats ? 1 | 2 | 4 : f == 2 ? 1 : f == 3 ? 2 : 0;    // (the switch's forward-only / backward-only modes: weight gradients on three pieces)
+  if (r.fwd != ROUTE_C || r.bwd != ROUTE_C) return 0;   // (mixed paths: switch-forced variants)
+  return (r.plan[0].h2x ? 1 : 0) | (r.plan[1].h2x ? 2 : 0) | (r.stats ? 4 : 0) | (r.plan[2].h2x && r.plan[3].h2x ? 8 : 0);
 }
 
 int cmlpl_debug_conv3_plan(const cmlpl_shape* shape, int nets, int n, int map, int mode, int* out3) {
   Dims d;
   if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
   if (nets < 1 || nets > 2 || n < 1 || map < 0 || map > 1 || mode < 0 || mode > 1 || !out3) return CMLPL_E_ARG;
-  Conv3Plan pl;
-  if (!plan_conv3(mode, map ? d.H2 : d.H, map ? d.W2 : d.W, nets * n, &pl)) return CMLPL_E_SHAPE;
+  NetRoute r;
+  make_route(d, nets, n, &r);
+  const Conv3Variant& pl = r.plan[2 * map + mode];
+  if (pl.S < 1) return CMLPL_E_SHAPE;
   out3[0] = pl.S; out3[1] = pl.MTW; out3[2] = pl.nw;
+  return 0;
+}
+
+int cmlpl_debug_route(const cmlpl_shape* shape, int nets, int n, int* out) {
+  Dims d;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  if (nets < 1 || nets > 2 || n < 1 || !out) return CMLPL_E_ARG;
+  NetRoute r;
+  if (!make_route(d, nets, n, &r)) return CMLPL_E_SHAPE;
+  int* o = out;
+  *o++ = r.fwd; *o++ = r.bwd; *o++ = (r.fwd_ps.big || r.bwd_ps.big) ? 1 : 0;
+  for (const Conv3Variant* v : {&r.fwd_ps, &r.bwd_ps}) { *o++ = v->nw; *o++ = v->tpw; *o++ = v->h2x ? 1 : 0; }
+  for (const Conv3Variant& p : r.plan) { *o++ = p.S; *o++ = p.MTW; *o++ = p.nw; *o++ = p.ks ? 1 : 0; *o++ = p.h2x ? 1 : 0; }
+  *o++ = r.stats ? 1 : 0;
   return 0;
 }
 

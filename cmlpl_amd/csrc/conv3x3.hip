@@ -2803,7 +2803,7 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
         const float* bp = dal + 32 * cn0 + l31;
         const int NS = (HWl + 15) >> 4;
 #pragma unroll
-        for (int kq = 0; kq < 2 * KMT; ++kq) {            // HW <= 32 KMT (conv3_fused_bwd_ok)
+        for (int kq = 0; kq < 2 * KMT; ++kq) {            // HW <= 32 KMT (route_net)
           if (kq < NS && !zskip) {                        // uniform
             float ra[8], rb[TPW][8];
 #pragma unroll
@@ -2965,6 +2965,11 @@ __global__ __launch_bounds__(256) void conv3x3_small_kernel(Conv3Args a) {
   }
 }
 
+
+// ------------------------------------------------------------------------------------------
+// the router: which kernels a forward / backward of the networks runs (kernels.hpp: NetRoute).  Host arithmetic only;
+// the launchers below follow what it wrote and decide nothing themselves.
+// ------------------------------------------------------------------------------------------
 static size_t conv3_lds(int S, int H, int W, int MTW, int NW = 4) {
   return ((size_t)S * (H + 2) * (W + 2) * CS + WBUF + (size_t)MTW * NW * 32) * 4;
 }
@@ -2972,7 +2977,7 @@ static size_t conv3_lds(int S, int H, int W, int MTW, int NW = 4) {
 // Pick samples-per-workgroup S.  Cost model: MFMA tile-times queued on the busiest SIMD (workgroups
 // on a CU share its 4 SIMDs, wave w of every workgroup lands on a different SIMD) plus a fixed
 // per-workgroup staging/drain overhead that is hidden when a second workgroup is co-resident.
-bool plan_conv3(int mode, int H, int W, int rows, Conv3Plan* p) {
+static bool plan_conv3(int mode, int H, int W, int rows, Conv3Variant* p) {
   const int PX = (mode == 0) ? (2 * (H / 2)) * (2 * (W / 2)) : H * W;
   if (PX <= 0) return false;
   const int force_s = switches().conv3_s;
@@ -2994,95 +2999,26 @@ bool plan_conv3(int mode, int H, int W, int rows, Conv3Plan* p) {
     // (CMLPL_CONV3_S: the forced count, or -- on a map whose images or tiles do not fit that many -- the largest that
     //  does: S only grows towards the break above, so the last one taken is it.  A 4 x 4 window holds 14, its 2 x 2 map 16.)
     if (force_s ? (S <= force_s) : (cost < best - 1e-9)) {
-      best = cost; p->S = S; p->MTW = split ? 0 : MTW; p->lds = lds; p->nw = 4; ok = true;
+      best = cost; p->S = S; p->MTW = split ? 0 : MTW; p->lds = lds; p->nw = 4; p->tpw = 2; ok = true;
       // one sample per workgroup, one tile per wave, two workgroups per CU: the barrier-free tap loop (KSG)
-      p->ks = (!split && S == 1 && MTW == 1 && resident >= 2 && switches().conv3_ks != 0) ? 1 : 0;
+      p->ks = !split && S == 1 && MTW == 1 && resident >= 2 && switches().conv3_ks != 0;
       // One workgroup per CU and several tiles per wave (20 x 20 windows: a 131 KB image, 13 pixel tiles): EIGHT waves
       // -- two per SIMD, so that a wave's LDS reads, barriers and stores have something to hide under (round 5;
       // CMLPL_CONV3_NW8=0: four waves as before)
       const size_t lds8 = conv3_lds(S, H, W, (MT + 7) / 8, 8);
       if (!split && resident == 1 && MTW >= 2 && lds8 <= LDS_MAX && switches().conv3_nw8 != 0) {
-        p->nw = 8; p->MTW = (MT + 7) / 8; p->lds = lds8; p->ks = 0;
+        p->nw = 8; p->tpw = 1; p->MTW = (MT + 7) / 8; p->lds = lds8; p->ks = false;
       }
     }
   }
   return ok;
 }
 
-template <int MODE, int MTW, int NW = 4>
-static hipError_t launch_conv3_t(const Conv3Args& a, dim3 grid, size_t lds, hipStream_t st) {
-  static DevOnce attr_once;
-  {
-    hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<MODE, MTW, 0, NW>);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((conv3x3_kernel<MODE, MTW, 0, NW>), grid, dim3(64 * NW), lds, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_conv3(int mode, int nets, int n, int H, int W, const float* in, const uint8_t* mask_in,
-                        const float* wpk, long long wpk_ns, const float* bias, long long bias_ns,
-                        float* out, uint8_t* mask_out, hipStream_t st, const Conv3H2* h2) {
-  Conv3Plan pl;
-  if (!plan_conv3(mode, H, W, nets * n, &pl)) return hipErrorInvalidValue;
-  const int HW = H * W, P2 = (H / 2) * (W / 2);
-  Conv3Args a;
-  a.in = in; a.mask_in = mask_in; a.wpk = wpk; a.bias = bias; a.out = out; a.mask_out = mask_out;
-  a.wpk_ns = wpk_ns; a.bias_ns = bias_ns;
-  if (mode == 0) { a.in_ns = (long long)n * HW * 64; a.out_ns = (long long)n * P2 * 64; a.mask_out_ns = a.out_ns; a.mask_in_ns = 0; }
-  else           { a.in_ns = (long long)n * P2 * 64; a.mask_in_ns = a.in_ns; a.out_ns = (long long)n * HW * 64; a.mask_out_ns = 0; }
-  a.n = n; a.H = H; a.W = W; a.S = pl.S;
-  conv3_set_magics(a);
-  a.w0t = nullptr; a.b0 = nullptr; a.a0out = nullptr; a.w0t_ns = a.b0_ns = 0; a.C = 0; a.xn_out = nullptr;
-  a.xs = XSrc(); a.part0 = nullptr; a.part0_ns = 0; a.bp = 0;
-  a.wpk16 = nullptr; a.wpk16_ns = 0; a.h2flag = nullptr; a.h2flag_ns = 0; a.maxslot = 0; a.h2_noskip = switches().f16x2 == 4 || switches().zero_skip == 0; a.hstat = nullptr; a.hkind = 0; a.pairshift = 0;
-  dim3 grid((n + pl.S - 1) / pl.S, nets);
-  // the two-piece tap loops (one sample per workgroup: the barrier-free loop, or eight waves with staged tap weights)
-  const bool h2x = h2 != nullptr && conv3_h2x_general(mode, H, W, nets * n);
-  if (h2x) {
-    a.wpk16 = h2->wpk16; a.wpk16_ns = h2->wpk16_ns; a.h2flag = h2->h2flag; a.h2flag_ns = h2->wpk16_ns; a.hstat = h2->hstat;
-    a.hkind = h2->kind; a.maxslot = (int)(pl.lds / 4);
-    const size_t lds = pl.lds + 64;
-#define CMLPL_H2_LAUNCH(...)                                                                       \
-    { static DevOnce attr_h;                                                                         \
-      hipError_t eh = ensure_max_lds(attr_h, conv3x3_kernel<__VA_ARGS__>);                           \
-      if (eh != hipSuccess) return eh;                                                               \
-      hipLaunchKernelGGL((conv3x3_kernel<__VA_ARGS__>), grid, dim3(pl.ks ? 256 : 512), lds, st, a);  \
-      return hipGetLastError(); }
-    if (pl.ks) { if (mode == 0) CMLPL_H2_LAUNCH(0, 1, 0, 4, 2, true, true) else CMLPL_H2_LAUNCH(1, 1, 0, 4, 2, true, true) }
-    if (pl.MTW == 1) { if (mode == 0) CMLPL_H2_LAUNCH(0, 1, 0, 8, 1, false, true) else CMLPL_H2_LAUNCH(1, 1, 0, 8, 1, false, true) }
-    if (mode == 0) CMLPL_H2_LAUNCH(0, 2, 0, 8, 1, false, true) else CMLPL_H2_LAUNCH(1, 2, 0, 8, 1, false, true)
-#undef CMLPL_H2_LAUNCH
-  }
-  if (pl.ks) {
-    static DevOnce attr_ks;
-    hipError_t e = ensure_max_lds(attr_ks, conv3x3_kernel<0, 1, 0, 4, 2, true>, conv3x3_kernel<1, 1, 0, 4, 2, true>);
-    if (e != hipSuccess) return e;
-    if (mode == 0) hipLaunchKernelGGL((conv3x3_kernel<0, 1, 0, 4, 2, true>), grid, dim3(256), pl.lds, st, a);
-    else           hipLaunchKernelGGL((conv3x3_kernel<1, 1, 0, 4, 2, true>), grid, dim3(256), pl.lds, st, a);
-    return hipGetLastError();
-  }
-  if (pl.nw == 8) {   // (MTW 1 .. 2: at most 16 pixel tiles in a 160 KB image)
-    if (pl.MTW > 2) return hipErrorInvalidValue;
-    if (mode == 0) return pl.MTW == 1 ? launch_conv3_t<0, 1, 8>(a, grid, pl.lds, st) : launch_conv3_t<0, 2, 8>(a, grid, pl.lds, st);
-    return pl.MTW == 1 ? launch_conv3_t<1, 1, 8>(a, grid, pl.lds, st) : launch_conv3_t<1, 2, 8>(a, grid, pl.lds, st);
-  }
-#define CMLPL_DISPATCH(M)                                                      \
-  switch (pl.MTW) {                                                            \
-    case 0: {                                                                  \
-      static DevOnce attr0;                                                    \
-      hipError_t e0 = ensure_max_lds(attr0, conv3x3_small_kernel<M>);          \
-      if (e0 != hipSuccess) return e0;                                         \
-      hipLaunchKernelGGL((conv3x3_small_kernel<M>), grid, dim3(256), pl.lds, st, a);                        \
-      return hipGetLastError();                                                \
-    }                                                                          \
-    case 1: return launch_conv3_t<M, 1>(a, grid, pl.lds, st);                  \
-    case 2: return launch_conv3_t<M, 2>(a, grid, pl.lds, st);                  \
-    case 3: return launch_conv3_t<M, 3>(a, grid, pl.lds, st);                  \
-    default: return launch_conv3_t<M, 4>(a, grid, pl.lds, st);                 \
-  }
-  if (mode == 0) { CMLPL_DISPATCH(0) } else { CMLPL_DISPATCH(1) }
-#undef CMLPL_DISPATCH
+// the kernels' magic-number divide by W is exact for every pixel index below `px`
+static bool conv3_divide_exact(int W, int px) {
+  for (int m = 0; m < px; ++m)
+    if (((m * ((65536 + W - 1) / W)) >> 16) != m / W) return false;
+  return true;
 }
 
 // conv0 fused into the conv1 forward (MODE 2).  Possible when the plain forward plan is one sample per workgroup
@@ -3118,9 +3054,7 @@ static bool conv3_big_geom(int H, int W, BigGeom* g) {
   if (g->HW <= 128 || g->HW > 256 || g->P2 > 64 || g->P4 < 1 || g->P4 > 12) return false;
   if ((size_t)g->NPX2 * CS > WBUF) return false;                                  // the pooled map / dz2 image in the tap-weight buffer
   if ((size_t)2560 + 3 * (size_t)g->NPX2 * 36 + 3072 > (size_t)g->IMG * CS) return false;   // head row + partials + bf16 planes + conv2's exchange in the dead image
-  for (int m = 0; m < 256; ++m)                                                   // the magic-number divide of the kernel
-    if (((m * ((65536 + W - 1) / W)) >> 16) != m / W) return false;
-  return true;
+  return conv3_divide_exact(W, 256);
 }
 static size_t conv3_big_plain(const BigGeom& g) { return ((size_t)g.IMG * CS + WBUF + 256 + 8192) * 4; }
 static size_t conv3_big_fwd_lds(const BigGeom& g, int C) {
@@ -3145,173 +3079,6 @@ static size_t conv3_big_bwd_lds(const BigGeom& g, int C) {
   const size_t need = (slab > reach ? slab : reach) * 4, plain = conv3_big_plain(g);
   return need > plain ? need : plain;
 }
-static bool conv3_big_fwd_ok(int H, int W, int C, BigGeom* g) {
-  return C >= 1 && conv3_big_geom(H, W, g) && conv3_big_fwd_lds(*g, C) <= LDS_MAX;
-}
-static bool conv3_big_bwd_ok(int H, int W, int C, BigGeom* g) {
-  if (switches().fuse_conv0_bwd == 0 || C < 1 || C > 256 || !conv3_big_geom(H, W, g)) return false;
-  if (conv3_big_bp(*g, C) < 32 && conv3_big_bp(*g, C) < C) return false;
-  // the head's hand-off buffers behind the LUT: dp1s [P2][64] + dp2s [P4][64] + dls [64] + red [8] share the fold exchange
-  if ((size_t)g->P2 * 64 + (size_t)g->P4 * 64 + 64 + 8 > 8192) return false;
-  return conv3_big_bwd_lds(*g, C) <= LDS_MAX;
-}
-
-bool conv3_fused_ok(int H, int W, int C, int rows) {
-  const bool off = switches().fuse_conv0 == 0;
-  if (off || C < 1) return false;
-  BigGeom bg;
-  if (conv3_big_fwd_ok(H, W, C, &bg)) return true;
-  Conv3Plan pl;
-  if (!plan_conv3(0, H, W, rows, &pl)) return false;
-  if (pl.S != 1 || pl.MTW != 1 || H * W > 128) return false;
-  for (int m = 0; m < 128; ++m)                       // the magic-number divide of the kernel
-    if (((m * ((65536 + W - 1) / W)) >> 16) != m / W) return false;
-  return 2 * conv3_fused_lds(H, W, C, pl.lds) <= LDS_MAX;
-}
-
-bool conv3_fused_tail_ok(int H, int W, int C, int rows, int K) {
-  const bool off = switches().fuse_tail == 0;
-  const int H2 = H / 2, W2 = W / 2;
-  BigGeom bg;
-  if (conv3_big_fwd_ok(H, W, C, &bg)) return K >= 1 && K <= 64;
-  return !off && conv3_fused_ok(H, W, C, rows) && H2 / 2 == 2 && W2 / 2 == 2 && (H2 + 2) * (W2 + 2) * CS <= 4096 &&
-         K >= 1 && K <= 64;
-}
-
-hipError_t launch_conv3_fused(int nets, int n, int C, int H, int W, const XSrc& xs, const float* w0t, long long w0t_ns,
-                              const float* b0, long long b0_ns, float* a0out, const float* wpk, long long wpk_ns,
-                              const float* bias, long long bias_ns, float* out, uint8_t* mask_out,
-                              const FwdTail* tail, hipStream_t st, float* xn_out) {
-  Conv3Plan pl;
-  if (!conv3_fused_ok(H, W, C, nets * n) || !plan_conv3(0, H, W, nets * n, &pl)) return hipErrorInvalidValue;
-  const int HW = H * W, P2 = (H / 2) * (W / 2);
-  BigGeom bg;
-  const bool big = conv3_big_fwd_ok(H, W, C, &bg);
-  if (big && tail == nullptr) return hipErrorInvalidValue;          // (the eight-tile kernels exist with their tail only)
-  Conv3Args a;
-  a.in = nullptr; a.mask_in = nullptr; a.wpk = wpk; a.bias = bias; a.out = out; a.mask_out = mask_out;
-  a.wpk_ns = wpk_ns; a.bias_ns = bias_ns;
-  a.in_ns = 0; a.mask_in_ns = 0; a.out_ns = (long long)n * P2 * 64; a.mask_out_ns = a.out_ns;
-  a.n = n; a.H = H; a.W = W; a.S = 1;
-  conv3_set_magics(a);
-  a.w0t = w0t; a.w0t_ns = w0t_ns; a.b0 = b0; a.b0_ns = b0_ns; a.a0out = a0out; a.C = C; a.xn_out = xn_out;
-  a.xs = xs; a.part0 = nullptr; a.part0_ns = 0; a.bp = 0;
-  a.wpk16 = nullptr; a.wpk16_ns = 0; a.h2flag = nullptr; a.h2flag_ns = 0; a.maxslot = 0; a.h2_noskip = switches().f16x2 == 4 || switches().zero_skip == 0; a.hstat = nullptr; a.hkind = 0; a.pairshift = 0;
-  (void)HW;
-  if (tail != nullptr) {
-    if (!conv3_fused_tail_ok(H, W, C, nets * n, tail->K)) return hipErrorInvalidValue;
-    a.w2f = tail->w2f; a.w2f_ns = tail->w2f_ns; a.b2 = tail->b2; a.wc = tail->wc; a.bc = tail->bc; a.p_ns = tail->p_ns;
-    a.yin = tail->y; a.dropmask = tail->dropmask; a.dropgen = tail->dropgen; a.catd = tail->catd; a.ynorm = tail->ynorm;
-    a.logits = tail->logits; a.feat = tail->feat; a.p2out = tail->p2; a.m2out = tail->m2;
-    a.dropout_p = tail->dropout_p; a.train = tail->train; a.K = tail->K;
-    static DevOnce attr_once;
-    hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<2, 1, 1>, conv3x3_kernel<2, 1, 1, 8>, conv3x3_kernel<2, 1, 1, 8, 2>);
-    if (e != hipSuccess) return e;
-    const bool h2x = (switches().f16x2 == 1 || switches().f16x2 == 2 || switches().f16x2 == 4) && tail->w1h != nullptr && tail->h2flag != nullptr;
-    if (h2x) { a.wpk16 = tail->w1h; a.wpk16_ns = tail->w1h_ns; a.h2flag = tail->h2flag; a.h2flag_ns = tail->w1h_ns; a.hstat = tail->hstat; }
-    if (big) {
-      const size_t ldsb = conv3_big_fwd_lds(bg, C);
-      if (h2x && ldsb + 64 <= LDS_MAX) {
-        static DevOnce attr_hb;
-        hipError_t eh = ensure_max_lds(attr_hb, conv3x3_kernel<2, 1, 1, 8, 2, false, true>);
-        if (eh != hipSuccess) return eh;
-        a.maxslot = (int)(ldsb / 4);
-        hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1, 8, 2, false, true>), dim3(n, nets), dim3(512), ldsb + 64, st, a);
-        return hipGetLastError();
-      }
-      a.hstat = nullptr;
-      hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1, 8, 2>), dim3(n, nets), dim3(512), ldsb, st, a);
-      return hipGetLastError();
-    }
-    if (conv3_ks8(nets * n)) {
-      const size_t lds8 = conv3_fused_lds(H, W, C, conv3_ks8_lds(pl.lds), 8);
-      if (lds8 > LDS_MAX) return hipErrorInvalidValue;
-      if (h2x && lds8 + 64 <= LDS_MAX) {
-        static DevOnce attr_h8;
-        hipError_t eh = ensure_max_lds(attr_h8, conv3x3_kernel<2, 1, 1, 8, 1, false, true>);
-        if (eh != hipSuccess) return eh;
-        a.maxslot = (int)(lds8 / 4);
-        hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1, 8, 1, false, true>), dim3(n, nets), dim3(512), lds8 + 64, st, a);
-        return hipGetLastError();
-      }
-      hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1, 8>), dim3(n, nets), dim3(512), lds8, st, a);
-      return hipGetLastError();
-    }
-    const size_t lds = conv3_fused_lds(H, W, C, pl.lds);
-    if (h2x && 2 * (lds + 64) <= LDS_MAX) {
-      // conv1's taps on two fp16 pieces; one more LDS word (the image's largest magnitude) behind everything else
-      static DevOnce attr_h;
-      hipError_t eh = ensure_max_lds(attr_h, conv3x3_kernel<2, 1, 1, 4, 2, false, true>);
-      if (eh != hipSuccess) return eh;
-      a.maxslot = (int)(lds / 4);
-      hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1, 4, 2, false, true>), dim3(n, nets), dim3(256), lds + 64, st, a);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((conv3x3_kernel<2, 1, 1>), dim3(n, nets), dim3(256), lds, st, a);
-    return hipGetLastError();
-  }
-  return launch_conv3_t<2, 1>(a, dim3(n, nets), conv3_fused_lds(H, W, C, pl.lds), st);
-}
-
-// Whole-image inference from the scene cube (cmlpl_infer_cube): the fused eval forward with the cube gather as its slab
-// source -- n consecutive pixels from pix0, one network; y = relu(feat_spe(spectrum)) of the same pixels comes from the
-// spectral launch in front.  Shapes: whatever the per-sample forward with its tail takes (four-wave kernels up to 128
-// window pixels, eight-tile kernels up to 256).
-// (one sample per workgroup whatever the training planner would pick for this window at this batch: its S > 1 choices
-//  are a throughput trade for the multi-sample kernels, not a limit of the per-sample one)
-static bool conv3_infer_small_ok(int H, int W, int C, size_t* lds) {
-  const int H2 = H / 2, W2 = W / 2;
-  if (switches().fuse_conv0 == 0 || switches().fuse_tail == 0 || C < 1 || H * W > 128 || H < 8 || W < 8) return false;
-  if (H2 / 2 != 2 || W2 / 2 != 2 || (H2 + 2) * (W2 + 2) * CS > 4096) return false;
-  for (int m = 0; m < 128; ++m)
-    if (((m * ((65536 + W - 1) / W)) >> 16) != m / W) return false;
-  *lds = conv3_fused_lds(H, W, C, conv3_lds(1, H, W, 1));
-  return 2 * *lds <= LDS_MAX;
-}
-bool conv3_infer_ok(int H, int W, int C, int K) {
-  BigGeom bg;
-  size_t lds;
-  return H == W && K >= 1 && K <= 64 && (conv3_big_fwd_ok(H, W, C, &bg) || conv3_infer_small_ok(H, W, C, &lds));
-}
-
-hipError_t launch_conv3_infer(int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
-                              const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
-                              long long* labels_out, hipStream_t st, const InferNets* nn) {
-  const int nets = nn != nullptr ? nn->nets : 1;
-  if (!conv3_infer_ok(H, W, C, t.K) || n < 1 || !cube || !labels_out || nets < 1 || nets > 2) return hipErrorInvalidValue;
-  if ((long long)crows * ccols * C >= (1LL << 31) || W / 2 > crows || W / 2 > ccols) return hipErrorInvalidValue;   // (32-bit offsets; one mirror fold)
-  BigGeom bg;
-  const bool big = conv3_big_fwd_ok(H, W, C, &bg);
-  size_t lds_small = 0;
-  if (!big && !conv3_infer_small_ok(H, W, C, &lds_small)) return hipErrorInvalidValue;
-  Conv3Args a;
-  memset(&a, 0, sizeof(a));
-  a.wpk = wpk; a.bias = bias;
-  a.n = n; a.H = H; a.W = W; a.S = 1;
-  conv3_set_magics(a);
-  a.w0t = w0t; a.b0 = b0; a.C = C;
-  a.w2f = t.w2f; a.b2 = t.b2; a.wc = t.wc; a.bc = t.bc; a.yin = t.y; a.logits = t.logits; a.K = t.K;
-  a.train = 0; a.dropout_p = 0.f;
-  a.cube = cube; a.crows = crows; a.ccols = ccols; a.pix0 = pix0; a.labels_out = labels_out;
-  if (nn != nullptr) {      // the networks' strides (every one of them 0 above: one network) and the pixel list
-    a.wpk_ns = nn->packed_ns; a.w0t_ns = nn->packed_ns; a.w2f_ns = nn->packed_ns;
-    a.bias_ns = nn->param_ns; a.b0_ns = nn->param_ns; a.p_ns = nn->param_ns;
-    a.pix = nn->pix;
-  }
-  static DevOnce attr_once;
-  hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<2, 1, 2>, conv3x3_kernel<2, 1, 2, 8, 2>, conv3x3_kernel<2, 1, 3>,
-                                conv3x3_kernel<2, 1, 3, 8, 2>);
-  if (e != hipSuccess) return e;
-  const dim3 grid(8 * ((n + 7) / 8), nets);
-  if (a.pix != nullptr) {       // TAIL == 3: the same kernels reading the list
-    if (big) hipLaunchKernelGGL((conv3x3_kernel<2, 1, 3, 8, 2>), grid, dim3(512), conv3_big_fwd_lds(bg, C), st, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<2, 1, 3>), grid, dim3(256), lds_small, st, a);
-    return hipGetLastError();
-  }
-  if (big) hipLaunchKernelGGL((conv3x3_kernel<2, 1, 2, 8, 2>), grid, dim3(512), conv3_big_fwd_lds(bg, C), st, a);
-  else hipLaunchKernelGGL((conv3x3_kernel<2, 1, 2>), grid, dim3(256), lds_small, st, a);
-  return hipGetLastError();
-}
 
 // conv0 weight gradient fused into the conv1 data gradient (MODE 3): same shape conditions as the fused forward, and
 // two workgroups per CU with slab [bp][HW] + da0 [HW+1][64] in LDS, bp = bands per pass (at most four band tiles).
@@ -3331,134 +3098,286 @@ static size_t conv3_fused_bwd_lds(int H, int W, int C, size_t plain) {
   return need > plain ? need : plain;
 }
 
-bool conv3_fused_bwd_ok(int H, int W, int C, int rows) {
-  const bool off = switches().fuse_conv0 == 0;
-  const bool offb = switches().fuse_conv0_bwd == 0;
-  if (off || offb || C < 1 || C > 256) return false;
-  BigGeom bg;
-  if (conv3_big_bwd_ok(H, W, C, &bg)) return true;
-  Conv3Plan pl;
-  if (!plan_conv3(1, H, W, rows, &pl)) return false;
-  if (pl.S != 1 || pl.MTW != 1 || H * W > 128 || conv3_bwd_bp(H, W, C) < 32) return false;
-  // band rows up to 127 are read (garbage rows are dropped later) and must stay inside the allocation
-  const size_t lds = conv3_fused_bwd_lds(H, W, C, pl.lds);
-  if ((size_t)128 * H * W * 4 > lds) return false;
-  return 2 * lds <= LDS_MAX;
+// a per-sample launch: one workgroup of nw waves x tpw pixel tiles per sample-net (eight waves of two: the big kernels)
+static Conv3Variant per_sample(int nw, int tpw, size_t lds, int bp = 0) {
+  Conv3Variant v{};
+  v.S = 1; v.MTW = 1; v.nw = nw; v.tpw = tpw; v.big = nw == 8 && tpw == 2; v.lds = lds; v.bp = bp;
+  return v;
+}
+// The two-piece tap loop needs one more LDS word pair behind everything else (the image's largest magnitude) without
+// costing the launch its workgroups per CU: two for the four-wave kernels, one for the eight-wave ones.
+static void take_h2x_if_it_fits(Conv3Variant& v) {
+  if ((v.nw == 8 ? 1 : 2) * (v.lds + 64) > LDS_MAX) return;
+  v.h2x = true; v.maxslot = (int)(v.lds / 4); v.lds += 64;
 }
 
-bool conv3_fused_head_ok(int H, int W, int C, int rows, int K) {
-  const bool off = switches().fuse_tail == 0;
+bool route_net(int H, int W, int C, int K, int rows, NetRoute* r) {
+  *r = NetRoute{};
+  r->fwd = r->bwd = ROUTE_C;
+  if (K < 1 || K > 64) return false;
+  const Switches& sw = switches();
+  const int HW = H * W, H2 = H / 2, W2 = W / 2;
+  // the general plans: conv1 / conv2 (the window / its pooled map), forward / data gradient.  A map that does not fit
+  // has no plan (S = 0) and the route is refused; what the others hold is still what the planner says of them.
+  bool ok = true;
+  for (int i = 0; i < 4; ++i) ok = plan_conv3(i & 1, i < 2 ? H : H2, i < 2 ? W : W2, rows, &r->plan[i]) && ok;
+  const Conv3Variant &pf = r->plan[0], &pb = r->plan[1];
+  BigGeom g;
+  const bool geom = conv3_big_geom(H, W, &g), ks8 = conv3_ks8(rows);
+  // the tail / head of the four-wave and eight-wave kernels: a final pooled map of 2 x 2, conv2's image in the tap-weight buffer
+  const bool pool22 = sw.fuse_tail != 0 && H2 / 2 == 2 && W2 / 2 == 2 && (H2 + 2) * (W2 + 2) * CS <= 4096;
+
+  // forward.  A: the whole sample in one launch, B: conv0 + conv1 (the big kernels exist with their tail only)
+  if (sw.fuse_conv0 != 0 && C >= 1) {
+    const size_t lds = conv3_fused_lds(H, W, C, pf.lds);
+    if (geom && conv3_big_fwd_lds(g, C) <= LDS_MAX) {
+      r->fwd = ROUTE_A; r->fwd_ps = per_sample(8, 2, conv3_big_fwd_lds(g, C));
+    } else if (pf.S == 1 && pf.MTW == 1 && HW <= 128 && conv3_divide_exact(W, 128) && 2 * lds <= LDS_MAX) {
+      r->fwd = pool22 ? ROUTE_A : ROUTE_B;
+      r->fwd_ps = (pool22 && ks8) ? per_sample(8, 1, conv3_fused_lds(H, W, C, conv3_ks8_lds(pf.lds), 8)) : per_sample(4, 2, lds);
+    }
+  }
+  // backward.  A: the data-gradient chain from the head down in one launch, B: conv1's data gradient + conv0's weight
+  // gradient.  (bp >= 32: docs/EXPERIMENTS.md, "C >= 32")
+  if (sw.fuse_conv0 != 0 && sw.fuse_conv0_bwd != 0 && C >= 1 && C <= 256) {
+    const size_t lds = conv3_fused_bwd_lds(H, W, C, pb.lds);
+    // the big head's hand-off buffers behind the LUT: dp1s [P2][64] + dp2s [P4][64] + dls [64] + red [8] share the fold exchange
+    if (geom && (conv3_big_bp(g, C) >= 32 || conv3_big_bp(g, C) >= C) && (size_t)g.P2 * 64 + (size_t)g.P4 * 64 + 64 + 8 <= 8192 &&
+        conv3_big_bwd_lds(g, C) <= LDS_MAX) {
+      r->bwd = ROUTE_A; r->bwd_ps = per_sample(8, 2, conv3_big_bwd_lds(g, C), conv3_big_bp(g, C));
+    } else if (pb.S == 1 && pb.MTW == 1 && HW <= 128 && conv3_bwd_bp(H, W, C) >= 32 &&
+               (size_t)128 * HW * 4 <= lds &&      // band rows up to 127 are read (garbage rows are dropped later) and must stay inside the allocation
+               2 * lds <= LDS_MAX) {
+      // the head's LDS behind the LUT: dp1s [P2][64] + dp2s [256] + dls [64] + red [4]
+      const size_t need = ((size_t)(H + 2) * (W + 2) * CS + WBUF + 128 + (size_t)H2 * W2 * 64 + 256 + 64 + 4) * 4;
+      const bool head = pool22 && H2 * W2 <= 32 && need <= lds;
+      r->bwd = head ? ROUTE_A : ROUTE_B;
+      r->bwd_ps = (head && ks8) ? per_sample(8, 1, conv3_fused_bwd_lds(H, W, C, conv3_ks8_lds(pb.lds)), conv3_bwd_bp(H, W, C))
+                                : per_sample(4, 2, lds, conv3_bwd_bp(H, W, C));
+    }
+  }
+
+  // conv1's tap loops on two fp16 pieces (CMLPL_F16X2): the whole-sample forward at 1, 2, 4, the fused-head backward at
+  // 1, 3, 4; the general launches at 1, 4 where the plan is one sample per workgroup on the barrier-free loop or on eight
+  // waves with one or two tiles each
+  const int f = sw.f16x2;
+  const bool both = f == 1 || f == 4;
+  if (r->fwd == ROUTE_A && (both || f == 2)) take_h2x_if_it_fits(r->fwd_ps);
+  if (r->bwd == ROUTE_A && (both || f == 3)) take_h2x_if_it_fits(r->bwd_ps);
+  bool general = both;
+  for (Conv3Variant& p : r->plan) {
+    if (both && p.S == 1 && (p.ks || (p.nw == 8 && p.MTW >= 1 && p.MTW <= 2))) take_h2x_if_it_fits(p);
+    general = general && p.h2x;
+  }
+  // ... and the statistics table the two-piece weight gradient scales by: written by EVERY launch that sees one of its
+  // four images, so all of them must be two-piece kernels
+  r->stats = both && ((r->fwd == ROUTE_A && r->bwd == ROUTE_A && r->fwd_ps.h2x && r->bwd_ps.h2x) ||
+                      (r->fwd == ROUTE_C && r->bwd == ROUTE_C && general));
+  return ok;
+}
+
+// Whole-image inference from the scene cube (cmlpl_infer_cube): the fused eval forward with the cube gather as its slab
+// source -- n consecutive pixels from pix0, one network; y = relu(feat_spe(spectrum)) of the same pixels comes from the
+// spectral launch in front.  Shapes: whatever the per-sample forward with its tail takes (four-wave kernels up to 128
+// window pixels, eight-tile kernels up to 256).
+// (one sample per workgroup whatever the training planner would pick for this window at this batch: its S > 1 choices
+//  are a throughput trade for the multi-sample kernels, not a limit of the per-sample one)
+bool route_infer(int H, int W, int C, int K, Conv3Variant* v) {
   const int H2 = H / 2, W2 = W / 2;
-  BigGeom bg;
-  if (conv3_big_bwd_ok(H, W, C, &bg)) return K >= 1 && K <= 64;
-  if (off || !conv3_fused_bwd_ok(H, W, C, rows) || H2 / 2 != 2 || W2 / 2 != 2 || (H2 + 2) * (W2 + 2) * CS > 4096 ||
-      H2 * W2 > 32 || K < 1 || K > 64)
-    return false;
-  // LDS behind the LUT: dp1s [P2][64] + dp2s [256] + dls [64] + red [4]
-  Conv3Plan pl;
-  if (!plan_conv3(1, H, W, rows, &pl)) return false;
-  const size_t need = ((size_t)(H + 2) * (W + 2) * CS + WBUF + 128 + (size_t)H2 * W2 * 64 + 256 + 64 + 4) * 4;
-  return need <= conv3_fused_bwd_lds(H, W, C, pl.lds);
+  *v = Conv3Variant{};
+  if (H != W || K < 1 || K > 64 || C < 1) return false;
+  BigGeom g;
+  if (conv3_big_geom(H, W, &g) && conv3_big_fwd_lds(g, C) <= LDS_MAX) {
+    *v = per_sample(8, 2, conv3_big_fwd_lds(g, C));
+    return true;
+  }
+  if (switches().fuse_conv0 == 0 || switches().fuse_tail == 0 || H * W > 128 || H < 8 || W < 8) return false;
+  if (H2 / 2 != 2 || W2 / 2 != 2 || (H2 + 2) * (W2 + 2) * CS > 4096 || !conv3_divide_exact(W, 128)) return false;
+  const size_t lds = conv3_fused_lds(H, W, C, conv3_lds(1, H, W, 1));
+  if (2 * lds > LDS_MAX) return false;
+  *v = per_sample(4, 2, lds);
+  return true;
 }
 
-hipError_t launch_conv3_fused_bwd(int nets, int n, int C, int H, int W, const float* dpool, const uint8_t* mask,
-                                  const float* wpk, long long wpk_ns, const XSrc& xs, float* part0, long long part0_ns,
-                                  const BwdHead* head, hipStream_t st) {
-  Conv3Plan pl;
-  if (!conv3_fused_bwd_ok(H, W, C, nets * n) || !plan_conv3(1, H, W, nets * n, &pl)) return hipErrorInvalidValue;
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+// what every launch sets: the activations and their per-network strides (the window-sized tensor is the input of MODE 0
+// and the output of MODE 1; every other one is pooled), the geometry and its magics; everything else null / zero
+static Conv3Args conv3_args(int mode, int n, int H, int W, int S, const float* in, const uint8_t* mask_in, float* out,
+                            uint8_t* mask_out) {
+  Conv3Args a{};
+  const long long window = (long long)n * H * W * 64, pooled = (long long)n * (H / 2) * (W / 2) * 64;
+  a.in = in; a.mask_in = mask_in; a.out = out; a.mask_out = mask_out;
+  if (in) a.in_ns = mode == 0 ? window : pooled;
+  if (mask_in) a.mask_in_ns = pooled;
+  if (out) a.out_ns = mode == 1 ? window : pooled;
+  if (mask_out) a.mask_out_ns = pooled;
+  a.n = n; a.H = H; a.W = W; a.S = S;
+  conv3_set_magics(a);
+  a.h2_noskip = switches().f16x2 == 4 || switches().zero_skip == 0;
+  return a;
+}
+static void conv3_args_h2x(Conv3Args& a, const Conv3Variant& v, const float* wpk16, long long wpk16_ns, const uint32_t* h2flag,
+                           uint32_t* hstat) {
+  a.wpk16 = wpk16; a.wpk16_ns = wpk16_ns; a.h2flag = h2flag; a.h2flag_ns = wpk16_ns; a.hstat = hstat; a.maxslot = v.maxslot;
+}
+
+// one instantiation: its dynamic-LDS attribute (once per device) and its launch
+template <int MODE, int MTW, int TAIL, int NW, int TPW, bool KSG, bool H2X>
+static hipError_t launch_conv3_k(const Conv3Args& a, dim3 grid, size_t lds, hipStream_t st) {
+  static DevOnce attr_once;
+  if (lds > LDS_MAX) return hipErrorInvalidValue;
+  hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<MODE, MTW, TAIL, NW, TPW, KSG, H2X>);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((conv3x3_kernel<MODE, MTW, TAIL, NW, TPW, KSG, H2X>), grid, dim3(64 * NW), lds, st, a);
+  return hipGetLastError();
+}
+template <int MODE>
+static hipError_t launch_conv3_small(const Conv3Args& a, dim3 grid, size_t lds, hipStream_t st) {
+  static DevOnce attr_once;
+  hipError_t e = ensure_max_lds(attr_once, conv3x3_small_kernel<MODE>);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((conv3x3_small_kernel<MODE>), grid, dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+// Every 3x3 convolution kernel the library holds, by what selects it: MODE (0 forward, 1 data gradient, 2 / 3 the same with
+// conv0 / conv0's weight gradient fused in), pixel tiles per wave of the planner (0: the one-tile kernel), TAIL (1: with the
+// tail / head; 2 / 3: inference by pixel range / list), waves, tiles a wave's tap loop carries, barrier-free loop, two
+// fp16 pieces.  A kernel is instantiated by its row here and nowhere else; the rows keep the order in which the code
+// object has always held the kernels.
+struct Conv3Kernel {
+  int mode, mtw, tail, nw, tpw; bool ks, h2x;
+  hipError_t (*launch)(const Conv3Args&, dim3, size_t, hipStream_t);
+};
+#define CMLPL_K(...) {__VA_ARGS__, launch_conv3_k<__VA_ARGS__>}
+static const Conv3Kernel conv3_kernels[] = {
+    CMLPL_K(0, 1, 0, 4, 2, true, true),
+    CMLPL_K(1, 1, 0, 4, 2, true, true),
+    CMLPL_K(0, 1, 0, 8, 1, false, true),
+    CMLPL_K(1, 1, 0, 8, 1, false, true),
+    CMLPL_K(0, 2, 0, 8, 1, false, true),
+    CMLPL_K(1, 2, 0, 8, 1, false, true),
+    CMLPL_K(0, 1, 0, 4, 2, true, false),
+    CMLPL_K(1, 1, 0, 4, 2, true, false),
+    CMLPL_K(0, 1, 0, 8, 1, false, false),
+    CMLPL_K(0, 2, 0, 8, 1, false, false),
+    CMLPL_K(1, 1, 0, 8, 1, false, false),
+    CMLPL_K(1, 2, 0, 8, 1, false, false),
+    {0, 0, 0, 4, 2, false, false, launch_conv3_small<0>},
+    CMLPL_K(0, 1, 0, 4, 2, false, false),
+    CMLPL_K(0, 2, 0, 4, 2, false, false),
+    CMLPL_K(0, 3, 0, 4, 2, false, false),
+    CMLPL_K(0, 4, 0, 4, 2, false, false),
+    {1, 0, 0, 4, 2, false, false, launch_conv3_small<1>},
+    CMLPL_K(1, 1, 0, 4, 2, false, false),
+    CMLPL_K(1, 2, 0, 4, 2, false, false),
+    CMLPL_K(1, 3, 0, 4, 2, false, false),
+    CMLPL_K(1, 4, 0, 4, 2, false, false),
+    CMLPL_K(2, 1, 1, 4, 2, false, false),
+    CMLPL_K(2, 1, 1, 8, 1, false, false),
+    CMLPL_K(2, 1, 1, 8, 2, false, false),
+    CMLPL_K(2, 1, 1, 8, 2, false, true),
+    CMLPL_K(2, 1, 1, 8, 1, false, true),
+    CMLPL_K(2, 1, 1, 4, 2, false, true),
+    CMLPL_K(2, 1, 0, 4, 2, false, false),
+    CMLPL_K(2, 1, 2, 4, 2, false, false),
+    CMLPL_K(2, 1, 2, 8, 2, false, false),
+    CMLPL_K(2, 1, 3, 4, 2, false, false),
+    CMLPL_K(2, 1, 3, 8, 2, false, false),
+    CMLPL_K(3, 1, 1, 4, 2, false, false),
+    CMLPL_K(3, 1, 1, 8, 1, false, false),
+    CMLPL_K(3, 1, 1, 8, 2, false, false),
+    CMLPL_K(3, 1, 1, 8, 2, false, true),
+    CMLPL_K(3, 1, 1, 8, 1, false, true),
+    CMLPL_K(3, 1, 1, 4, 2, false, true),
+    CMLPL_K(3, 1, 0, 4, 2, false, false),
+};
+#undef CMLPL_K
+
+static hipError_t launch_conv3_variant(int mode, int tail, const Conv3Variant& v, const Conv3Args& a, dim3 grid, hipStream_t st) {
+  for (const Conv3Kernel& k : conv3_kernels)
+    if (k.mode == mode && k.tail == tail && k.mtw == v.MTW && k.nw == v.nw && k.tpw == v.tpw && k.ks == v.ks && k.h2x == v.h2x)
+      return k.launch(a, grid, v.lds, st);
+  return hipErrorInvalidValue;      // no such kernel: not a variant the router writes
+}
+
+hipError_t launch_conv3(const Conv3Variant& v, int mode, int nets, int n, int H, int W, const float* in, const uint8_t* mask_in,
+                        const float* wpk, long long wpk_ns, const float* bias, long long bias_ns,
+                        float* out, uint8_t* mask_out, hipStream_t st, const Conv3H2& h2) {
+  if (v.S < 1) return hipErrorInvalidValue;
+  Conv3Args a = conv3_args(mode, n, H, W, v.S, in, mask_in, out, mask_out);
+  a.wpk = wpk; a.wpk_ns = wpk_ns; a.bias = bias; a.bias_ns = bias_ns;
+  // the two-piece tap loops (one sample per workgroup: the barrier-free loop, or eight waves with staged tap weights)
+  if (v.h2x) { conv3_args_h2x(a, v, h2.wpk16, h2.wpk16_ns, h2.h2flag, h2.hstat); a.hkind = h2.kind; }
+  const dim3 grid((n + v.S - 1) / v.S, nets);
+  return launch_conv3_variant(mode, 0, v, a, grid, st);
+}
+
+hipError_t launch_conv3_fused(const NetRoute& r, int nets, int n, int C, int H, int W, const XSrc& xs, const float* w0t,
+                              long long w0t_ns, const float* b0, long long b0_ns, float* a0out, const float* wpk,
+                              long long wpk_ns, const float* bias, long long bias_ns, float* out, uint8_t* mask_out,
+                              const FwdTail* tail, hipStream_t st, float* xn_out) {
+  const Conv3Variant& v = r.fwd_ps;
+  if (r.fwd != (tail != nullptr ? ROUTE_A : ROUTE_B)) return hipErrorInvalidValue;
+  Conv3Args a = conv3_args(2, n, H, W, 1, nullptr, nullptr, out, mask_out);
+  a.wpk = wpk; a.wpk_ns = wpk_ns; a.bias = bias; a.bias_ns = bias_ns;
+  a.w0t = w0t; a.w0t_ns = w0t_ns; a.b0 = b0; a.b0_ns = b0_ns; a.a0out = a0out; a.C = C; a.xn_out = xn_out;
+  a.xs = xs;
+  if (tail == nullptr) return launch_conv3_variant(2, 0, v, a, dim3(n, nets), st);
+  a.w2f = tail->w2f; a.w2f_ns = tail->w2f_ns; a.b2 = tail->b2; a.wc = tail->wc; a.bc = tail->bc; a.p_ns = tail->p_ns;
+  a.yin = tail->y; a.dropmask = tail->dropmask; a.dropgen = tail->dropgen; a.catd = tail->catd; a.ynorm = tail->ynorm;
+  a.logits = tail->logits; a.feat = tail->feat; a.p2out = tail->p2; a.m2out = tail->m2;
+  a.dropout_p = tail->dropout_p; a.train = tail->train; a.K = tail->K;
+  if (v.h2x) {      // conv1's taps on two fp16 pieces
+    if (tail->w1h == nullptr || tail->h2flag == nullptr) return hipErrorInvalidValue;
+    conv3_args_h2x(a, v, tail->w1h, tail->w1h_ns, tail->h2flag, tail->hstat);
+  }
+  return launch_conv3_variant(2, 1, v, a, dim3(n, nets), st);
+}
+
+// nn == null: one network, the range from pix0; else the networks' strides and the pixel list
+hipError_t launch_conv3_infer(const Conv3Variant& v, int n, int C, int H, int W, const float* cube, int crows, int ccols,
+                              long long pix0, const float* w0t, const float* b0, const float* wpk, const float* bias,
+                              const FwdTail& t, long long* labels_out, hipStream_t st, const InferNets* nn) {
+  const int nets = nn != nullptr ? nn->nets : 1;
+  if (v.S != 1 || n < 1 || !cube || !labels_out || nets < 1 || nets > 2) return hipErrorInvalidValue;
+  if ((long long)crows * ccols * C >= (1LL << 31) || W / 2 > crows || W / 2 > ccols) return hipErrorInvalidValue;   // (32-bit offsets; one mirror fold)
+  Conv3Args a = conv3_args(2, n, H, W, 1, nullptr, nullptr, nullptr, nullptr);
+  a.wpk = wpk; a.bias = bias;
+  a.w0t = w0t; a.b0 = b0; a.C = C;
+  a.w2f = t.w2f; a.b2 = t.b2; a.wc = t.wc; a.bc = t.bc; a.yin = t.y; a.logits = t.logits; a.K = t.K;
+  a.cube = cube; a.crows = crows; a.ccols = ccols; a.pix0 = pix0; a.labels_out = labels_out;
+  if (nn != nullptr) {      // the networks' strides (every one of them 0 above: one network) and the pixel list
+    a.wpk_ns = nn->packed_ns; a.w0t_ns = nn->packed_ns; a.w2f_ns = nn->packed_ns;
+    a.bias_ns = nn->param_ns; a.b0_ns = nn->param_ns; a.p_ns = nn->param_ns;
+    a.pix = nn->pix;
+  }
+  const dim3 grid(8 * ((n + 7) / 8), nets);
+  return launch_conv3_variant(2, a.pix != nullptr ? 3 : 2, v, a, grid, st);
+}
+
+hipError_t launch_conv3_fused_bwd(const NetRoute& r, int nets, int n, int C, int H, int W, const float* dpool,
+                                  const uint8_t* mask, const float* wpk, long long wpk_ns, const XSrc& xs, float* part0,
+                                  long long part0_ns, const BwdHead* head, hipStream_t st) {
+  const Conv3Variant& v = r.bwd_ps;
+  if (r.bwd != (head != nullptr ? ROUTE_A : ROUTE_B)) return hipErrorInvalidValue;
   // slab_range() reads plain rows by batch row: no noise, no index lists (the rows the forward saw, api.hip)
   if (xs.sigma != 0.f || xs.sel.lab_idx != nullptr || xs.sel.unl_idx != nullptr) return hipErrorInvalidValue;
-  const int P2 = (H / 2) * (W / 2);
-  BigGeom bg;
-  const bool big = conv3_big_bwd_ok(H, W, C, &bg);
-  if (big && head == nullptr) return hipErrorInvalidValue;          // (the eight-tile kernels exist with their head only)
-  Conv3Args a;
-  a.in = dpool; a.mask_in = mask; a.wpk = wpk; a.bias = nullptr; a.out = nullptr; a.mask_out = nullptr;
-  a.wpk_ns = wpk_ns; a.bias_ns = 0;
-  a.in_ns = (long long)n * P2 * 64; a.mask_in_ns = a.in_ns; a.out_ns = 0; a.mask_out_ns = 0;
-  a.n = n; a.H = H; a.W = W; a.S = 1;
-  conv3_set_magics(a);
-  a.w0t = nullptr; a.b0 = nullptr; a.a0out = nullptr; a.w0t_ns = a.b0_ns = 0; a.C = C; a.xn_out = nullptr;
-  a.xs = xs; a.part0 = part0; a.part0_ns = part0_ns; a.bp = big ? conv3_big_bp(bg, C) : conv3_bwd_bp(H, W, C);
-  a.wpk16 = nullptr; a.wpk16_ns = 0; a.h2flag = nullptr; a.h2flag_ns = 0; a.maxslot = 0; a.h2_noskip = switches().f16x2 == 4 || switches().zero_skip == 0; a.hstat = nullptr; a.hkind = 0; a.pairshift = 0;
-  if (head != nullptr) {
-    if (!conv3_fused_head_ok(H, W, C, nets * n, head->K)) return hipErrorInvalidValue;
-    a.dlogits = head->dlogits; a.dfeat = head->dfeat; a.hmask = head->mask; a.wc = head->wc; a.p_ns = head->p_ns;
-    a.yin = head->y; a.ynrm = head->ynorm; a.m2in = head->m2; a.w2d = head->w2d; a.w2d_ns = head->w2d_ns;
-    a.dy = head->dy; a.dp2out = head->dp2; a.dp1out = head->dp1; a.K = head->K;
-    static DevOnce attr_once;
-    hipError_t e = ensure_max_lds(attr_once, conv3x3_kernel<3, 1, 1>, conv3x3_kernel<3, 1, 1, 8>, conv3x3_kernel<3, 1, 1, 8, 2>);
-    if (e != hipSuccess) return e;
-    const bool h2x = (switches().f16x2 == 1 || switches().f16x2 == 3 || switches().f16x2 == 4) && head->w1h != nullptr && head->h2flag != nullptr;
-    if (h2x) { a.wpk16 = head->w1h; a.wpk16_ns = head->w1h_ns; a.h2flag = head->h2flag; a.h2flag_ns = head->w1h_ns; a.hstat = head->hstat; }
-    a.pairshift = (nets == 2 && switches().bwd_pair != 0) ? 1 : 0;
-    if (big) {
-      const size_t ldsb = conv3_big_bwd_lds(bg, C);
-      if (h2x && ldsb + 64 <= LDS_MAX) {
-        static DevOnce attr_hb;
-        hipError_t eh = ensure_max_lds(attr_hb, conv3x3_kernel<3, 1, 1, 8, 2, false, true>);
-        if (eh != hipSuccess) return eh;
-        a.maxslot = (int)(ldsb / 4);
-        hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1, 8, 2, false, true>), dim3(n, nets), dim3(512), ldsb + 64, st, a);
-        return hipGetLastError();
-      }
-      a.hstat = nullptr;
-      hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1, 8, 2>), dim3(n, nets), dim3(512), ldsb, st, a);
-      return hipGetLastError();
-    }
-    if (conv3_ks8(nets * n)) {
-      const size_t lds8 = conv3_fused_bwd_lds(H, W, C, conv3_ks8_lds(pl.lds));
-      if (lds8 > LDS_MAX) return hipErrorInvalidValue;
-      if (h2x && lds8 + 64 <= LDS_MAX) {
-        static DevOnce attr_h8;
-        hipError_t eh = ensure_max_lds(attr_h8, conv3x3_kernel<3, 1, 1, 8, 1, false, true>);
-        if (eh != hipSuccess) return eh;
-        a.maxslot = (int)(lds8 / 4);
-        hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1, 8, 1, false, true>), dim3(n, nets), dim3(512), lds8 + 64, st, a);
-        return hipGetLastError();
-      }
-      hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1, 8>), dim3(n, nets), dim3(512), lds8, st, a);
-      return hipGetLastError();
-    }
-    const size_t lds = conv3_fused_bwd_lds(H, W, C, pl.lds);
-    if (h2x && 2 * (lds + 64) <= LDS_MAX) {
-      static DevOnce attr_h;
-      hipError_t eh = ensure_max_lds(attr_h, conv3x3_kernel<3, 1, 1, 4, 2, false, true>);
-      if (eh != hipSuccess) return eh;
-      a.maxslot = (int)(lds / 4);
-      hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1, 4, 2, false, true>), dim3(n, nets), dim3(256), lds + 64, st, a);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((conv3x3_kernel<3, 1, 1>), dim3(n, nets), dim3(256), lds, st, a);
-    return hipGetLastError();
+  Conv3Args a = conv3_args(3, n, H, W, 1, dpool, mask, nullptr, nullptr);
+  a.wpk = wpk; a.wpk_ns = wpk_ns;
+  a.C = C; a.xs = xs; a.part0 = part0; a.part0_ns = part0_ns; a.bp = v.bp;
+  if (head == nullptr) return launch_conv3_variant(3, 0, v, a, dim3(n, nets), st);
+  a.dlogits = head->dlogits; a.dfeat = head->dfeat; a.hmask = head->mask; a.wc = head->wc; a.p_ns = head->p_ns;
+  a.yin = head->y; a.ynrm = head->ynorm; a.m2in = head->m2; a.w2d = head->w2d; a.w2d_ns = head->w2d_ns;
+  a.dy = head->dy; a.dp2out = head->dp2; a.dp1out = head->dp1; a.K = head->K;
+  a.pairshift = (nets == 2 && switches().bwd_pair != 0) ? 1 : 0;
+  if (v.h2x) {
+    if (head->w1h == nullptr || head->h2flag == nullptr) return hipErrorInvalidValue;
+    conv3_args_h2x(a, v, head->w1h, head->w1h_ns, head->h2flag, head->hstat);
   }
-  return launch_conv3_t<3, 1>(a, dim3(n, nets), conv3_fused_bwd_lds(H, W, C, pl.lds), st);
-}
-
-// do the fused forward AND backward launches of this shape / batch take the two-piece kernels (which also collect the
-// batch statistics the two-piece weight gradient needs)?  Mirrors the launchers below.
-bool conv3_h2x_both(int H, int W, int C, int rows, int K) {
-  if (switches().f16x2 != 1 && switches().f16x2 != 4) return false;
-  BigGeom bg;
-  if (!conv3_fused_tail_ok(H, W, C, rows, K) || !conv3_fused_head_ok(H, W, C, rows, K)) return false;
-  if (conv3_big_fwd_ok(H, W, C, &bg) || conv3_big_bwd_ok(H, W, C, &bg))           // the eight-tile kernels (windows of 129 .. 256 pixels)
-    return conv3_big_fwd_ok(H, W, C, &bg) && conv3_big_bwd_ok(H, W, C, &bg) && conv3_big_fwd_lds(bg, C) + 64 <= LDS_MAX &&
-           conv3_big_bwd_lds(bg, C) + 64 <= LDS_MAX;
-  Conv3Plan pf, pb;
-  if (!plan_conv3(0, H, W, rows, &pf) || !plan_conv3(1, H, W, rows, &pb)) return false;
-  if (conv3_ks8(rows))
-    return conv3_fused_lds(H, W, C, conv3_ks8_lds(pf.lds), 8) + 64 <= LDS_MAX && conv3_fused_bwd_lds(H, W, C, conv3_ks8_lds(pb.lds)) + 64 <= LDS_MAX;
-  return 2 * (conv3_fused_lds(H, W, C, pf.lds) + 64) <= LDS_MAX && 2 * (conv3_fused_bwd_lds(H, W, C, pb.lds) + 64) <= LDS_MAX;
-}
-
-// would launch_conv3 run this map on a two-piece kernel?  (one sample per workgroup: the barrier-free loop of at most four
-// tiles, or the eight-wave kernels with one or two tiles per wave; LDS for one more word)
-bool conv3_h2x_general(int mode, int H, int W, int rows) {
-  if (switches().f16x2 != 1 && switches().f16x2 != 4) return false;
-  Conv3Plan pl;
-  if (!plan_conv3(mode, H, W, rows, &pl) || pl.S != 1) return false;
-  if (pl.ks) return 2 * (pl.lds + 64) <= LDS_MAX;
-  return pl.nw == 8 && pl.MTW >= 1 && pl.MTW <= 2 && pl.lds + 64 <= LDS_MAX;
+  return launch_conv3_variant(3, 1, v, a, dim3(n, nets), st);
 }
 
 }  // namespace cmlpl

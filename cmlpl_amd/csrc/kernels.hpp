@@ -99,18 +99,37 @@ hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w,
 // ---- conv3x3.hip
 hipError_t launch_pack_weights(int nets, const float* params, long long pstride, const PackInfo& pi, float* packed,
                                hipStream_t st);
-struct Conv3Plan { int S, MTW; size_t lds; int nw; int ks; };   // nw: waves of the workgroup (4, or 8: one workgroup per CU, several tiles per wave); ks: the barrier-free tap loop (S = 1, one tile per wave)
-bool plan_conv3(int mode, int H, int W, int rows, Conv3Plan* p);
+// One launch of a 3x3 kernel as the router decided it: conv3x3_kernel<MODE, MTW, TAIL, nw, tpw, ks, h2x> (MTW 0: the
+// one-tile kernel whose four waves split the channel halves) on S samples per workgroup -- S = 0: no such launch.
+//   nw: waves of the workgroup (4, or 8: one workgroup per CU); tpw: pixel tiles a wave's tap loop carries at a time;
+//   ks: the barrier-free tap loop (S = 1, one tile per wave); big: the eight-tile per-sample kernels (129 .. 256 pixels);
+//   h2x: conv1's / this map's tap loop on two fp16 pieces, the image's largest magnitude in LDS word `maxslot`;
+//   lds: dynamic LDS of the launch in bytes, everything included; bp: bands per pass of the fused conv0 weight gradient
+struct Conv3Variant { int S, MTW, nw, tpw; bool ks, big, h2x; size_t lds; int maxslot, bp; };
+// Which kernels a forward and a backward of `rows` = networks x samples windows run (conv3x3.hip: route_net; the letters
+// are those of tests/envelope_cases.py).  Decided once per call of an entry point; api.hip and the launchers read it.
+enum { ROUTE_A = 0, ROUTE_B = 1, ROUTE_C = 2 };
+struct NetRoute {
+  int fwd;                 // A: the whole sample in one launch (fwd_ps with its tail), B: conv0 + conv1 (fwd_ps) then the general conv2 and head, C: general
+  int bwd;                 // A: the data-gradient chain in one launch (bwd_ps with its head), B: general head and conv2, then conv1's data gradient + conv0's weight gradient (bwd_ps), C: general
+  Conv3Variant fwd_ps, bwd_ps;
+  Conv3Variant plan[4];    // the general launches: conv1 forward, conv1 data gradient, conv2 forward, conv2 data gradient (planned whether or not a per-sample kernel takes the launch instead)
+  bool stats;              // the per-sample maxima table ([4][2][n], plain stores) is written by this step's launches and read by its two-piece weight gradient: only when EVERY launch that sees one of the four images is a two-piece kernel
+  bool xn_copy() const { return fwd == ROUTE_C || bwd == ROUTE_C; }   // a conv0 pass on the unfused kernels: it reads an augmented copy of the patches from HBM
+  bool conv0_partials_per_sample() const { return bwd != ROUTE_C; }   // conv0's weight-gradient partials come from the fused data gradient, one per sample
+};
+// false: a map has no plan (it does not fit LDS) or K is out of range -- no entry point takes the shape
+bool route_net(int H, int W, int C, int K, int rows, NetRoute* r);
+// whole-image inference (one sample per workgroup whatever the batch): the per-sample forward with its tail; false: not a shape it takes
+bool route_infer(int H, int W, int C, int K, Conv3Variant* v);
 // mode 0: out = avgpool2(relu(conv(in)+bias+in)), mask_out = relu bits; in [nets][n][H*W][64]
 // mode 1: in = dpool [nets][n][(H/2)*(W/2)][64] + mask_in; out = dgrad(dz) + dz, [nets][n][H*W][64]
 // what a general 3x3 launch needs for the two-piece tap loop: this map's two-piece weight set (pack_off_h2), the
 // networks' range flags, the per-sample statistics table ([4][2][n], or null) and which of its rows this launch's image is
 struct Conv3H2 { const float* wpk16; long long wpk16_ns; const uint32_t* h2flag; uint32_t* hstat; int kind; };
-bool conv3_h2x_general(int mode, int H, int W, int rows);
-hipError_t launch_conv3(int mode, int nets, int n, int H, int W, const float* in, const uint8_t* mask_in,
+hipError_t launch_conv3(const Conv3Variant& plan, int mode, int nets, int n, int H, int W, const float* in, const uint8_t* mask_in,
                         const float* wpk, long long wpk_nstride, const float* bias, long long bias_nstride,
-                        float* out, uint8_t* mask_out, hipStream_t st, const Conv3H2* h2 = nullptr /* two-piece tap loop where the plan allows, or null */);
-bool conv3_fused_ok(int H, int W, int C, int rows);
+                        float* out, uint8_t* mask_out, hipStream_t st, const Conv3H2& h2 /* read where the plan says h2x */);
 // the rest of the forward (conv2 + pool + head) in the same per-sample workgroup: see conv3_fwd_tail
 struct FwdTail {
   const float* w2f; long long w2f_ns; const float* b2; const float* wc; const float* bc; long long p_ns;
@@ -119,20 +138,17 @@ struct FwdTail {
   const float* w1h = nullptr; long long w1h_ns = 0; const uint32_t* h2flag = nullptr;   // conv1's two-piece fp16 set (pack_off_h2(.., 0)) + its flag words, or null
   uint32_t* hstat = nullptr;        // [4 kinds][2 networks][n] per-sample maxima for the two-piece weight gradient, or null
 };
-bool conv3_fused_tail_ok(int H, int W, int C, int rows, int K);
-hipError_t launch_conv3_fused(int nets, int n, int C, int H, int W, const XSrc& xs, const float* w0t, long long w0t_ns,
+hipError_t launch_conv3_fused(const NetRoute& r, int nets, int n, int C, int H, int W, const XSrc& xs, const float* w0t, long long w0t_ns,
                               const float* b0, long long b0_ns, float* a0out, const float* wpk, long long wpk_ns,
                               const float* bias, long long bias_ns, float* out, uint8_t* mask_out,
                               const FwdTail* tail /* or null */, hipStream_t st, float* xn_out = nullptr);
-bool conv3_infer_ok(int H, int W, int C, int K);
 // nn == null: one network, pixels pix0 .. pix0 + n - 1 (cmlpl_infer_cube).  Else (cmlpl_infer_pixels) `nets` networks in
 // grid.y -- their parameters / packed weights param_ns / packed_ns floats apart, t.y / t.logits / labels_out [nets][n] rows --
 // and, when pix is set, sample s = scene pixel pix[s].
 struct InferNets { int nets; long long param_ns, packed_ns; const long long* pix; };
-hipError_t launch_conv3_infer(int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
+hipError_t launch_conv3_infer(const Conv3Variant& v /* route_infer */, int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
                               const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
                               long long* labels_out, hipStream_t st, const InferNets* nn = nullptr);
-bool conv3_fused_bwd_ok(int H, int W, int C, int rows);
 // the head / conv2 part of the backward in the same per-sample workgroup: see conv3_bwd_head
 struct BwdHead {
   const float* dlogits; const float* dfeat; const float* mask; const float* wc; long long p_ns;
@@ -141,9 +157,7 @@ struct BwdHead {
   const float* w1h = nullptr; long long w1h_ns = 0; const uint32_t* h2flag = nullptr;   // conv1's data-gradient two-piece fp16 set (pack_off_h2(.., 1)), or null
   uint32_t* hstat = nullptr;
 };
-bool conv3_fused_head_ok(int H, int W, int C, int rows, int K);
-bool conv3_h2x_both(int H, int W, int C, int rows, int K);
-hipError_t launch_conv3_fused_bwd(int nets, int n, int C, int H, int W, const float* dpool, const uint8_t* mask,
+hipError_t launch_conv3_fused_bwd(const NetRoute& r, int nets, int n, int C, int H, int W, const float* dpool, const uint8_t* mask,
                                   const float* wpk, long long wpk_ns, const XSrc& xs, float* part0, long long part0_ns,
                                   const BwdHead* head /* or null */, hipStream_t st);
 struct Wgrad3Plan { int RU, U, G, cspl, rsplit, UPG, b3; size_t lds; };   // rsplit > 0: row-split kernel with CPR = rsplit, UPG units per workgroup

@@ -13,7 +13,7 @@
 
 namespace {
 
-constexpr int KMAX = 64;          // classes (the classifier's limit: conv3_infer_ok, conv3_fused_tail_ok)
+constexpr int KMAX = 64;          // classes (the classifier's limit: route_infer, route_net)
 constexpr int ROWS_PER_WG = 4096; // list rows a workgroup counts: 16 per thread (a workgroup's int32 cell cannot overflow)
 constexpr int WG_MAX = 1024;      // workgroups per network; past WG_MAX * ROWS_PER_WG rows they stride over the list
 

@@ -685,6 +685,22 @@ int cmlpl_debug_two_piece(const cmlpl_shape* shape, int nets, int n);
  * launch instead.  Host arithmetic only.  CMLPL_E_ARG / CMLPL_E_SHAPE (no plan: the map does not fit). */
 int cmlpl_debug_conv3_plan(const cmlpl_shape* shape, int nets, int n, int map, int mode, int* out3);
 
+/* Added after ABI 6, no bump (nothing existing moves).  Test aid: the route of a forward and a backward on `nets`
+ * networks x n rows under the current switches -- which kernels run, decided once per call and read by everything
+ * that launches.  out[CMLPL_ROUTE_INTS]:
+ *   [0] forward regime   0 = A the whole sample in one launch, 1 = B conv0 + conv1 fused, 2 = C one launch per stage
+ *   [1] backward regime  0 = A the data-gradient chain in one launch, 1 = B conv1 data gradient + conv0 weight gradient
+ *                        fused, 2 = C one launch per stage
+ *   [2] 1 when a per-sample launch is an eight-tile kernel (windows of 129 .. 256 pixels)
+ *   [3..5], [6..8] the per-sample forward / backward launch of regime A or B: waves, pixel tiles per wave, 1 = conv1's
+ *                        tap loop on two fp16 pieces (zeros in regime C)
+ *   [9 + 5 i ..] i = 0 .. 3: the general plan of conv1 forward, conv1 data gradient, conv2 forward, conv2 data gradient
+ *                        as cmlpl_debug_conv3_plan's three, then 1 = the barrier-free tap loop, 1 = two fp16 pieces
+ *   [29] 1 when the step's launches write the per-sample maxima its two-piece weight gradient scales by
+ * Host arithmetic only.  CMLPL_E_ARG / CMLPL_E_SHAPE (a map does not fit). */
+#define CMLPL_ROUTE_INTS 30
+int cmlpl_debug_route(const cmlpl_shape* shape, int nets, int n, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ def __getattr__(name):
     if name == "TrainEngine":
         from .engine import TrainEngine
         return TrainEngine
-    if name in ("BaseNet2", "Normalize"):
+    if name in ("BaseNet2", "Normalize", "WeightEMA_BN"):
         from . import models
         return getattr(models, name)
     raise AttributeError(name)

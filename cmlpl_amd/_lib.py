@@ -39,6 +39,7 @@ EXPORTS = (
     "cmlpl_packed_flag_offset",
     "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
     "cmlpl_debug_conv3_plan", "cmlpl_debug_route",                               # added after ABI 6, no bump: test aids
+    "cmlpl_ema_update",                                                          # added after ABI 6, no bump: the EMA teacher
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
@@ -243,6 +244,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_cps_loss_workspace_bytes.argtypes = [SP, i32, i32]
     lib.cmlpl_cps_loss_workspace_bytes.restype = sz
     lib.cmlpl_cps_loss_fwd_bwd.argtypes = [SP, i32, i32, vp, vp, HP, vp, vp, vp, vp, sz, vp]
+    lib.cmlpl_ema_update.argtypes = [vp, vp, i64, C.c_double, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

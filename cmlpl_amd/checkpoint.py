@@ -5,7 +5,8 @@ file holds is ``TrainEngine.checkpoint_state()`` -- the flat parameter / Adam bu
 pointers, the step counters that key the in-kernel noise and dropout streams, the two-piece range flag words of each
 network, and an ``identity`` record that ``load_checkpoint_state`` checks (``check_identity``) -- plus ``"Base"`` and
 ``"Base1"``, the two networks as ``state_dict``s with the reference's 16 keys (they load into this package's
-``BaseNet2`` and into the reference's class alike), plus whatever the driver adds under ``"extra"`` (train.py: the
+``BaseNet2`` and into the reference's class alike), plus -- from an engine that keeps an EMA teacher (``teacher_alpha``)
+only -- ``teacher_params`` and ``"Teacher"`` / ``"Teacher1"``, the averaged weights in the same two forms, plus whatever the driver adds under ``"extra"`` (train.py: the
 epoch reached, ``loss_hist`` so far, the validation curve, the permutation generator's state).
 
 Tensors, numbers, strings, lists and dicts only: a file is read with ``torch.load(weights_only=True)``, nothing in it
@@ -31,16 +32,19 @@ class CheckpointError(RuntimeError):
 
 
 def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_hash: str, abi: int,
-                  method: str = "cmlpl") -> Dict[str, Any]:
+                  method: str = "cmlpl", teacher_alpha: Optional[float] = None) -> Dict[str, Any]:
     """the record ``check_identity`` compares: plain dicts and numbers (``NetShape`` / ``HyperParams`` by field).  The
     training ``method`` is part of it; a CMLPL record carries no ``method`` key (what it held before there was a second
-    method: such files still load, and a record without the key reads as ``cmlpl``)."""
+    method: such files still load, and a record without the key reads as ``cmlpl``).  ``teacher_alpha``: the coefficient of
+    an engine that keeps an EMA teacher -- a key only such an engine's record has (without one the record is what it was)."""
     from dataclasses import asdict
     rec = dict(shape={k: int(v) for k, v in asdict(shape).items()},
                hp={k: (int(v) if isinstance(v, int) and not isinstance(v, bool) else float(v)) for k, v in asdict(hp).items()},
                bt=int(bt_global), btu=int(btu_global), Q=int(Q), source_hash=str(source_hash), abi=int(abi))
     if method != "cmlpl":
         rec["method"] = str(method)
+    if teacher_alpha is not None:
+        rec["teacher_alpha"] = float(teacher_alpha)
     return rec
 
 
@@ -63,6 +67,10 @@ def identity_differences(saved: Dict[str, Any], mine: Dict[str, Any]) -> List[st
     for k in ("bt", "btu", "Q", "abi"):
         if saved.get(k) != mine.get(k):
             out.append(f"{k}: file {saved.get(k)!r}, here {mine.get(k)!r}")
+    # (a teacher on one side only is no difference: an engine with one starts it from the file's parameters, an engine
+    #  without one leaves the file's aside -- two different coefficients are two different averages)
+    if "teacher_alpha" in saved and "teacher_alpha" in mine and saved["teacher_alpha"] != mine["teacher_alpha"]:
+        out.append(f"teacher_alpha: file {saved['teacher_alpha']!r}, here {mine['teacher_alpha']!r}")
     return out
 
 

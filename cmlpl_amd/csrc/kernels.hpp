@@ -356,6 +356,9 @@ hipError_t launch_adam(int nets, float* params, long long pstride, const float* 
                        float* packed, const PackInfo& pi, hipStream_t st, DynRef dyn = DynRef());
 void adam_bias_scalars(float lr, float b1, float b2, long long t, float* step_size, float* bc2_sqrt);
 
+// ---- ema.hip  (the weight average of reference tools/models.py:155-164: ema = fl(fl(src * oma) + fl(ema * alpha)))
+hipError_t launch_ema(const float* src, float* ema, long long count, float alpha, float oma, hipStream_t st);
+
 
 // ---- memobank.hip  (loss_helper.py)
 hipError_t launch_mb_select(const float* prob, const float* label, const float* low_mask, const float* high_mask, int N,

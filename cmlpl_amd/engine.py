@@ -43,6 +43,46 @@ def _chk_f32(t: torch.Tensor, shape, name):
                          f"got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+class Teacher:
+    """The averaged weights of an engine built with ``teacher_alpha`` (``eng.teacher``), with what
+    ``cmlpl_amd.infer._nets_buffers`` / ``_net_buffers`` read from an engine: ``(eng.teacher, None)`` and
+    ``(eng.teacher, k)`` go where ``(eng, None)`` and ``(eng, k)`` go -- ``infer_cube``, ``infer_pixels``,
+    ``Evaluator.evaluate``.  The packed fragment sets of the averaged weights are a block of their own, allocated at first
+    use and rebuilt (one full ``cmlpl_pack_weights``) only when the teacher has changed since they were last built."""
+
+    def __init__(self, eng: "TrainEngine"):
+        self._eng = eng
+        self._packed = None
+        self._dirty = True
+
+    cshape = property(lambda self: self._eng.cshape)
+    device = property(lambda self: self._eng.device)
+
+    @property
+    def params(self) -> torch.Tensor:
+        self._eng._teacher_begin()
+        return self._eng.teacher_params
+
+    @property
+    def packed(self) -> torch.Tensor:
+        if self._packed is None:
+            self._packed = torch.zeros_like(self._eng.packed)
+            self._dirty = True
+        return self._packed
+
+    def _ensure_packed(self, stream) -> None:
+        eng = self._eng
+        flat, packed = self.params, self.packed
+        if self._dirty:
+            _lib.check("cmlpl_pack_weights",
+                       eng.lib.cmlpl_pack_weights(C.byref(eng.cshape), 2, _ptr(flat), eng.P, _ptr(packed), stream))
+            self._dirty = False
+
+    def state_dict(self, net: int) -> "OrderedDict[str, torch.Tensor]":
+        eng = self._eng
+        return OrderedDict((k, eng.view(self.params, net, k).detach().clone()) for k in eng.state_dict_keys())
+
+
 class TrainEngine:
     """Both networks (Base = net 0 / "s", Base1 = net 1 / "w"), their Adam state and
     the two memory banks, resident in HBM for the whole run.
@@ -56,14 +96,25 @@ class TrainEngine:
     step is forward -> CPS loss (one launch) -> backward -> Adam; the banks stay allocated and untouched, ``epoch`` /
     ``batch_index`` of ``step`` play no part, ``hp.w_mutual`` is set to the reference's cross-loss weight 0.1, and
     ``loss_row`` / ``loss_window`` give the reference's row ``[con, total, cls, con, acc]`` (trian_CPS.py:254-258).
+
+    ``teacher_alpha``: keep an exponential moving average of both networks' weights, the reference's
+    ``WeightEMA_BN(Base, Ensemble, alpha)`` (tools/models.py:155-164) applied to the whole flat parameter block -- dead
+    tensors and padding too -- behind every step that applies its update: one ``cmlpl_ema_update`` launch on the step's
+    stream, eager or behind a graph replay.  The average starts as a copy of the parameters, made in front of the first
+    step after construction, ``load_state_dict`` or ``init_params_default`` (``teacher_reset()`` makes it on demand);
+    ``eng.teacher`` (``Teacher``) is what evaluates and saves it.  None (the default): no buffer, no launch, and a
+    checkpoint is byte for byte what it is without the feature.
     """
     takes_indices = True      # step(..., lab_idx=, unl_idx=): batches as row indices into the resident splits
     takes_cube = True         # step(None, Xl, Y, None, Xu, ..., cube=, lab_pix=, unl_pix=): windows gathered from the scene
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
-                 hist_rows: int = 1, method: str = "cmlpl"):
+                 hist_rows: int = 1, method: str = "cmlpl", teacher_alpha: Optional[float] = None):
         self.method = check_method(method)
+        if teacher_alpha is not None and not 0.0 <= float(teacher_alpha) <= 1.0:       # (a NaN fails both comparisons)
+            raise ValueError(f"teacher_alpha {teacher_alpha!r}: a coefficient in [0, 1]")
+        self.teacher_alpha = None if teacher_alpha is None else float(teacher_alpha)
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("cmlpl_amd.TrainEngine needs a GPU (no CPU fallback)")
@@ -114,6 +165,10 @@ class TrainEngine:
         self._captured = False      # a StepGraph of this engine exists: its kernels' arguments hold the seed
         self._flag_off = None       # offset of the range flag words inside a network's packed block (asked of the library)
         self._saved_flags = None    # load_checkpoint_state: flag words to OR back in behind the next full pack
+        # the EMA teacher: [2][param_stride] beside the parameters; stale = to be started from them in front of the next step
+        self.teacher_params = z(2, self.P) if self.teacher_alpha is not None else None
+        self.teacher = Teacher(self) if self.teacher_alpha is not None else None
+        self._teacher_stale = True
 
     @property
     def scalars(self) -> torch.Tensor:
@@ -149,6 +204,7 @@ class TrainEngine:
             if key in sd:
                 self.view(self.params, net, key).copy_(sd[key].to(self.device, torch.float32))
         self._packed_dirty = True
+        self._teacher_stale = True
 
     def state_dict(self, net: int) -> "OrderedDict[str, torch.Tensor]":
         return OrderedDict((k, self.view(self.params, net, k).detach().clone()) for k in self.state_dict_keys())
@@ -169,6 +225,26 @@ class TrainEngine:
                 b = 1.0 / (fan_in ** 0.5)
                 self.view(self.params, net, key).copy_((torch.rand(shp, generator=g) * 2 - 1) * b)
         self._packed_dirty = True
+        self._teacher_stale = True
+
+    # ------------------------------------------------------------------ the EMA teacher
+    def teacher_reset(self) -> None:
+        """the teacher := the parameters as they are now (stream-ordered device copy)"""
+        if self.teacher is None:
+            raise RuntimeError("teacher_reset(): an engine built with teacher_alpha")
+        self.teacher_params.copy_(self.params)
+        self.teacher._dirty = True
+        self._teacher_stale = False
+
+    def _teacher_begin(self) -> None:
+        if self.teacher is not None and self._teacher_stale:
+            self.teacher_reset()
+
+    def _teacher_update(self, stream) -> None:
+        """behind a step that has applied its update: teacher = params * (1 - alpha) + teacher * alpha over the whole block"""
+        _lib.check("cmlpl_ema_update", self.lib.cmlpl_ema_update(_ptr(self.params), _ptr(self.teacher_params),
+                                                                 2 * self.P, self.teacher_alpha, stream))
+        self.teacher._dirty = True
 
     def _ensure_packed(self, stream) -> None:
         if self._packed_dirty:
@@ -202,7 +278,8 @@ class TrainEngine:
         from .checkpoint import make_identity
         W = getattr(self, "world", 1)
         return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
-                             self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method)
+                             self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method,
+                             teacher_alpha=getattr(self, "teacher_alpha", None))
 
     def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
         """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
@@ -217,6 +294,11 @@ class TrainEngine:
                    range_flags=self._flag_words())
         for net, key in enumerate(("Base", "Base1")):
             src[key] = OrderedDict((k, self.view(self.params, net, k)) for k in self.state_dict_keys())
+        if getattr(self, "teacher", None) is not None:
+            self._teacher_begin()
+            src["teacher_params"] = self.teacher_params
+            for net, key in enumerate(("Teacher", "Teacher1")):
+                src[key] = OrderedDict((k, self.view(self.teacher_params, net, k)) for k in self.state_dict_keys())
         if into is not None:
             st = into
             for k, t in src.items():
@@ -261,6 +343,19 @@ class TrainEngine:
         self.adam_t, self.step_count = int(state["adam_t"]), int(state["step_count"])
         self._saved_flags = flags.to(self.device).clone()
         self._packed_dirty = True
+        if getattr(self, "teacher", None) is not None:
+            # (a state without a teacher: the average starts from the loaded parameters; an engine without one ignores
+            #  the state's)
+            t = state.get("teacher_params")
+            if t is None:
+                self.teacher_reset()
+            else:
+                if tuple(t.shape) != tuple(self.teacher_params.shape) or t.dtype != torch.float32:
+                    raise ValueError(f"teacher_params: need float32 {tuple(self.teacher_params.shape)}, the checkpoint has "
+                                     f"{t.dtype} {tuple(t.shape)}")
+                self.teacher_params.copy_(t)
+                self.teacher._dirty = True
+                self._teacher_stale = False
 
     def _set_seed(self) -> None:
         self._io.seed = self.seed
@@ -428,6 +523,7 @@ class TrainEngine:
         n = bt + btu
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._ensure_packed(stream)
+        self._teacher_begin()
         io = self._io
         self._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube, lab_pix, unl_pix)
         io.noise8, io.d_dropmask = None, None
@@ -453,6 +549,8 @@ class TrainEngine:
         io.apply_update = 1 if apply_update else 0
         _lib.check("cmlpl_train_step",
                    self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
+        if self.teacher is not None and apply_update:
+            self._teacher_update(stream)
         self._advance(n, apply_update)
         self._last_btu = btu
 
@@ -638,7 +736,10 @@ class StepGraph:
             raise RuntimeError("no programmed step left: call program() first")
         stream = C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)
         eng._ensure_packed(stream)            # set_params / load_state_dict between replays: the packed copies follow
+        eng._teacher_begin()
         _lib.check("cmlpl_step_graph_launch", eng.lib.cmlpl_step_graph_launch(self.handle, stream))
+        if eng.teacher is not None:           # one eager launch behind the replay: the captured step is what it was
+            eng._teacher_update(stream)
         eng._cur_row = eng.step_count % eng.hist_rows
         eng._advance(self.bt + self.btu, True)
         eng._last_btu = self.btu

@@ -1,4 +1,4 @@
-"""Drop-in ``BaseNet2`` / ``Normalize`` (reference tools/models.py:81-90,97-152) on the HIP path.
+"""Drop-in ``BaseNet2`` / ``Normalize`` / ``WeightEMA_BN`` (reference tools/models.py:81-90,97-152,155-164) on the HIP path.
 
 Same constructor, same 16 ``state_dict`` keys and shapes, same
 ``forward(x, y) -> (logits, l2-normalised 1024-d feature)``; forward and backward run in
@@ -205,3 +205,39 @@ class ContrastiveLoss(nn.Module):
         if emb_i.shape != emb_j.shape or emb_i.shape[0] != self.batch_size:
             raise ValueError("emb_i / emb_j must both be [batch_size, D]")
         return _NTXentFn.apply(emb_i.contiguous().float(), emb_j.contiguous().float(), self._temperature)
+
+
+def WeightEMA_BN(Base, Ensemble, alpha):
+    """Drop-in for the reference's tools.models.WeightEMA_BN (tools/models.py:155-164): every entry of ``Ensemble``'s
+    ``state_dict`` becomes ``Base's * (1 - alpha) + Ensemble's * alpha``, in place; returns ``Ensemble``.  Any two modules
+    with the same ``state_dict`` keys and shapes; their floating entries are contiguous fp32 on the GPU and go through
+    ``cmlpl_ema_update``, one launch per tensor on the current stream (bit for bit the reference's fp32 result: two
+    rounded products and their rounded sum).  An entry of another dtype (BatchNorm's ``num_batches_tracked``) is left as
+    the reference's ``load_state_dict`` leaves it: the fp32 expression, cast back."""
+    lib = _lib.load()
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha {alpha!r}: a coefficient in [0, 1]")
+    base, ens = Base.state_dict(), Ensemble.state_dict()
+    if list(base) != list(ens):
+        raise ValueError("WeightEMA_BN: the two modules' state_dict keys differ")
+    for k in ens:
+        b, e = base[k], ens[k]
+        if not (b.is_cuda and e.is_cuda):
+            raise RuntimeError(f"WeightEMA_BN runs on the GPU only (no CPU fallback); {k!r} is on {b.device} / {e.device}")
+        if b.shape != e.shape or b.dtype != e.dtype or b.device != e.device:
+            raise ValueError(f"WeightEMA_BN: {k!r} is {b.dtype} {tuple(b.shape)} on {b.device} in Base, {e.dtype} "
+                             f"{tuple(e.shape)} on {e.device} in Ensemble")
+    with torch.no_grad():
+        for k in ens:
+            b, e = base[k], ens[k]
+            if not e.is_floating_point():
+                e.copy_(b * (1.0 - alpha) + e * alpha)
+                continue
+            if e.dtype != torch.float32 or not (b.is_contiguous() and e.is_contiguous()):
+                raise ValueError(f"WeightEMA_BN: {k!r} must be contiguous float32, got {e.dtype}")
+            with torch.cuda.device(e.device):
+                stream = C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
+                _lib.check("cmlpl_ema_update", lib.cmlpl_ema_update(b.data_ptr(), e.data_ptr(), e.numel(), alpha, stream))
+            torch.autograd.graph.increment_version(e)       # written behind torch's back: BaseNet2's flat copy follows
+    return Ensemble

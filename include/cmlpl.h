@@ -540,6 +540,23 @@ int cmlpl_cps_loss_fwd_bwd(const cmlpl_shape* shape, int bt, int btu, const floa
                            const cmlpl_hparams* hp, float* d_scalars, float* d_dlogits, int64_t* d_pseudo,
                            void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- the EXPONENTIAL MOVING AVERAGE of the weights, the "teacher"
+ * (reference tools/models.py:155-164 WeightEMA_BN: Ensemble = Base * (1 - alpha) + Ensemble * alpha).
+ *
+ * cmlpl_ema_update: d_ema[i] = fl( fl(d_src[i] * oma) + fl(d_ema[i] * a) ) for i < count, a = (float)alpha,
+ *   oma = (float)(1.0 - alpha): three separately rounded fp32 operations, never an FMA -- what the reference's two tensor
+ *   products and their sum round to, bit for bit.  `alpha` is a DOUBLE because the reference forms 1 - alpha in double
+ *   before the product rounds it to fp32: (float)(1.0 - 0.95) and 1.0f - (float)0.95 are three ulps apart, and with the
+ *   second the result differs from the reference's in nearly every other element.
+ *   One contiguous range, any count, any 4-byte aligned pointers (16-byte accesses where both are aligned alike, single
+ *   floats otherwise); d_src == d_ema is allowed (each element is read before it is written); NaN and infinity propagate
+ *   as the arithmetic says.  One kernel launch, no atomics, no workspace, no synchronisation, no other host call: it can
+ *   be captured in a graph.  count == 0 returns 0 without a launch.  CMLPL_E_ARG: count < 0, alpha outside [0, 1] or not
+ *   finite, a null or misaligned pointer with count > 0.
+ * cmlpl_amd.TrainEngine(teacher_alpha=) enqueues it over both networks' whole parameter block behind every step that
+ * applies its update (and behind every graph replay); cmlpl_amd.models.WeightEMA_BN calls it once per tensor. */
+int cmlpl_ema_update(const float* d_src, float* d_ema, int64_t count, double alpha, void* stream);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the

@@ -8,7 +8,7 @@ The window shape and the class count come from the checkpoint (cmlpl_amd.checkpo
 directory's ``cube.npy`` + ``scene.json`` (``HSIDataSet(.., 'wholeset').cube_source``), labelled on the device by
 ``cmlpl_infer_cube`` through ``tools.hyper_tools.test_whole`` -- the end-of-run evaluation of ``train.py``
 (``train.evaluate_whole``), without a training engine.  ``--out`` receives the int64 label map [rows * cols]
-(``--net both``: [2][rows * cols]); when the directory has ``test_array.npy`` / ``Y.npy`` the ``Result:`` / ``producerA`` /
+(``--net both``: [2][rows * cols]; ``--net ema0 | ema1 | ema_both``: the EMA teachers of a ``train.py --ema`` run); when the directory has ``test_array.npy`` / ``Y.npy`` the ``Result:`` / ``producerA`` /
 ``AA`` lines of ``train.py`` are printed.  ``--synthetic SHAPE`` labels the seeded synthetic scene that
 ``train.py --synthetic`` evaluates on (datasets are not shipped)."""
 import argparse
@@ -44,12 +44,20 @@ def main(args, device=None):
         if os.path.exists(whole.root + 'test_array.npy') and os.path.exists(whole.root + 'Y.npy'):
             test_array = np.load(whole.root + 'test_array.npy')
             Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
-    which = [0, 1] if args.net == 'both' else [int(args.net)]
-    preds = evaluate_whole(shape, whole, [(k, ck["Base" if k == 0 else "Base1"]) for k in which], device,
+    both = args.net in ('both', 'ema_both')
+    if args.net.startswith('ema'):
+        which = ['ema0', 'ema1'] if both else [args.net]
+        if "Teacher" not in ck or "Teacher1" not in ck:
+            raise SystemExit("--net %s: %s holds no EMA teacher (\"Teacher\" / \"Teacher1\"): it was written by a run "
+                             "without train.py --ema" % (args.net, args.ckpt))
+    else:
+        which = [0, 1] if both else [int(args.net)]
+    keys = {0: "Base", 1: "Base1", 'ema0': "Teacher", 'ema1': "Teacher1"}
+    preds = evaluate_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device,
                            synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"],
                            val_batch_size=args.val_batch_size, test_array=test_array, Y_test=Y_test)
     labels = np.stack([preds[k] for k in which]).astype(np.int64)
-    labels = labels if args.net == 'both' else labels[0]
+    labels = labels if both else labels[0]
     if args.out:
         np.save(args.out, labels)
     return labels
@@ -59,7 +67,9 @@ def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     parser.add_argument('--ckpt', required=True, help='a checkpoint of train.py --save_ckpt / --save_best')
     parser.add_argument('--dataID', type=int, default=1)
-    parser.add_argument('--net', choices=('0', '1', 'both'), default='0', help='Base (0), Base1 (1) or both')
+    parser.add_argument('--net', choices=('0', '1', 'both', 'ema0', 'ema1', 'ema_both'), default='0',
+                        help="Base (0), Base1 (1) or both; ema0 / ema1 / ema_both: their EMA teachers (a checkpoint of "
+                             "train.py --ema)")
     parser.add_argument('--out', default=None, help='write the int64 label map as .npy ([rows*cols]; both: [2][rows*cols])')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')

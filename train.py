@@ -24,6 +24,10 @@ Differences from the reference that are deliberate, MI355X-first choices:
   * ``--method cps``: the cross-pseudo-supervision baseline of the reference's ``trian_CPS.py`` instead of CMLPL, on the
     same two networks, loaders, evaluation and checkpoints (one GPU; ``trian_CPS.py`` here presets it).  The printed
     line is the shared one: for CPS ``loss_contrast`` repeats ``con_loss`` (trian_CPS.py:254).
+  * ``--ema``: an exponential moving average of both networks' weights (the reference's ``WeightEMA_BN``, coefficient
+    ``--teacher_alpha``) is kept on the device, updated behind every step (one launch; also behind a graph replay), scored
+    by ``--eval_every`` on two more lines (``validation_ema`` / ``validation_ema1``), saved with every checkpoint
+    (``"Teacher"`` / ``"Teacher1"``) and evaluated after the run.  One GPU.  Without it ``--teacher_alpha`` is ignored.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -93,6 +97,8 @@ def run_record(args, hp, shape, from_scene):
     rec = {k: getattr(args, k) for k in RUN_FLAGS}
     if run_method(args) != "cmlpl":       # (a CMLPL run's record is what it was before there was a second method)
         rec["method"] = run_method(args)
+    if run_ema(args):                     # (and a run without a teacher's is what it was before there was one)
+        rec.update(ema=True, teacher_alpha=args.teacher_alpha)
     rec.update(shape=[int(v) for v in shape], data=("synthetic %s%s" % (args.synthetic, " scene" if from_scene else ""))
                if args.synthetic else "dataID %d" % int(args.dataID))
     return rec
@@ -102,13 +108,22 @@ def run_method(args):
     return getattr(args, "method", "cmlpl")
 
 
+def run_ema(args):
+    return bool(getattr(args, "ema", False))
+
+
 def run_differences(saved, mine):
-    return ["%s: file %r, here %r" % (k, saved.get(k), mine[k]) for k in mine if saved.get(k) != mine[k]]
+    keys = list(mine) + [k for k in ("ema", "teacher_alpha") if k in saved and k not in mine]     # --ema: both ways
+    return ["%s: file %r, here %r" % (k, saved.get(k), mine.get(k)) for k in keys if saved.get(k) != mine.get(k)]
+
+
+NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1'}      # evaluate_whole: a network, or a network's EMA teacher
 
 
 def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
                    test_array=None, Y_test=None, resident_cube=None, last_eval=None):
-    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index, state_dict)]: the end of a
+    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index -- or 'ema0' / 'ema1', a
+    network's EMA teacher --, state_dict)]: the end of a
     training run, and all of predict.py.  Returns {network index: int64 label per scene pixel}.
     The scene stays in HBM as its cube and the forward gathers the windows itself (cmlpl_infer_cube): no 19.9 GB patch
     tensor, no DataLoader (train.py:291-294 streams the materialised patches).  Window shapes the per-sample forward does
@@ -147,11 +162,11 @@ def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
         if test_array is None:
             continue
         OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
-        tag = '' if net == 0 else '1'
+        tag = NET_TAGS[net]
         print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
         print('producerA%s:' % tag, producerA * 100)
         print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
-        if last_eval is not None:
+        if last_eval is not None and net in (0, 1):
             # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
             same = last_eval[net][0] == OA
             print('validation check%s: matrix OA %s whole-image OA (%.6f / %.6f)' %
@@ -168,6 +183,8 @@ def main(args, make_engine=None, device=None):
     if method != "cmlpl" and world > 1:      # before any device or communicator work
         raise SystemExit(f"--method {method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
                          f"{world} ranks)")
+    if run_ema(args) and world > 1:
+        raise SystemExit(f"--ema runs on one GPU: the sharded engine keeps no EMA teacher (this job has {world} ranks)")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -210,7 +227,8 @@ def main(args, make_engine=None, device=None):
         eng = DistTrainEngine(NetShape(*shape), bt // world, btu // world, hp, device=device, seed=1088, hist_rows=ppb)
     else:
         from cmlpl_amd import TrainEngine
-        eng = TrainEngine(NetShape(*shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=method)
+        eng = TrainEngine(NetShape(*shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=method,
+                          teacher_alpha=args.teacher_alpha if run_ema(args) else None)
     eng.init_params_default(1088)
 
     gen = torch.Generator().manual_seed(1088)                        # same permutations on every rank
@@ -252,6 +270,8 @@ def main(args, make_engine=None, device=None):
         lab_loader = DeviceLoader(labeled.device_arrays(device), bt, gen)
         unl_loader = DeviceLoader(unlabeled.device_arrays(device), btu, gen)
     evaluator, eval_log, eval_cms = None, [], []          # --eval_every: (epoch, [net][OA, AA, Kappa]) and the matrices
+    ema = run_ema(args)
+    eval_log_ema, eval_cms_ema = [], []                   # --ema: the same two of the teachers, a curve of their own
     if args.eval_every > 0 and rank == 0:
         # the test split registered once: its pixels, spectra and labels beside the resident cube (rank 0 evaluates, as
         # after the last epoch; its own generators: no draw of the training streams is consumed)
@@ -283,6 +303,10 @@ def main(args, make_engine=None, device=None):
         if evaluator is not None:      # (the curve so far: a leg without --eval_every leaves a gap, not an error)
             eval_log = [(int(e), [[float(v) for v in net] for net in row]) for e, row in zip(ex["eval_epochs"], ex["eval_curve"].tolist())]
             eval_cms = [cm for cm in ex["eval_cms"].numpy()]
+            if ema and "eval_curve_ema" in ex:
+                eval_log_ema = [(int(e), [[float(v) for v in net] for net in row])
+                                for e, row in zip(ex["eval_epochs_ema"], ex["eval_curve_ema"].tolist())]
+                eval_cms_ema = [cm for cm in ex["eval_cms_ema"].numpy()]
     index_i = start_epoch * num_batches - 1
     best_oa, best_state, best_extra = None, None, None               # --save_best
     if eval_log:
@@ -291,12 +315,18 @@ def main(args, make_engine=None, device=None):
     def run_extra(epochs_done):
         """what this driver adds to a checkpoint written after ``epochs_done`` epochs"""
         done = epochs_done * num_batches
+        more = {}
+        if ema:
+            more = dict(eval_epochs_ema=[e for e, _ in eval_log_ema],
+                        eval_curve_ema=torch.tensor([r for _, r in eval_log_ema], dtype=torch.float64).reshape(len(eval_log_ema), 2, 3),
+                        eval_cms_ema=torch.from_numpy(np.stack(eval_cms_ema)) if eval_cms_ema else
+                        torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64))
         return dict(epoch=epochs_done, num_batches=num_batches, loss_hist=torch.from_numpy(loss_hist[:done].copy()),
                     eval_epochs=[e for e, _ in eval_log],
                     eval_curve=torch.tensor([r for _, r in eval_log], dtype=torch.float64).reshape(len(eval_log), 2, 3),
                     eval_cms=torch.from_numpy(np.stack(eval_cms)) if eval_cms else torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64),
-                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items() if not (k == 'method' and v == 'cmlpl')},
-                    run=run_record(args, hp, shape, from_scene), world=world)
+                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items() if not (k == 'method' and v == 'cmlpl') and not (k == 'ema' and not v)},
+                    run=run_record(args, hp, shape, from_scene), world=world, **more)
     pending = []                      # loss_hist rows of the steps run since the last read-back of the device ring
 
     def read_back():
@@ -368,6 +398,17 @@ def main(args, make_engine=None, device=None):
                       (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
             eval_log.append((epoch + 1, row))
             eval_cms.append(cms)
+            if ema:
+                # the teachers: their packed weights are rebuilt here, when they are read, not behind every step
+                cms_t = evaluator.evaluate((eng.teacher, None)).cpu().numpy()
+                row_t = []
+                for net in range(2):
+                    OA, Kappa, _, AA = evaluator.metrics(cms_t[net])
+                    row_t.append((OA, AA, Kappa))
+                    print('Epoch %d/%d: validation_ema%s OA = %.2f AA = %.2f Kappa = %.2f' %
+                          (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
+                eval_log_ema.append((epoch + 1, row_t))
+                eval_cms_ema.append(cms_t)
             if args.save_best and (best_oa is None or row[0][0] > best_oa):
                 # network 0's best validation so far (the first of equals): the state is copied on the device, behind
                 # the step that produced it on the stream -- no synchronisation, no file until the run is over
@@ -404,9 +445,16 @@ def main(args, make_engine=None, device=None):
             best = int(np.argmax(curve[:, net, 0]))                   # (the first of equal bests)
             print('best validation%s: epoch %d OA = %.2f' % ('' if net == 0 else '1', epochs[best], curve[best, net, 0] * 100))
         if args.save_eval:
-            np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms))
+            more = {}
+            if ema and eval_log_ema:
+                more = dict(curve_ema=np.array([r for _, r in eval_log_ema]), cm_ema=np.stack(eval_cms_ema),
+                            epochs_ema=np.array([e for e, _ in eval_log_ema]))
+            np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms), **more)
     if rank == 0 and not args.no_eval:
-        evaluate_whole(shape, whole, [(net, eng.state_dict(net)) for net in range(2)], device, synthetic=args.synthetic,
+        nets = [(net, eng.state_dict(net)) for net in range(2)]
+        if ema:
+            nets += [('ema%d' % net, eng.teacher.state_dict(net)) for net in range(2)]
+        evaluate_whole(shape, whole, nets, device, synthetic=args.synthetic,
                        dataID=args.dataID, dropout=args.dropout, val_batch_size=args.val_batch_size,
                        test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"),
                        last_eval=eval_log[-1][1] if eval_log and eval_log[-1][0] == args.num_epochs else None)
@@ -435,7 +483,8 @@ def build_parser():
     parser.add_argument('--queue-batch', type=float, default=17, help='number of batches stored in memory bank')
     parser.add_argument('--temperature', default=0.3, type=float, help='softmax temperature')
     # network
-    parser.add_argument('--teacher_alpha', type=float, default=0.95)
+    parser.add_argument('--teacher_alpha', type=float, default=0.95,
+                        help='--ema: the coefficient of the moving average (ignored without --ema)')
     parser.add_argument('--dropout', type=float, default=0.8)
     parser.add_argument('--noise', type=float, default=0.5)
     parser.add_argument('--m', type=int, default=5, help='number of stochastic augmentations')
@@ -444,6 +493,10 @@ def build_parser():
                         help="the training method: 'cmlpl' (the reference's train.py) or 'cps', the cross-pseudo-supervision "
                              "baseline of its trian_CPS.py (labelled CE + 0.1 x each network's CE against the other's "
                              "hard label; one GPU)")
+    parser.add_argument('--ema', action='store_true',
+                        help="keep an exponential moving average of both networks' weights (the reference's WeightEMA_BN, "
+                             "coefficient --teacher_alpha), updated on the device behind every step; --eval_every scores it "
+                             "too, checkpoints carry it as \"Teacher\" / \"Teacher1\" (one GPU)")
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

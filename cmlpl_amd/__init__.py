@@ -4,6 +4,7 @@ Public surface:
   NetShape, HyperParams ........ shape / flag records
   TrainEngine .................. the fused training step (train.py:150-278 of the reference)
   BaseNet2 ..................... drop-in nn.Module (tools/models.py:97-152 of the reference)
+  ensemble_logits / _cube / _pixels ... averaged probabilities, label, confidence, entropy of 1..4 networks
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name in ("BaseNet2", "Normalize", "WeightEMA_BN"):
         from . import models
         return getattr(models, name)
+    if name in ("ensemble_logits", "ensemble_cube", "ensemble_pixels", "EnsembleResult"):
+        from . import ensemble
+        return getattr(ensemble, name)
     raise AttributeError(name)

@@ -40,6 +40,7 @@ EXPORTS = (
     "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
     "cmlpl_debug_conv3_plan", "cmlpl_debug_route",                               # added after ABI 6, no bump: test aids
     "cmlpl_ema_update",                                                          # added after ABI 6, no bump: the EMA teacher
+    "cmlpl_ensemble",                                                            # added after ABI 6, no bump: ensemble prediction
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
@@ -245,6 +246,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_cps_loss_workspace_bytes.restype = sz
     lib.cmlpl_cps_loss_fwd_bwd.argtypes = [SP, i32, i32, vp, vp, HP, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_ema_update.argtypes = [vp, vp, i64, C.c_double, vp]
+    lib.cmlpl_ensemble.argtypes = [vp, i32, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

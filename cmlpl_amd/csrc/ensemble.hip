@@ -1,0 +1,148 @@
+// Ensemble prediction of 1..4 networks' logits: what lies between the eval forward's logits and a result.  Per pixel i:
+//   p_m      = softmax(z_m[i]) in fp32, the maximum subtracted first, expf and a division as in cps_loss.hip --
+//              torch.softmax's semantics: a member row that holds a NaN or a +inf is NaN everywhere, -inf logits give 0
+//   p        = sum_m w_m p_m, m ascending; the weights arrive by value, normalised on the host (in double, then rounded)
+//   label    = the FIRST maximum of p; a NaN counts as the maximum and the first NaN wins (torch.max's rule, as in
+//              cmlpl_infer_cube)
+//   conf     = p[label]
+//   entropy  = -sum_c p_c logf(p_c), 0 log 0 = 0; NaN when p is NaN
+//   disagree = the number of members whose own label (the same rule on p_m) is not `label`
+//
+// A group of G lanes per pixel, G the smallest power of two >= K (1 .. 64): a wave holds 64 / G pixels, lane c of a group
+// owns class c, padding lanes carry -inf into the maxima and 0 into the sums and never store.  Every reduction is a
+// __shfl_xor butterfly of width G: both partners of a stage add (or compare) the same two values, so every lane of a
+// group ends with the same bits, in an order that depends on G alone -- the results are the same bytes on every run,
+// whatever the grid.  No LDS, no atomics, no scratch; a grid-stride loop over blocks of 256 / G pixels, whose trip count
+// is the same for every lane of a workgroup (the shuffles are never divergent); plain loads and stores.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <cmath>
+#include <stdint.h>
+
+#include "../../include/cmlpl.h"
+
+namespace cmlpl {
+namespace {
+
+constexpr int ENS_THREADS = 256;
+constexpr int ENS_MAX_MEMBERS = 4;
+constexpr int ENS_WG_MAX = 4096;      // past ENS_WG_MAX workgroups the grid strides over the pixels
+
+struct EnsArgs {
+  const float* logits; long long member_stride;
+  float w[ENS_MAX_MEMBERS];
+  int members, n, K;
+  long long* labels; float* probs; float* conf; float* entropy; int* disagree;
+};
+
+template <int G> __device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int G> __device__ __forceinline__ float group_max(float v) {     // (fmaxf: the maximum of what is not NaN)
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// torch.max(v, 1)[1] of the row a group holds one class per lane: the first index of the maximum; a NaN counts as the
+// maximum and the first NaN wins.  mx = group_max(v); kv = this lane owns a class
+template <int G> __device__ __forceinline__ int group_argmax(float v, float mx, bool kv, int shift) {
+  const unsigned long long mask = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
+  const unsigned long long nanb = (__ballot(kv && v != v) >> shift) & mask;
+  const unsigned long long eqb = (__ballot(kv && v == mx) >> shift) & mask;
+  return __ffsll((long long)(nanb ? nanb : eqb)) - 1;
+}
+
+template <int G> __global__ __launch_bounds__(ENS_THREADS) void ensemble_kernel(EnsArgs a) {
+  constexpr int PPW = ENS_THREADS / G;                  // pixels per workgroup and trip
+  const int tid = threadIdx.x;
+  const int c = tid & (G - 1);                          // the class this lane owns
+  const int shift = (tid & 63) & ~(G - 1);              // the first lane of this group within its wave
+  const int K = a.K, n = a.n;
+  const bool kv = c < K;
+  const float NEG_INF = -INFINITY;
+  for (long long base = (long long)blockIdx.x * PPW; base < n; base += (long long)gridDim.x * PPW) {
+    const long long i = base + tid / G;
+    const bool live = kv && i < n;                      // (a group past the last pixel runs on padding and stores nothing)
+    float p = 0.f;
+    int lab_m[ENS_MAX_MEMBERS] = {0, 0, 0, 0};
+#pragma unroll
+    for (int m = 0; m < ENS_MAX_MEMBERS; ++m) {
+      if (m < a.members) {
+        const float z = live ? a.logits[m * a.member_stride + i * K + c] : NEG_INF;
+        const float mx = group_max<G>(z);
+        const float e = live ? expf(z - mx) : 0.f;
+        const float s = group_sum<G>(e);
+        const float pm = live ? e / s : 0.f;
+        lab_m[m] = group_argmax<G>(pm, group_max<G>(pm), kv, shift);
+        p += a.w[m] * pm;
+      }
+    }
+    const int label = group_argmax<G>(p, group_max<G>(p), kv, shift);
+    const float plab = __shfl(p, shift + label, 64);
+    const float t = (p == 0.f) ? 0.f : p * logf(p);     // (a NaN p is not 0: it goes through)
+    const float ent = 0.f - group_sum<G>(kv ? t : 0.f);
+    if (live) {
+      if (a.probs != nullptr) a.probs[i * K + c] = p;
+      if (c == 0) {
+        a.labels[i] = label;
+        if (a.conf != nullptr) a.conf[i] = plab;
+        if (a.entropy != nullptr) a.entropy[i] = ent;
+        if (a.disagree != nullptr) {
+          int d = 0;
+#pragma unroll
+          for (int m = 0; m < ENS_MAX_MEMBERS; ++m) d += (m < a.members && lab_m[m] != label) ? 1 : 0;
+          a.disagree[i] = d;
+        }
+      }
+    }
+  }
+}
+
+template <int G> hipError_t launch_g(const EnsArgs& a, hipStream_t st) {
+  constexpr int PPW = ENS_THREADS / G;
+  long long wgs = ((long long)a.n + PPW - 1) / PPW;
+  if (wgs > ENS_WG_MAX) wgs = ENS_WG_MAX;
+  hipLaunchKernelGGL(ensemble_kernel<G>, dim3((unsigned)wgs), dim3(ENS_THREADS), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble(const EnsArgs& a, hipStream_t st) {
+  if (a.K <= 1) return launch_g<1>(a, st);
+  if (a.K <= 2) return launch_g<2>(a, st);
+  if (a.K <= 4) return launch_g<4>(a, st);
+  if (a.K <= 8) return launch_g<8>(a, st);
+  if (a.K <= 16) return launch_g<16>(a, st);
+  if (a.K <= 32) return launch_g<32>(a, st);
+  return launch_g<64>(a, st);
+}
+
+}  // namespace
+}  // namespace cmlpl
+
+extern "C" int cmlpl_ensemble(const float* d_logits, int members, int64_t member_stride, const float* weights, int n, int K,
+                              int64_t* d_labels, float* d_probs, float* d_conf, float* d_entropy, int32_t* d_disagree,
+                              void* stream) {
+  if (members < 1 || members > cmlpl::ENS_MAX_MEMBERS || K < 1 || K > 64 || n < 1) return CMLPL_E_ARG;
+  if (!d_logits || !d_labels) return CMLPL_E_ARG;
+  if (members > 1 && member_stride < (int64_t)n * K) return CMLPL_E_ARG;          // the members' blocks must not overlap
+  if ((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_conf) |
+       reinterpret_cast<uintptr_t>(d_entropy) | reinterpret_cast<uintptr_t>(d_disagree)) & 3) return CMLPL_E_ARG;
+  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  cmlpl::EnsArgs a = {};
+  double sum = 0.0;
+  for (int m = 0; m < members; ++m) {
+    const double w = weights ? (double)weights[m] : 1.0;
+    if (!(w >= 0.0) || !std::isfinite(w)) return CMLPL_E_ARG;                    // (a NaN fails the comparison)
+    sum += w;
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) return CMLPL_E_ARG;
+  for (int m = 0; m < members; ++m) a.w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum);
+  a.logits = d_logits; a.member_stride = members > 1 ? (long long)member_stride : 0;
+  a.members = members; a.n = n; a.K = K;
+  a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
+  a.disagree = d_disagree;
+  const hipError_t e = cmlpl::launch_ensemble(a, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : (int)e;
+}

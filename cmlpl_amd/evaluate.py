@@ -57,25 +57,43 @@ class Evaluator:
         self.chunk = max(8, min(int(chunk), n))
         need = self.lib.cmlpl_eval_workspace_bytes(C.byref(self.cshape), 2, self.chunk)
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None     # None: windows go by patches
+        self.logits = self.ens_labels = self.cm_ens = None       # evaluate(ensemble=True) creates them at its first call
 
     @torch.no_grad()
-    def evaluate(self, nets) -> torch.Tensor:
+    def evaluate(self, nets, ensemble: bool = False) -> torch.Tensor:
         """confusion matrices int64 [nets, K, K] on the device (row = true class, column = predicted class) of the
         registered split under ``nets`` -- what ``cmlpl_amd.infer.infer_pixels`` takes: ``(TrainEngine, None)`` for both
         networks of an engine, one network, or a pair of modules.  A view of this object's buffer: the next call
-        overwrites it.  On the current stream, no synchronisation."""
+        overwrites it.  On the current stream, no synchronisation.
+        ``ensemble``: [nets + 1, K, K] -- the same matrices, then the one of the networks' equally weighted ensemble
+        (``cmlpl_ensemble`` over the logits of the same forward: the label of the averaged softmax, first maximum).  Its
+        buffers (the logits, the ensemble's labels, the matrices) are created at the first such call."""
         cs, nn, flat, pstride, packed, kstride, _ = _nets_buffers(nets)
         if (cs.C, cs.H, cs.W, cs.bands, cs.K) != tuple(getattr(self.cshape, k) for k in ("C", "H", "W", "bands", "K")):
             raise ValueError("the networks' shape is not the registered split's")
         labels = self.labels[:nn]
+        logits = None
+        if ensemble:
+            if self.cm_ens is None:
+                dev = self.cube.device
+                self.logits = torch.empty(2, self.n, cs.K, dtype=torch.float32, device=dev)
+                self.ens_labels = torch.empty(self.n, dtype=torch.int64, device=dev)
+                self.cm_ens = torch.zeros(3, cs.K, cs.K, dtype=torch.int64, device=dev)
+            logits = self.logits.view(-1)[:nn * self.n * cs.K].view(nn, self.n, cs.K)
         _infer_pixels_into(self.lib, cs, nn, flat, pstride, packed, kstride, self.cube, self.spectra, self.spec_rows,
-                           self.pix, labels, None, self.ws, self.chunk)
-        cm = self.cm[:nn]
+                           self.pix, labels, logits, self.ws, self.chunk)
+        cm = self.cm_ens[:nn + 1] if ensemble else self.cm[:nn]
         cm.zero_()
         self.ignored.zero_()
         st = C.c_void_p(torch.cuda.current_stream(self.cube.device).cuda_stream)
         _lib.check("cmlpl_confusion", self.lib.cmlpl_confusion(
             labels.data_ptr(), nn, self.truth.data_ptr(), self.n, cs.K, cm.data_ptr(), self.ignored.data_ptr(), st))
+        if ensemble:
+            _lib.check("cmlpl_ensemble", self.lib.cmlpl_ensemble(
+                logits.data_ptr(), nn, self.n * cs.K, None, self.n, cs.K, self.ens_labels.data_ptr(), None, None, None,
+                None, st))
+            _lib.check("cmlpl_confusion", self.lib.cmlpl_confusion(
+                self.ens_labels.data_ptr(), 1, self.truth.data_ptr(), self.n, cs.K, cm[nn].data_ptr(), None, st))
         return cm
 
     @staticmethod

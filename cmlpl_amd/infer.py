@@ -51,11 +51,12 @@ def infer_supported(shape) -> bool:
 
 @torch.no_grad()
 def infer_cube(net, cube: torch.Tensor, spectra: torch.Tensor, pixel0: int = 0, n: Optional[int] = None,
-               chunk: int = 65536, want_logits: bool = False):
+               chunk: int = 65536, want_logits: bool = False, out=None):
     """argmax labels (int64 cuda [n]) of pixels pixel0 .. pixel0 + n - 1 (row-major; default: the whole scene), and the
     logits [n, K] when asked for.  Asynchronous.  Window shapes the fused per-sample forward does not take (more than 256
     window pixels: the reference's 20 x 20) go through ``_infer_cube_by_patches``: same results, ``chunk`` pixels' windows
-    in HBM at a time."""
+    in HBM at a time.  ``out``: (labels, logits) buffers that exist -- contiguous int64 [n] and float32 [n, K] (or None)
+    -- are written instead of new tensors (cmlpl_amd.ensemble fills one buffer with several networks' logits)."""
     if not (cube.is_cuda and cube.dtype == torch.float32 and cube.is_contiguous() and cube.dim() == 3):
         raise ValueError("cube: need contiguous float32 cuda tensor [rows, cols, C]")
     rows, cols, Cc = cube.shape
@@ -70,8 +71,19 @@ def infer_cube(net, cube: torch.Tensor, spectra: torch.Tensor, pixel0: int = 0, 
         raise ValueError("pixel range outside the scene")
     lib = _lib.load()
     dev = cube.device
-    labels = torch.empty(n, dtype=torch.int64, device=dev)
-    logits = torch.empty(n, cs.K, dtype=torch.float32, device=dev) if want_logits else None
+    if out is None:
+        labels = torch.empty(n, dtype=torch.int64, device=dev)
+        logits = torch.empty(n, cs.K, dtype=torch.float32, device=dev) if want_logits else None
+    else:
+        labels, logits = out
+        ok = labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (n,)
+        if want_logits:
+            ok = ok and logits is not None and logits.is_cuda and logits.dtype == torch.float32 \
+                and logits.is_contiguous() and tuple(logits.shape) == (n, cs.K)
+        else:
+            logits = None
+        if not ok:
+            raise ValueError("out: need contiguous cuda (int64 [n], float32 [n, K]) buffers")
     chunk = max(8, min(int(chunk), n))
     need = lib.cmlpl_infer_workspace_bytes(C.byref(cs), chunk)
     if need == 0:                                           # not a window the fused per-sample forward takes

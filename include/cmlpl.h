@@ -557,6 +557,30 @@ int cmlpl_cps_loss_fwd_bwd(const cmlpl_shape* shape, int bt, int btu, const floa
  * applies its update (and behind every graph replay); cmlpl_amd.models.WeightEMA_BN calls it once per tensor. */
 int cmlpl_ema_update(const float* d_src, float* d_ema, int64_t count, double alpha, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- the ENSEMBLE of 1..4 networks' logits: averaged class
+ * probabilities, the label they give, its confidence, the entropy and the members' disagreement (the reference has no
+ * counterpart: it reports each network alone).
+ *
+ * cmlpl_ensemble: d_logits holds `members` (1..4) blocks [n][K] f32, member_stride floats apart (>= n K when members > 1;
+ *   ignored for one member).  Per pixel i < n:
+ *     p_m      = softmax(z_m[i]) in fp32, the maximum subtracted first -- torch.softmax's semantics: a member row that holds
+ *                a NaN or a +inf is NaN everywhere, -inf logits give probability 0
+ *     p        = sum_m w_m p_m, m ascending; w_m = weights[m] / sum(weights), formed in double and rounded to fp32 on the
+ *                host.  `weights` is a HOST array [members], read during the call; NULL = equal weights
+ *     label    = the FIRST maximum of p; a NaN counts as the maximum and the first NaN wins (torch.max's rule, as in
+ *                cmlpl_infer_cube)                                                        -> d_labels [n] int64
+ *     conf     = p[label]                                                                 -> d_conf [n] or NULL
+ *     entropy  = -sum_c p_c logf(p_c) with 0 log 0 = 0, NaN when p is NaN                 -> d_entropy [n] or NULL
+ *     disagree = the number of members whose own label (the same rule on p_m) is not label -> d_disagree [n] int32 or NULL
+ *     p itself                                                                            -> d_probs [n][K] or NULL
+ *   One launch: a group of G lanes per pixel (G = the smallest power of two >= K), shuffle butterflies of width G, no LDS,
+ *   no atomics, no workspace, no synchronisation, no other host call (it can be captured in a graph); the same bytes on
+ *   every run.  CMLPL_E_ARG before any launch: members outside 1..4, K outside 1..64, n < 1, a weight that is negative or
+ *   not finite, weights whose sum is not positive, a member_stride below n K with members > 1, a null d_logits / d_labels,
+ *   a misaligned pointer. */
+int cmlpl_ensemble(const float* d_logits, int members, int64_t member_stride, const float* weights, int n, int K,
+                   int64_t* d_labels, float* d_probs, float* d_conf, float* d_entropy, int32_t* d_disagree, void* stream);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the

@@ -9,7 +9,11 @@ directory's ``cube.npy`` + ``scene.json`` (``HSIDataSet(.., 'wholeset').cube_sou
 ``cmlpl_infer_cube`` through ``tools.hyper_tools.test_whole`` -- the end-of-run evaluation of ``train.py``
 (``train.evaluate_whole``), without a training engine.  ``--out`` receives the int64 label map [rows * cols]
 (``--net both``: [2][rows * cols]; ``--net ema0 | ema1 | ema_both``: the EMA teachers of a ``train.py --ema`` run); when the directory has ``test_array.npy`` / ``Y.npy`` the ``Result:`` / ``producerA`` /
-``AA`` lines of ``train.py`` are printed.  ``--synthetic SHAPE`` labels the seeded synthetic scene that
+``AA`` lines of ``train.py`` are printed.  ``--net ensemble`` labels the scene with Base and Base1 TOGETHER -- the first
+maximum of their averaged softmax (cmlpl_amd.ensemble; ``ensemble_all`` adds both EMA teachers) -- and prints the lines
+with the tag ``_ens``; ``--proba`` / ``--confidence`` / ``--entropy`` write the class probabilities float32
+[rows * cols, K], the probability of the label and the entropy float32 [rows * cols] -- of the ensemble, or of a single
+``--net`` (its own softmax: a one-member ensemble; its label map stays the argmax of its logits).  ``--synthetic SHAPE`` labels the seeded synthetic scene that
 ``train.py --synthetic`` evaluates on (datasets are not shipped)."""
 import argparse
 import os
@@ -19,10 +23,20 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import DATASETS, SYNTH, evaluate_whole
+from train import DATASETS, SYNTH, ensemble_whole, evaluate_whole
+
+ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
+
+
+def check_args(args):
+    """what the command line cannot mean, said before anything is loaded"""
+    if args.net in ('both', 'ema_both') and (args.proba or args.confidence or args.entropy):
+        raise SystemExit("--proba / --confidence / --entropy describe ONE prediction: --net %s writes two label maps "
+                         "(name one network, or --net ensemble for the two together)" % args.net)
 
 
 def main(args, device=None):
+    check_args(args)
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -45,32 +59,57 @@ def main(args, device=None):
             test_array = np.load(whole.root + 'test_array.npy')
             Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
     both = args.net in ('both', 'ema_both')
-    if args.net.startswith('ema'):
-        which = ['ema0', 'ema1'] if both else [args.net]
-        if "Teacher" not in ck or "Teacher1" not in ck:
-            raise SystemExit("--net %s: %s holds no EMA teacher (\"Teacher\" / \"Teacher1\"): it was written by a run "
-                             "without train.py --ema" % (args.net, args.ckpt))
-    else:
-        which = [0, 1] if both else [int(args.net)]
+    which = {'both': [0, 1], 'ema_both': ['ema0', 'ema1'], **ENSEMBLES}.get(args.net) or \
+        [args.net if args.net.startswith('ema') else int(args.net)]
+    if any(str(k).startswith('ema') for k in which) and ("Teacher" not in ck or "Teacher1" not in ck):
+        raise SystemExit("--net %s: %s holds no EMA teacher (\"Teacher\" / \"Teacher1\"): it was written by a run "
+                         "without train.py --ema" % (args.net, args.ckpt))
     keys = {0: "Base", 1: "Base1", 'ema0': "Teacher", 'ema1': "Teacher1"}
+    extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
+    common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
+    if args.net in ENSEMBLES:
+        ens = ensemble_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device, **common, **extras)
+        save_extras(args, ens)
+        if args.out:
+            np.save(args.out, ens["labels"])
+        return ens["labels"]
     preds = evaluate_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device,
                            synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"],
                            val_batch_size=args.val_batch_size, test_array=test_array, Y_test=Y_test)
     labels = np.stack([preds[k] for k in which]).astype(np.int64)
     labels = labels if both else labels[0]
+    if any(extras.values()):
+        # the network's own softmax: a one-member ensemble, silent (the Result: lines above are the argmax of its logits)
+        save_extras(args, ensemble_whole(shape, whole, [(which[0], ck[keys[which[0]]])], device, **dict(common, test_array=None),
+                                         **extras))
     if args.out:
         np.save(args.out, labels)
     return labels
+
+
+def save_extras(args, ens):
+    for path, key in ((args.proba, "probs"), (args.confidence, "conf"), (args.entropy, "entropy")):
+        if path:
+            np.save(path, ens[key])
 
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     parser.add_argument('--ckpt', required=True, help='a checkpoint of train.py --save_ckpt / --save_best')
     parser.add_argument('--dataID', type=int, default=1)
-    parser.add_argument('--net', choices=('0', '1', 'both', 'ema0', 'ema1', 'ema_both'), default='0',
+    parser.add_argument('--net', choices=('0', '1', 'both', 'ema0', 'ema1', 'ema_both', 'ensemble', 'ensemble_all'),
+                        default='0',
                         help="Base (0), Base1 (1) or both; ema0 / ema1 / ema_both: their EMA teachers (a checkpoint of "
-                             "train.py --ema)")
+                             "train.py --ema); ensemble: Base and Base1 together, one label map from their averaged "
+                             "softmax; ensemble_all: with both EMA teachers")
     parser.add_argument('--out', default=None, help='write the int64 label map as .npy ([rows*cols]; both: [2][rows*cols])')
+    parser.add_argument('--proba', default=None, metavar='FILE',
+                        help='write the class probabilities float32 [rows*cols, K] as .npy (the ensemble\'s, or one '
+                             'network\'s own softmax; not with both / ema_both)')
+    parser.add_argument('--confidence', default=None, metavar='FILE',
+                        help='write the probability of the predicted class float32 [rows*cols] as .npy')
+    parser.add_argument('--entropy', default=None, metavar='FILE',
+                        help='write the entropy of the class probabilities float32 [rows*cols] as .npy')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

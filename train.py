@@ -28,6 +28,10 @@ Differences from the reference that are deliberate, MI355X-first choices:
     ``--teacher_alpha``) is kept on the device, updated behind every step (one launch; also behind a graph replay), scored
     by ``--eval_every`` on two more lines (``validation_ema`` / ``validation_ema1``), saved with every checkpoint
     (``"Teacher"`` / ``"Teacher1"``) and evaluated after the run.  One GPU.  Without it ``--teacher_alpha`` is ignored.
+  * ``--ensemble``: the two networks are also scored TOGETHER -- the label of their averaged softmax
+    (cmlpl_amd.ensemble, one launch behind the eval forward): a third ``validation_ens`` line per ``--eval_every``
+    evaluation, a curve of its own in ``--save_eval`` and the checkpoints, a third ``Result:`` block (``OA_ens``) after
+    the run.  It reads the networks and changes nothing they compute: ``loss_hist`` is what it is without the flag.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -112,12 +116,65 @@ def run_ema(args):
     return bool(getattr(args, "ema", False))
 
 
+def saved_args(args):
+    """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble) is left
+    out at its default, so a file written without it is byte for byte what it was before the flag existed"""
+    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False}
+    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
+
+
 def run_differences(saved, mine):
     keys = list(mine) + [k for k in ("ema", "teacher_alpha") if k in saved and k not in mine]     # --ema: both ways
     return ["%s: file %r, here %r" % (k, saved.get(k), mine.get(k)) for k in keys if saved.get(k) != mine.get(k)]
 
 
-NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1'}      # evaluate_whole: a network, or a network's EMA teacher
+NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
+            'ens': '_ens'}                                         # ensemble_whole: several of them together
+
+
+def run_ensemble(args):
+    return bool(getattr(args, "ensemble", False))
+
+
+def print_result(tag, pred, test_array, Y_test):
+    """the ``Result:`` / ``producerA`` / ``AA`` lines (train.py:297-306) of one label map; returns its OA"""
+    OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
+    print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
+    print('producerA%s:' % tag, producerA * 100)
+    print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
+    return OA
+
+
+def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
+                   resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+    """Whole-image ENSEMBLE of ``nets`` = [(key, state_dict)] (1..4 networks, ``evaluate_whole``'s list): the label of their
+    averaged softmax for every scene pixel, and its probabilities / confidence / entropy when asked for
+    (cmlpl_amd.ensemble.ensemble_cube: every member's eval forward from the resident cube, one launch behind each chunk).
+    Returns {'labels': int64 [pixels], 'probs': float32 [pixels, K], 'conf', 'entropy': float32 [pixels]} (numpy; what was
+    not asked for is absent) and prints the ``Result:`` lines with the tag ``_ens`` when the test pixels are given.  It
+    needs the scene as its cube: there is no loader fall-back."""
+    from cmlpl_amd.ensemble import ensemble_cube
+    from cmlpl_amd.infer import infer_supported
+    source = None
+    if infer_supported(NetShape(*shape)):
+        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
+            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
+    if source is None:
+        raise SystemExit("the ensemble needs the scene cube (cube.npy + scene.json in the dataset directory, "
+                         "sample_generation.py) and a square window")
+    models = []
+    for _, sd in nets:
+        model = BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
+                         window=shape[1]).to(device)
+        model.load_state_dict(sd)
+        models.append(model.eval())
+    t1 = time.time()
+    res = ensemble_cube(models, source.cube, source.spectra, weights=weights, probs=probs, conf=conf, entropy=entropy)
+    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
+    print('ensemble inference time == %.3f s (%d networks)' % (time.time() - t1, len(models)))
+    if test_array is not None:
+        print_result(NET_TAGS['ens'], out["labels"], test_array, Y_test)
+    return out
 
 
 def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
@@ -161,11 +218,8 @@ def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
         print('inference time == %.3f s' % (time.time() - t1))
         if test_array is None:
             continue
-        OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
         tag = NET_TAGS[net]
-        print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
-        print('producerA%s:' % tag, producerA * 100)
-        print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
+        OA = print_result(tag, pred, test_array, Y_test)
         if last_eval is not None and net in (0, 1):
             # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
             same = last_eval[net][0] == OA
@@ -272,6 +326,8 @@ def main(args, make_engine=None, device=None):
     evaluator, eval_log, eval_cms = None, [], []          # --eval_every: (epoch, [net][OA, AA, Kappa]) and the matrices
     ema = run_ema(args)
     eval_log_ema, eval_cms_ema = [], []                   # --ema: the same two of the teachers, a curve of their own
+    ens = run_ensemble(args)
+    eval_log_ens, eval_cms_ens = [], []                   # --ensemble: (epoch, [OA, AA, Kappa]) and the matrix of the pair
     if args.eval_every > 0 and rank == 0:
         # the test split registered once: its pixels, spectra and labels beside the resident cube (rank 0 evaluates, as
         # after the last epoch; its own generators: no draw of the training streams is consumed)
@@ -307,6 +363,10 @@ def main(args, make_engine=None, device=None):
                 eval_log_ema = [(int(e), [[float(v) for v in net] for net in row])
                                 for e, row in zip(ex["eval_epochs_ema"], ex["eval_curve_ema"].tolist())]
                 eval_cms_ema = [cm for cm in ex["eval_cms_ema"].numpy()]
+            if ens and "eval_curve_ens" in ex:
+                eval_log_ens = [(int(e), [float(v) for v in row])
+                                for e, row in zip(ex["eval_epochs_ens"], ex["eval_curve_ens"].tolist())]
+                eval_cms_ens = [cm for cm in ex["eval_cms_ens"].numpy()]
     index_i = start_epoch * num_batches - 1
     best_oa, best_state, best_extra = None, None, None               # --save_best
     if eval_log:
@@ -321,11 +381,16 @@ def main(args, make_engine=None, device=None):
                         eval_curve_ema=torch.tensor([r for _, r in eval_log_ema], dtype=torch.float64).reshape(len(eval_log_ema), 2, 3),
                         eval_cms_ema=torch.from_numpy(np.stack(eval_cms_ema)) if eval_cms_ema else
                         torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64))
+        if ens:
+            more.update(eval_epochs_ens=[e for e, _ in eval_log_ens],
+                        eval_curve_ens=torch.tensor([r for _, r in eval_log_ens], dtype=torch.float64).reshape(len(eval_log_ens), 3),
+                        eval_cms_ens=torch.from_numpy(np.stack(eval_cms_ens)) if eval_cms_ens else
+                        torch.zeros(0, num_classes, num_classes, dtype=torch.int64))
         return dict(epoch=epochs_done, num_batches=num_batches, loss_hist=torch.from_numpy(loss_hist[:done].copy()),
                     eval_epochs=[e for e, _ in eval_log],
                     eval_curve=torch.tensor([r for _, r in eval_log], dtype=torch.float64).reshape(len(eval_log), 2, 3),
                     eval_cms=torch.from_numpy(np.stack(eval_cms)) if eval_cms else torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64),
-                    gen_state=gen.get_state(), args={k: v for k, v in vars(args).items() if not (k == 'method' and v == 'cmlpl') and not (k == 'ema' and not v)},
+                    gen_state=gen.get_state(), args=saved_args(args),
                     run=run_record(args, hp, shape, from_scene), world=world, **more)
     pending = []                      # loss_hist rows of the steps run since the last read-back of the device ring
 
@@ -389,7 +454,7 @@ def main(args, make_engine=None, device=None):
         read_back()                   # rows of the epoch's tail (num_batches % print_per_batches steps)
         if evaluator is not None and (epoch + 1) % args.eval_every == 0:
             # between two steps (or replays), on their stream: launches + one read-back of nets x K x K integers
-            cms = evaluator.evaluate((eng, None)).cpu().numpy()
+            cms = (evaluator.evaluate((eng, None), ensemble=True) if ens else evaluator.evaluate((eng, None))).cpu().numpy()
             row = []
             for net in range(2):
                 OA, Kappa, _, AA = evaluator.metrics(cms[net])
@@ -397,7 +462,14 @@ def main(args, make_engine=None, device=None):
                 print('Epoch %d/%d: validation%s OA = %.2f AA = %.2f Kappa = %.2f' %
                       (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
             eval_log.append((epoch + 1, row))
-            eval_cms.append(cms)
+            eval_cms.append(cms[:2])
+            if ens:
+                # the pair together: the third matrix of the same call (the averaged softmax's label, counted there)
+                OA, Kappa, _, AA = evaluator.metrics(cms[2])
+                print('Epoch %d/%d: validation_ens OA = %.2f AA = %.2f Kappa = %.2f' %
+                      (epoch + 1, args.num_epochs, OA * 100, AA * 100, Kappa * 100))
+                eval_log_ens.append((epoch + 1, (OA, AA, Kappa)))
+                eval_cms_ens.append(cms[2])
             if ema:
                 # the teachers: their packed weights are rebuilt here, when they are read, not behind every step
                 cms_t = evaluator.evaluate((eng.teacher, None)).cpu().numpy()
@@ -444,11 +516,18 @@ def main(args, make_engine=None, device=None):
         for net in range(2):
             best = int(np.argmax(curve[:, net, 0]))                   # (the first of equal bests)
             print('best validation%s: epoch %d OA = %.2f' % ('' if net == 0 else '1', epochs[best], curve[best, net, 0] * 100))
+        if ens and eval_log_ens:
+            curve_ens = np.array([r for _, r in eval_log_ens])        # [evaluations][OA, AA, Kappa]
+            epochs_ens = np.array([e for e, _ in eval_log_ens])
+            best = int(np.argmax(curve_ens[:, 0]))
+            print('best validation_ens: epoch %d OA = %.2f' % (epochs_ens[best], curve_ens[best, 0] * 100))
         if args.save_eval:
             more = {}
             if ema and eval_log_ema:
                 more = dict(curve_ema=np.array([r for _, r in eval_log_ema]), cm_ema=np.stack(eval_cms_ema),
                             epochs_ema=np.array([e for e, _ in eval_log_ema]))
+            if ens and eval_log_ens:
+                more.update(curve_ens=curve_ens, cm_ens=np.stack(eval_cms_ens), epochs_ens=epochs_ens)
             np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms), **more)
     if rank == 0 and not args.no_eval:
         nets = [(net, eng.state_dict(net)) for net in range(2)]
@@ -458,6 +537,9 @@ def main(args, make_engine=None, device=None):
                        dataID=args.dataID, dropout=args.dropout, val_batch_size=args.val_batch_size,
                        test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"),
                        last_eval=eval_log[-1][1] if eval_log and eval_log[-1][0] == args.num_epochs else None)
+        if ens:
+            ensemble_whole(shape, whole, nets[:2], device, synthetic=args.synthetic, dataID=args.dataID,
+                           dropout=args.dropout, test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"))
     if world > 1 and make_engine is None:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -497,6 +579,10 @@ def build_parser():
                         help="keep an exponential moving average of both networks' weights (the reference's WeightEMA_BN, "
                              "coefficient --teacher_alpha), updated on the device behind every step; --eval_every scores it "
                              "too, checkpoints carry it as \"Teacher\" / \"Teacher1\" (one GPU)")
+    parser.add_argument('--ensemble', action='store_true',
+                        help="score the two networks TOGETHER as well: the label of their averaged softmax, on the device -- a "
+                             "third validation_ens line per --eval_every evaluation (curve_ens in --save_eval) and a third "
+                             "Result: block (OA_ens) after the run; --save_best keeps its criterion, network 0's OA")
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

@@ -38,7 +38,7 @@ EXPORTS = (
     "cmlpl_eval_workspace_bytes", "cmlpl_infer_pixels", "cmlpl_confusion",      # added after ABI 6, no bump (include/cmlpl.h)
     "cmlpl_packed_flag_offset",
     "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
-    "cmlpl_debug_conv3_plan", "cmlpl_debug_route",                               # added after ABI 6, no bump: test aids
+    "cmlpl_debug_conv3_plan", "cmlpl_debug_route", "cmlpl_debug_wgrad3_plan",    # added after ABI 6, no bump: test aids
     "cmlpl_ema_update",                                                          # added after ABI 6, no bump: the EMA teacher
     "cmlpl_ensemble",                                                            # added after ABI 6, no bump: ensemble prediction
 )
@@ -276,6 +276,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_debug_two_piece.argtypes = [SP, i32, i32]
     lib.cmlpl_debug_conv3_plan.argtypes = [SP, i32, i32, i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_route.argtypes = [SP, i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_wgrad3_plan.argtypes = [SP, i32, i32, C.POINTER(i32)]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]

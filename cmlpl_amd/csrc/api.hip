@@ -1351,4 +1351,23 @@ int cmlpl_debug_route(const cmlpl_shape* shape, int nets, int n, int* out) {
   return 0;
 }
 
+int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out) {
+  Dims d;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  if (nets < 1 || nets > 2 || n < 1 || !out) return CMLPL_E_ARG;
+  NetRoute r;
+  if (!make_route(d, nets, n, &r)) return CMLPL_E_SHAPE;
+  Wgrad3Plan p1, p2;
+  bool pair = false;
+  if (!plan_wgrad3_both(nets, n, d.H, d.W, d.H2, d.W2, true, &p1, &p2, &pair)) return CMLPL_E_SHAPE;
+  // (the list exists in the pair launch only, and only in a step whose launches leave the maxima table)
+  const size_t lbytes = pair ? wgrad3_pair_list_bytes(p1, p2, n, d.H, d.H2, r.stats) : 0;
+  int* o = out;
+  for (const Wgrad3Plan* p : {&p1, &p2}) {
+    *o++ = p->rsplit; *o++ = p->b3; *o++ = p->U; *o++ = p->UPG; *o++ = p->G; *o++ = (int)(p->lds + lbytes); *o++ = p->cspl;
+  }
+  *o++ = pair ? 1 : 0; *o++ = lbytes > 0 ? 1 : 0; *o++ = device_cus();
+  return 0;
+}
+
 }  // extern "C"

@@ -164,6 +164,7 @@ struct Wgrad3Plan { int RU, U, G, cspl, rsplit, UPG, b3; size_t lds; };   // rsp
 bool plan_wgrad3(int nets, int n, int H, int W, Wgrad3Plan* p, int role = 0);   // role: 0 alone, 1 / 2 first / second map of a pair launch
 bool plan_wgrad3_both(int nets, int n, int H1, int W1, int H2, int W2, bool want_pair, Wgrad3Plan* p1, Wgrad3Plan* p2,
                       bool* pair);
+size_t wgrad3_pair_list_bytes(const Wgrad3Plan& p1, const Wgrad3Plan& p2, int n, int H1, int H2, bool have_stats);   // LDS bytes of a pair launch's zero-skip sample list (0: not placed)
 hipError_t launch_wgrad3(int nets, int n, int H, int W, const float* in, const float* dpool, const uint8_t* mask,
                          float* part, hipStream_t st);
 hipError_t launch_wgrad3_pair(int nets, int n, int H1, int W1, const float* in1, const float* dpool1,

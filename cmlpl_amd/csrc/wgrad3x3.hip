@@ -1069,6 +1069,16 @@ bool plan_wgrad3_both(int nets, int n, int H1, int W1, int H2, int W2, bool want
   return true;
 }
 
+// Room for the list of samples with a non-zero gradient operand behind the stage buffers of a pair launch: zero samples
+// are skipped (CMLPL_ZERO_SKIP=0: never).  The list's bytes, or 0 when it is not placed (no maxima table this step, a
+// pooled map of one row, no room in LDS).
+size_t wgrad3_pair_list_bytes(const Wgrad3Plan& p1, const Wgrad3Plan& p2, int n, int H1, int H2, bool have_stats) {
+  const size_t lds = p1.lds > p2.lds ? p1.lds : p2.lds;
+  const size_t lbytes = ((size_t)2 * n + 15) & ~(size_t)15;
+  const bool placed = have_stats && switches().zero_skip != 0 && n <= 65535 && H1 / 2 >= 2 && H2 / 2 >= 2 && lds + lbytes <= LDS_MAX;
+  return placed ? lbytes : 0;
+}
+
 // both 3x3 weight gradients of a backward pass: one launch where a pair kernel exists, else two
 hipError_t launch_wgrad3_pair(int nets, int n, int H1, int W1, const float* in1, const float* dpool1,
                               const uint8_t* mask1, float* part1, int H2, int W2, const float* in2,
@@ -1087,10 +1097,8 @@ hipError_t launch_wgrad3_pair(int nets, int n, int H1, int W1, const float* in1,
       a.h2flag = b.h2flag = h2flag; a.h2flag_ns = b.h2flag_ns = h2flag_ns;
     }
     size_t lds = p1.lds > p2.lds ? p1.lds : p2.lds;
-    // room for the list of samples with a non-zero gradient operand behind the stage buffers: zero samples are skipped
-    // (CMLPL_ZERO_SKIP=0: never)
-    const size_t lbytes = ((size_t)2 * n + 15) & ~(size_t)15;
-    if (hstat != nullptr && switches().zero_skip != 0 && n <= 65535 && H1 / 2 >= 2 && H2 / 2 >= 2 && lds + lbytes <= LDS_MAX) {
+    const size_t lbytes = wgrad3_pair_list_bytes(p1, p2, n, H1, H2, hstat != nullptr);
+    if (lbytes > 0) {
       a.slist_off = b.slist_off = (int)lds;
       a.mg_ups = (uint32_t)((0x100000000ULL + (uint32_t)(H1 / 2) - 1) / (uint32_t)(H1 / 2));
       b.mg_ups = (uint32_t)((0x100000000ULL + (uint32_t)(H2 / 2) - 1) / (uint32_t)(H2 / 2));

@@ -742,6 +742,24 @@ int cmlpl_debug_conv3_plan(const cmlpl_shape* shape, int nets, int n, int map, i
 #define CMLPL_ROUTE_INTS 30
 int cmlpl_debug_route(const cmlpl_shape* shape, int nets, int n, int* out);
 
+/* Added after ABI 6, no bump (nothing existing moves).  Test aid: what the planner of the two 3x3 weight gradients
+ * (plan_wgrad3_both, asked as a backward pass asks it) decides for `nets` networks x n rows under the current switches.
+ * out[CMLPL_WGRAD3_PLAN_INTS]:
+ *   [0..6], [7..13]  the window's map (conv1), then its pooled map (conv2):
+ *                      [0] column pairs per row (the row-split kernels' template parameter CPR; 0 = the general kernel)
+ *                      [1] 1 = the split-bf16 kernel (0 with [0] > 0: the f32-input row-split kernel)
+ *                      [2] U: pooled rows per stage (general kernel: units per pass)
+ *                      [3] UPG: pooled rows per workgroup, a multiple of U (0 for the general kernel)
+ *                      [4] G: workgroups per network (and per kernel row in the row-split kernels)
+ *                      [5] dynamic LDS bytes of the map's plan, plus the sample list's bytes when [15] is set
+ *                      [6] 2 = the general kernel with its output channels split over two workgroups, else 1
+ *   [14] 1 = both maps in ONE launch (the pair kernel)
+ *   [15] 1 = the pair launch would place the list of samples with a non-zero gradient image (zero samples are skipped)
+ *   [16] the compute-unit count the plans were made for
+ * Host arithmetic only, nothing is launched.  CMLPL_E_ARG / CMLPL_E_SHAPE. */
+#define CMLPL_WGRAD3_PLAN_INTS 17
+int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out);
+
 #ifdef __cplusplus
 }
 #endif

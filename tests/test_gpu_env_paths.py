@@ -173,6 +173,32 @@ def test_separate_weight_gradient_launches_pass_backward_parity():
     _run(J_WG_SEP)
 
 
+_WGRAD = "tests/test_gpu_wgrad_envelope.py"
+J_WGT_GEN = _job("wgrad", "wgrad-table-general", {"CMLPL_WGRAD3_R": "0"}, [_WGRAD, "-k", "in_their_regime"])
+J_WGT_SEP = _job("wgrad", "wgrad-table-separate", {"CMLPL_WGRAD3_PAIR": "0"}, [_WGRAD, "-k", "in_their_regime"])
+J_WGT_F32 = _job("wgrad", "wgrad-table-f32", {"CMLPL_WGRAD3_B3": "0"}, [_WGRAD, "-k", "in_their_regime and (cpr2_ or cpr5_)"])
+
+
+def test_weight_gradient_table_on_the_general_kernel():
+    """CMLPL_WGRAD3_R=0: wgrad3_kernel<1> on every case of the weight-gradient regime table (its own group: one child
+    process apart from the older convolution jobs), against the fp64 oracle; the cases assert the plan they ran under
+    (the general kernel for both maps, two launches)"""
+    _run(J_WGT_GEN)
+
+
+def test_weight_gradient_table_with_separate_launches():
+    """CMLPL_WGRAD3_PAIR=0: wgrad3b_kernel<CPR> alone for CPR 4 .. 10 (a window of 8 .. 21 columns takes the pair launch
+    under the default switches), still in several stages per workgroup"""
+    _run(J_WGT_SEP)
+
+
+def test_weight_gradient_table_on_the_f32_row_split_kernel():
+    """CMLPL_WGRAD3_B3=0 on the cases whose first map has CPR 2 or 5: wgrad3r_kernel<2 | 5> with its own carried (sample,
+    row) advance, in two stages or more per workgroup (asserted from the plan: UPG / U >= 2), the other map on the general
+    kernel"""
+    _run(J_WGT_F32)
+
+
 J_UNF0 = _job("conv", "conv0-unfused", {"CMLPL_FUSE_CONV0": "0"}, ["tests/test_gpu_ops.py", "-k", "forward_backward and B2"])
 
 

@@ -16,8 +16,9 @@ SHAPES = {
     "B2": O.NetShape(103, 11, 11, 103, 9),      # BASELINE configs[1]
     "B4": O.NetShape(200, 11, 11, 200, 16),
     "B5": O.NetShape(48, 15, 15, 48, 20),
-    # other window sizes: every column-pair count of the row-split weight-gradient kernel between 2 and 11,
-    # even and odd maps, tiny and ragged channel counts
+    # other window sizes: column-pair counts 4 .. 10 of the row-split weight-gradient kernel for the window and 2 .. 5 for
+    # its pooled map, one stage per workgroup (CPR 1, 3 and 11, several stages, and the windows of more than 23 columns
+    # that take the general kernel: tests/wgrad_cases.py), even and odd maps, tiny and ragged channel counts
     "W8": O.NetShape(8, 8, 8, 12, 5),
     "W9": O.NetShape(33, 9, 9, 7, 4),
     "W12": O.NetShape(5, 12, 12, 9, 3),

@@ -5,6 +5,7 @@ Public surface:
   TrainEngine .................. the fused training step (train.py:150-278 of the reference)
   BaseNet2 ..................... drop-in nn.Module (tools/models.py:97-152 of the reference)
   ensemble_logits / _cube / _pixels ... averaged probabilities, label, confidence, entropy of 1..4 networks
+  TTA, tta_cube / tta_pixels, views_of ... the same from several noisy views per pixel (test-time augmentation)
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in ("ensemble_logits", "ensemble_cube", "ensemble_pixels", "EnsembleResult"):
         from . import ensemble
         return getattr(ensemble, name)
+    if name in ("TTA", "tta_cube", "tta_pixels", "views_of"):
+        from . import tta
+        return getattr(tta, name)
     raise AttributeError(name)

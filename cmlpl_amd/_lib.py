@@ -41,6 +41,8 @@ EXPORTS = (
     "cmlpl_debug_conv3_plan", "cmlpl_debug_route", "cmlpl_debug_wgrad3_plan",    # added after ABI 6, no bump: test aids
     "cmlpl_ema_update",                                                          # added after ABI 6, no bump: the EMA teacher
     "cmlpl_ensemble",                                                            # added after ABI 6, no bump: ensemble prediction
+    "cmlpl_infer_tta_workspace_bytes", "cmlpl_infer_cube_tta", "cmlpl_eval_tta_workspace_bytes",     # added after ABI 6, no bump:
+    "cmlpl_infer_pixels_tta", "cmlpl_tta_patches", "cmlpl_ensemble_views",                           # test-time augmentation
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
@@ -247,6 +249,16 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_cps_loss_fwd_bwd.argtypes = [SP, i32, i32, vp, vp, HP, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_ema_update.argtypes = [vp, vp, i64, C.c_double, vp]
     lib.cmlpl_ensemble.argtypes = [vp, i32, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
+    u32 = C.c_uint32
+    lib.cmlpl_infer_tta_workspace_bytes.argtypes = [SP, i32]
+    lib.cmlpl_infer_tta_workspace_bytes.restype = sz
+    lib.cmlpl_infer_cube_tta.argtypes = [vp, vp, vp, vp, i32, i32, vp, i64, i32, vp, vp, vp, sz, vp, f32, u64, u32]
+    lib.cmlpl_eval_tta_workspace_bytes.argtypes = [SP, i32, i32]
+    lib.cmlpl_eval_tta_workspace_bytes.restype = sz
+    lib.cmlpl_infer_pixels_tta.argtypes = [SP, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp,
+                                           f32, u64, u32]
+    lib.cmlpl_tta_patches.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, u64, u32, vp]
+    lib.cmlpl_ensemble_views.argtypes = [vp, i32, i32, i64, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]
@@ -285,7 +297,8 @@ def load(path: str = LIB_PATH):
     for s in EXPORTS[1:]:
         if hasattr(lib, s) and s not in ("cmlpl_workspace_bytes", "cmlpl_loss_workspace_bytes", "cmlpl_ntxent_workspace_bytes",
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
-                     "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes"):
+                     "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes",
+                     "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

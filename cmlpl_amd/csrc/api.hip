@@ -1142,6 +1142,113 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
                                 d_params + L.param_off[3], t, (long long*)d_labels, st, &nn));
 }
 
+// ---- test-time augmentation (include/cmlpl.h, "THE DEFINITION OF A VIEW"): the two entry points above on a noisy view.
+// Workspace: what the clean call takes (y), then the view's spectra rows [n][bands].
+static bool view_args_ok(float sigma) { return sigma >= 0.f && sigma <= 3.0e38f; }   // (a NaN fails both)
+
+size_t cmlpl_infer_tta_workspace_bytes(const cmlpl_shape* shape, int n) {
+  const size_t y = cmlpl_infer_workspace_bytes(shape, n);
+  return y == 0 ? 0 : y + up256((size_t)n * shape->bands * 4);
+}
+
+int cmlpl_infer_cube_tta(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
+                         int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
+                         float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, float sigma,
+                         uint64_t seed, uint32_t view) {
+  Dims d;
+  cmlpl_layout_t L;
+  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
+  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_labels || !d_workspace || rows < 1 || cols < 1 || n < 1 ||
+      pixel0 < 0 || pixel0 + n > (int64_t)rows * cols || !view_args_ok(sigma))
+    return CMLPL_E_ARG;
+  Conv3Variant v;
+  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
+  if (cmlpl_infer_tta_workspace_bytes(shape, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
+  if (sigma == 0.f)      // the clean forward, its launches and its bytes
+    return cmlpl_infer_cube(shape, d_params, d_packed, d_cube, rows, cols, d_spectra, pixel0, n, d_labels, d_logits,
+                            d_workspace, workspace_bytes, stream);
+  if ((int64_t)rows * cols * d.C >= (1LL << 31) || d.W / 2 > rows || d.W / 2 > cols) return CMLPL_E_ARG;   // (what the launcher refuses)
+  hipStream_t st = (hipStream_t)stream;
+  float* y = (float*)d_workspace;
+  float* sn = (float*)((char*)d_workspace + cmlpl_infer_workspace_bytes(shape, n));
+  const ViewKey key = {sigma, seed, view};
+  int rc;
+  if ((rc = chk(launch_tta_spectra(d_spectra + (long long)pixel0 * d.bands, nullptr, nullptr, pixel0, (long long)rows * cols, n,
+                                   d.bands, sn, key, st)))) return rc;
+  if ((rc = chk(launch_spe_fwd(1, n, d.bands, sn, d_params + L.param_off[6], d_params + L.param_off[7], L.param_total, y,
+                               st)))) return rc;
+  FwdTail t;
+  memset(&t, 0, sizeof(t));
+  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
+  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
+  t.y = y; t.logits = d_logits; t.K = d.K;
+  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
+                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
+                                d_params + L.param_off[3], t, (long long*)d_labels, st, nullptr, &key));
+}
+
+size_t cmlpl_eval_tta_workspace_bytes(const cmlpl_shape* shape, int nets, int n) {
+  const size_t y = cmlpl_eval_workspace_bytes(shape, nets, n);
+  return y == 0 ? 0 : y + up256((size_t)n * shape->bands * 4);
+}
+
+int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                           const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                           const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                           int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
+                           float sigma, uint64_t seed, uint32_t view) {
+  Dims d;
+  cmlpl_layout_t L;
+  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
+  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_pix || !d_labels || !d_workspace || n < 1 || nets < 1 ||
+      nets > 2 || rows < 1 || cols < 1 || rows < d.H / 2 || cols < d.W / 2 ||
+      (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)) || !view_args_ok(sigma))
+    return CMLPL_E_ARG;
+  Conv3Variant v;
+  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
+  if ((int64_t)rows * cols * d.C >= (1LL << 31)) return CMLPL_E_ARG;          // (the gather's 32-bit offsets)
+  if (cmlpl_eval_tta_workspace_bytes(shape, nets, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
+  if (sigma == 0.f)
+    return cmlpl_infer_pixels(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra,
+                              d_spec_row, d_pix, n, d_labels, d_logits, d_workspace, workspace_bytes, stream);
+  hipStream_t st = (hipStream_t)stream;
+  float* y = (float*)d_workspace;
+  float* sn = (float*)((char*)d_workspace + cmlpl_eval_workspace_bytes(shape, nets, n));
+  const ViewKey key = {sigma, seed, view};
+  int rc;
+  // every network scores the same view: one set of rows, read by both (network stride 0)
+  if ((rc = chk(launch_tta_spectra(d_spectra, (const long long*)d_spec_row, (const long long*)d_pix, 0,
+                                   (long long)rows * cols, n, d.bands, sn, key, st)))) return rc;
+  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, sn, d_params + L.param_off[6], d_params + L.param_off[7], param_stride, y,
+                               st, nullptr, 0)))) return rc;
+  FwdTail t;
+  memset(&t, 0, sizeof(t));
+  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
+  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
+  t.y = y; t.logits = d_logits; t.K = d.K;
+  const InferNets nn = {nets, (long long)param_stride, (long long)packed_stride, (const long long*)d_pix};
+  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
+                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
+                                d_params + L.param_off[3], t, (long long*)d_labels, st, &nn, &key));
+}
+
+int cmlpl_tta_patches(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
+                      float* d_out, const float* d_spectra, const int64_t* d_spec_row, int bands, float* d_spectra_out,
+                      float sigma, uint64_t seed, uint32_t view, void* stream) {
+  if (!d_pixel_idx || (!d_out && !d_spectra_out) || rows < 1 || cols < 1 || n < 1 || !view_args_ok(sigma)) return CMLPL_E_ARG;
+  if (d_out && (!d_cube || C < 1 || w < 1)) return CMLPL_E_ARG;
+  if (d_spectra_out && (!d_spectra || bands < 1)) return CMLPL_E_ARG;
+  if (d_out && (w / 2 > rows || w / 2 > cols || tta_patches_lds(C, w) > LDS_MAX)) return CMLPL_E_SHAPE;
+  const ViewKey key = {sigma, seed, view};
+  int rc;
+  if (d_out && (rc = chk(launch_tta_patches(d_cube, rows, cols, C, w, (const long long*)d_pixel_idx, n, d_out, key,
+                                            (hipStream_t)stream)))) return rc;
+  if (d_spectra_out && (rc = chk(launch_tta_spectra(d_spectra, (const long long*)d_spec_row, (const long long*)d_pixel_idx, 0,
+                                                    (long long)rows * cols, n, bands, d_spectra_out, key,
+                                                    (hipStream_t)stream)))) return rc;
+  return 0;
+}
+
 size_t cmlpl_ntxent_workspace_bytes(int B, int D) { return (B < 1 || D < 1) ? 0 : ntxent_ws_floats(B, D) * 4; }
 
 int cmlpl_ntxent_fwd_bwd(const float* d_emb_i, const float* d_emb_j, int B, int D, float temperature, float* d_loss,

@@ -168,6 +168,9 @@ __device__ __forceinline__ float4 philox_uniform4(uint64_t seed, uint64_t step, 
 constexpr uint32_t STREAM_NOISE_XP = 0x100;   // + net
 constexpr uint32_t STREAM_NOISE_X = 0x200;    // + net
 constexpr uint32_t STREAM_DROPOUT = 0x300;    // + net
+// the views of test-time augmentation (include/cmlpl.h, "views"): the same for every network, disjoint from the training streams
+constexpr uint32_t STREAM_TTA_XP = CMLPL_STREAM_TTA_XP;   // 0x400: windows
+constexpr uint32_t STREAM_TTA_X = CMLPL_STREAM_TTA_X;     // 0x500: spectra
 
 // Counter of the Philox block that carries the noise of elements 4g .. 4g+3 of one sample's patch (or spectrum):
 // (GLOBAL sample index, group) -- the same in the augmentation kernel, the fused forward and the fused data

@@ -937,11 +937,13 @@ struct Conv3Ctx {
 
 // NW = waves of the workgroup: 4 (every MODE), or 8 for the per-sample kernels (MODE >= 2) when one workgroup has a CU
 // to itself (see ks_unit); NT = its threads, TPW = M tiles per wave in the tap loop.
-template <int MODE, int NW = 4, int TPW = 8 / NW, int CUBE = 0 /* 1: pixels pix0 + s, 2: pixels pix[s] */, bool H2X = false>
+template <int MODE, int NW = 4, int TPW = 8 / NW, int CUBE = 0 /* 1: pixels pix0 + s, 2: pixels pix[s] */, bool H2X = false,
+          bool TTA = false /* CUBE: the window is view xs.step of its scene pixel under (xs.seed, xs.sigma), include/cmlpl.h */>
 __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int lut_entries, Conv3Ctx& c,
                                             const float* dp_lds = nullptr, const uint32_t* mpre = nullptr) {
   constexpr int NT = 64 * NW;
   static_assert(!CUBE || MODE == 2, "the cube source feeds the fused forward");
+  static_assert(!TTA || CUBE, "the views of test-time augmentation are gathered from the cube");
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int net, s0;
@@ -1003,8 +1005,9 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
     // once (not once per output-channel tile, as with wave = (channel tile, pixel half))
     const int nfl = C * HW, nf4 = CUBE ? (1 << 30) : (nfl >> 2), rem = CUBE ? 0 : (nfl & 3);
     const float* xrow = CUBE ? a.cube : xsrc_row(a.xs, net, s0, nfl);
-    const float sigma = CUBE ? 0.f : a.xs.sigma;
-    const float* nzrow = (sigma != 0.f) ? xsrc_noise_row(a.xs, net, s0, nfl) : nullptr;
+    const float sigma = (CUBE && !TTA) ? 0.f : a.xs.sigma;
+    const float* nzrow = (!TTA && sigma != 0.f) ? xsrc_noise_row(a.xs, net, s0, nfl) : nullptr;
+    uint64_t vpix = 0;                                    // TTA: the scene pixel, which keys the view's noise
     const uint64_t gsample = xsrc_global_sample(a.xs, s0);
     const uint64_t rstep = xsrc_step(a.xs);               // counter of the random streams (launch argument, or the device-side row)
     // The augmented rows also go to HBM (16-byte stores from the registers that feed the LDS slots): the backward pass
@@ -1071,6 +1074,7 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
           pix = uni64(a.pix[s0]);
           pix = pix < 0 ? 0 : (pix > last ? last : pix);
         }
+        vpix = (uint64_t)pix;
         const int pr = (int)(pix / a.ccols), pc = (int)(pix - (long long)pr * a.ccols), hwin = W >> 1;
         const int magicp = (65536 + W - 1) / W;
 #pragma unroll
@@ -1123,7 +1127,26 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
       // one lambda both paths write the same registers, and the compiler guards the generated values' write with a
       // vmcnt(0) against the possibly outstanding load -- which also waits for every chunk load in flight, 14 times.)
       auto noise_live = [&](int kq, int k) { return sigma != 0.f && kq < nch && item_g0(k) < CH4l; };   // uniform
-      if (nzrow != nullptr) {                             // parity mode: the reference's own draws
+      if constexpr (TTA) {
+        // A view's noise is keyed by (scene pixel, window pixel, band quad), not by the [C][H][W] element order of the
+        // training streams: group G = window pixel * QP + band quad, so that the lane's two items -- bands 8c .. 8c + 7
+        // of ONE window pixel, the band-last gather's unit -- are one hash call.  pch(kq) is the TRUE chunk, whatever
+        // slot of the ring it lands in (B4's second pass).
+        const int QP = 4 * KQ0;
+#pragma unroll
+        for (int kq = 0; kq < SLAB_NUP; ++kq) {
+          const int g = item_g(0);
+          const uint32_t G = (uint32_t)((g >> 2) * QP + 4 * pch(kq) + (g & 3));
+          float4 z0 = make_float4(0.f, 0.f, 0.f, 0.f), z1 = z0;
+          if constexpr (TPW == 2) {
+            if (noise_live(kq, 0)) noise_normal8(a.xs.seed, a.xs.step, STREAM_TTA_XP, vpix, G >> 1, z0, z1);
+            nzv[kq][0] = z0; nzv[kq][TPW - 1] = z1;
+          } else {
+            if (noise_live(kq, 0)) z0 = noise_normal4p(a.xs.seed, a.xs.step, STREAM_TTA_XP, vpix, G);
+            nzv[kq][0] = z0;
+          }
+        }
+      } else if (nzrow != nullptr) {                      // parity mode: the reference's own draws
 #pragma unroll
         for (int kq = 0; kq < SLAB_NUP; ++kq)
 #pragma unroll
@@ -1163,7 +1186,15 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
           const int g = item_g(k), gg = pch(kq) * CH4l + g;
           if constexpr (CUBE) {     // (band quad, pixel) -> four rows of the slot [16 bands][HW]
             if (g < CH4l) {
-              const float4 v = dv[kq % SLAB_WIN][k];
+              float4 v = dv[kq % SLAB_WIN][k];
+              if constexpr (TTA) if (sigma != 0.f) {      // (bands past C stay exactly zero)
+                const int b0 = 16 * pch(kq) + 4 * (g & 3);
+                const float4 z = nzv[kq][k];
+                if (b0 < C) v.x = fmaf(z.x, sigma, v.x);
+                if (b0 + 1 < C) v.y = fmaf(z.y, sigma, v.y);
+                if (b0 + 2 < C) v.z = fmaf(z.z, sigma, v.z);
+                if (b0 + 3 < C) v.w = fmaf(z.w, sigma, v.w);
+              }
               float* d4 = sl + (4 * (g & 3)) * HWl + (g >> 2);
               d4[0] = v.x; d4[HWl] = v.y; d4[2 * HWl] = v.z; d4[3 * HWl] = v.w;
             }
@@ -2401,6 +2432,8 @@ __device__ __forceinline__ const float* conv3_bwd_head_g(const Conv3Args& a, flo
 //  H2X (MODE 2 / 3 with tail / head, four waves): conv1's tap loop on TWO fp16 pieces (conv3_taps_ks_h) whenever the
 //  sample's image and the network's weights are inside the ranges that scheme needs -- else, workgroup-uniformly, the
 //  three-piece bf16 loop, which has no range conditions.
+//  TAIL 4 / 5 (MODE 2): TAIL 2 / 3 -- the cube-fed eval forward by pixel range / list -- on a noisy VIEW of every window
+//  (test-time augmentation, include/cmlpl.h): kernels of their own, so that the clean ones are the code they were.
 template <int MODE, int MTW, int TAIL = 0, int NW = 4, int TPW = 8 / NW, bool KSG = false, bool H2X = false>
 __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) void conv3x3_kernel(Conv3Args a) {
   static_assert(!KSG || (MODE < 2 && MTW == 1 && TAIL == 0 && NW == 4 && TPW == 2), "KSG: four waves, S = 1, four tiles");
@@ -2423,7 +2456,7 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
     if constexpr (BIG) dp_lds = conv3_bwd_head_g(a, smem, mpre);
     else dp_lds = conv3_bwd_head<NW>(a, smem, mpre);
   }
-  conv3_stage<MODE, NW, TPW, INFER ? TAIL - 1 : 0, H2X>(a, smem, LUTN, c, dp_lds, mpre);
+  conv3_stage<MODE, NW, TPW, INFER ? (TAIL & 1) + 1 : 0, H2X, (INFER && TAIL >= 4)>(a, smem, LUTN, c, dp_lds, mpre);
   STAMPG(MODE & 1, 1);
   const int tid = c.tid, lane = c.lane, l31 = c.l31, hh = c.hh, wave = c.wave, net = c.net, s0 = c.s0;
   const int HW = c.HW, PW = c.PW, S = c.S, PX = c.PX, npx = c.npx;
@@ -2883,6 +2916,7 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
 }
 
 
+
 // Small-map variant (all output pixels of the workgroup fit ONE 32-row tile, e.g. the 5x5 / 4x4 maps of
 // conv2 at 11x11 windows): instead of one busy wave and three idle ones, wave w takes output-channel half
 // (w & 1) and input-channel half (w >> 1); the two K halves are folded through LDS before the epilogue.
@@ -3244,7 +3278,7 @@ static hipError_t launch_conv3_small(const Conv3Args& a, dim3 grid, size_t lds, 
 
 // Every 3x3 convolution kernel the library holds, by what selects it: MODE (0 forward, 1 data gradient, 2 / 3 the same with
 // conv0 / conv0's weight gradient fused in), pixel tiles per wave of the planner (0: the one-tile kernel), TAIL (1: with the
-// tail / head; 2 / 3: inference by pixel range / list), waves, tiles a wave's tap loop carries, barrier-free loop, two
+// tail / head; 2 / 3: inference by pixel range / list; 4 / 5: the same on a noisy view), waves, tiles a wave's tap loop carries, barrier-free loop, two
 // fp16 pieces.  A kernel is instantiated by its row here and nowhere else; the rows keep the order in which the code
 // object has always held the kernels.
 struct Conv3Kernel {
@@ -3293,6 +3327,10 @@ static const Conv3Kernel conv3_kernels[] = {
     CMLPL_K(3, 1, 1, 8, 1, false, true),
     CMLPL_K(3, 1, 1, 4, 2, false, true),
     CMLPL_K(3, 1, 0, 4, 2, false, false),
+    CMLPL_K(2, 1, 4, 4, 2, false, false),     // the cube-fed forward on a noisy view: range / list, four-wave / eight-tile
+    CMLPL_K(2, 1, 4, 8, 2, false, false),
+    CMLPL_K(2, 1, 5, 4, 2, false, false),
+    CMLPL_K(2, 1, 5, 8, 2, false, false),
 };
 #undef CMLPL_K
 
@@ -3340,7 +3378,7 @@ hipError_t launch_conv3_fused(const NetRoute& r, int nets, int n, int C, int H, 
 // nn == null: one network, the range from pix0; else the networks' strides and the pixel list
 hipError_t launch_conv3_infer(const Conv3Variant& v, int n, int C, int H, int W, const float* cube, int crows, int ccols,
                               long long pix0, const float* w0t, const float* b0, const float* wpk, const float* bias,
-                              const FwdTail& t, long long* labels_out, hipStream_t st, const InferNets* nn) {
+                              const FwdTail& t, long long* labels_out, hipStream_t st, const InferNets* nn, const ViewKey* view) {
   const int nets = nn != nullptr ? nn->nets : 1;
   if (v.S != 1 || n < 1 || !cube || !labels_out || nets < 1 || nets > 2) return hipErrorInvalidValue;
   if ((long long)crows * ccols * C >= (1LL << 31) || W / 2 > crows || W / 2 > ccols) return hipErrorInvalidValue;   // (32-bit offsets; one mirror fold)
@@ -3355,6 +3393,10 @@ hipError_t launch_conv3_infer(const Conv3Variant& v, int n, int C, int H, int W,
     a.pix = nn->pix;
   }
   const dim3 grid(8 * ((n + 7) / 8), nets);
+  if (view != nullptr && view->sigma != 0.f) {      // a noisy view: the entries of their own (sigma == 0 is the clean launch)
+    a.xs.sigma = view->sigma; a.xs.seed = view->seed; a.xs.step = view->view;
+    return launch_conv3_variant(2, a.pix != nullptr ? 5 : 4, v, a, grid, st);
+  }
   return launch_conv3_variant(2, a.pix != nullptr ? 3 : 2, v, a, grid, st);
 }
 

@@ -108,6 +108,84 @@ template <int G> hipError_t launch_g(const EnsArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- members x views blocks (test-time augmentation: every member scores several noisy views of a pixel; include/cmlpl.h,
+// cmlpl_ensemble_views).  The same lane scheme with a RUN-TIME loop over the blocks, m ascending and within m v ascending:
+//   weights   lane l of every wave holds w_l (selected once from the by-value array with constant indices: a run-time
+//             index into a kernel argument would send the array through scratch); a member's weight is read from lane m
+//   disagree  lane c counts the blocks whose own label is c; the count of the final label's lane is read at the end --
+//             64 blocks need no array of their labels
+constexpr int ENS_MAX_BLOCKS = 64;
+struct EnsViewsArgs {
+  const float* logits; long long member_stride, view_stride;
+  float w[ENS_MAX_BLOCKS];                // per MEMBER: fl32(w_m / sum w / views)
+  int members, views, n, K;
+  long long* labels; float* probs; float* conf; float* entropy; int* disagree;
+};
+
+template <int G> __global__ __launch_bounds__(ENS_THREADS) void ensemble_views_kernel(EnsViewsArgs a) {
+  constexpr int PPW = ENS_THREADS / G;
+  const int tid = threadIdx.x;
+  const int c = tid & (G - 1);
+  const int shift = (tid & 63) & ~(G - 1);
+  const int K = a.K, n = a.n;
+  const bool kv = c < K;
+  const float NEG_INF = -INFINITY;
+  float wl = 0.f;
+#pragma unroll
+  for (int l = 0; l < ENS_MAX_BLOCKS; ++l) wl = ((tid & 63) == l) ? a.w[l] : wl;
+  for (long long base = (long long)blockIdx.x * PPW; base < n; base += (long long)gridDim.x * PPW) {
+    const long long i = base + tid / G;
+    const bool live = kv && i < n;
+    float p = 0.f;
+    int mine = 0;                                         // blocks whose own label is class c
+    for (int m = 0; m < a.members; ++m) {                 // (uniform)
+      const float wm = __shfl(wl, m, 64);
+      const float* zm = a.logits + m * a.member_stride;
+      for (int v = 0; v < a.views; ++v) {
+        const float z = live ? zm[v * a.view_stride + i * K + c] : NEG_INF;
+        const float mx = group_max<G>(z);
+        const float e = live ? expf(z - mx) : 0.f;
+        const float s = group_sum<G>(e);
+        const float pm = live ? e / s : 0.f;
+        mine += (group_argmax<G>(pm, group_max<G>(pm), kv, shift) == c) ? 1 : 0;
+        p += wm * pm;
+      }
+    }
+    const int label = group_argmax<G>(p, group_max<G>(p), kv, shift);
+    const float plab = __shfl(p, shift + label, 64);
+    const int agree = __shfl(mine, shift + label, 64);
+    const float t = (p == 0.f) ? 0.f : p * logf(p);
+    const float ent = 0.f - group_sum<G>(kv ? t : 0.f);
+    if (live) {
+      if (a.probs != nullptr) a.probs[i * K + c] = p;
+      if (c == 0) {
+        a.labels[i] = label;
+        if (a.conf != nullptr) a.conf[i] = plab;
+        if (a.entropy != nullptr) a.entropy[i] = ent;
+        if (a.disagree != nullptr) a.disagree[i] = a.members * a.views - agree;
+      }
+    }
+  }
+}
+
+template <int G> hipError_t launch_views_g(const EnsViewsArgs& a, hipStream_t st) {
+  constexpr int PPW = ENS_THREADS / G;
+  long long wgs = ((long long)a.n + PPW - 1) / PPW;
+  if (wgs > ENS_WG_MAX) wgs = ENS_WG_MAX;
+  hipLaunchKernelGGL(ensemble_views_kernel<G>, dim3((unsigned)wgs), dim3(ENS_THREADS), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble_views(const EnsViewsArgs& a, hipStream_t st) {
+  if (a.K <= 1) return launch_views_g<1>(a, st);
+  if (a.K <= 2) return launch_views_g<2>(a, st);
+  if (a.K <= 4) return launch_views_g<4>(a, st);
+  if (a.K <= 8) return launch_views_g<8>(a, st);
+  if (a.K <= 16) return launch_views_g<16>(a, st);
+  if (a.K <= 32) return launch_views_g<32>(a, st);
+  return launch_views_g<64>(a, st);
+}
+
 hipError_t launch_ensemble(const EnsArgs& a, hipStream_t st) {
   if (a.K <= 1) return launch_g<1>(a, st);
   if (a.K <= 2) return launch_g<2>(a, st);
@@ -144,5 +222,40 @@ extern "C" int cmlpl_ensemble(const float* d_logits, int members, int64_t member
   a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
   a.disagree = d_disagree;
   const hipError_t e = cmlpl::launch_ensemble(a, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+extern "C" int cmlpl_ensemble_views(const float* d_logits, int members, int views, int64_t member_stride, int64_t view_stride,
+                                    const float* weights, int n, int K, int64_t* d_labels, float* d_probs, float* d_conf,
+                                    float* d_entropy, int32_t* d_disagree, void* stream) {
+  if (members < 1 || views < 1 || members > cmlpl::ENS_MAX_BLOCKS || views > cmlpl::ENS_MAX_BLOCKS ||
+      members * views > cmlpl::ENS_MAX_BLOCKS || K < 1 || K > 64 || n < 1)
+    return CMLPL_E_ARG;
+  if (!d_logits || !d_labels) return CMLPL_E_ARG;
+  {  // the blocks must not overlap: views inside members, or members inside views (a stride whose count is 1 is ignored)
+    const int64_t B = (int64_t)n * K;
+    const int64_t ms = members > 1 ? member_stride : 0, vs = views > 1 ? view_stride : 0;
+    const bool v_in_m = (views == 1 || vs >= B) && (members == 1 || ms >= (views == 1 ? B : (int64_t)views * vs));
+    const bool m_in_v = (members == 1 || ms >= B) && (views == 1 || vs >= (members == 1 ? B : (int64_t)members * ms));
+    if (!v_in_m && !m_in_v) return CMLPL_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_conf) |
+       reinterpret_cast<uintptr_t>(d_entropy) | reinterpret_cast<uintptr_t>(d_disagree)) & 3) return CMLPL_E_ARG;
+  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  cmlpl::EnsViewsArgs a = {};
+  double sum = 0.0;
+  for (int m = 0; m < members; ++m) {
+    const double w = weights ? (double)weights[m] : 1.0;
+    if (!(w >= 0.0) || !std::isfinite(w)) return CMLPL_E_ARG;
+    sum += w;
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) return CMLPL_E_ARG;
+  for (int m = 0; m < members; ++m) a.w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum / (double)views);
+  a.logits = d_logits;
+  a.member_stride = members > 1 ? (long long)member_stride : 0; a.view_stride = views > 1 ? (long long)view_stride : 0;
+  a.members = members; a.views = views; a.n = n; a.K = K;
+  a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
+  a.disagree = d_disagree;
+  const hipError_t e = cmlpl::launch_ensemble_views(a, (hipStream_t)stream);
   return e == hipSuccess ? 0 : (int)e;
 }

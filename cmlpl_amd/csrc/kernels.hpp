@@ -89,6 +89,15 @@ hipError_t launch_dist_unpack(const float* recv_f, const float* recv_z, int W, i
 hipError_t launch_extract_patches(const float* cube, int rows, int cols, int C, int w, const long long* idx, int n,
                                   float* out, hipStream_t st);
 
+// ---- tta.hip: the noisy views of test-time augmentation as tensors (include/cmlpl.h); ViewKey: below, with launch_conv3_infer
+struct ViewKey;
+size_t tta_patches_lds(int C, int w);
+hipError_t launch_tta_patches(const float* cube, int rows, int cols, int C, int w, const long long* pix, int n, float* out,
+                              const ViewKey& view, hipStream_t st);
+// out [n][bands] = the view of spectrum row (spec_rows ? spec_rows[i] : i), keyed by pixel (pix ? clamp(pix[i]) : pix0 + i)
+hipError_t launch_tta_spectra(const float* spectra, const long long* spec_rows, const long long* pix, long long pix0,
+                              long long scene_pixels, int n, int bands, float* out, const ViewKey& view, hipStream_t st);
+
 // ---- cube_feed.hip: augmented patch rows of both networks gathered from the scene cube (the cube-fed step)
 size_t cube_feed_lds(int C, int w);
 hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w, const long long* lab_pix,
@@ -146,9 +155,11 @@ hipError_t launch_conv3_fused(const NetRoute& r, int nets, int n, int C, int H, 
 // grid.y -- their parameters / packed weights param_ns / packed_ns floats apart, t.y / t.logits / labels_out [nets][n] rows --
 // and, when pix is set, sample s = scene pixel pix[s].
 struct InferNets { int nets; long long param_ns, packed_ns; const long long* pix; };
+// view `view` of every scene pixel under (seed, sigma) -- test-time augmentation, include/cmlpl.h; sigma == 0: the clean window
+struct ViewKey { float sigma; uint64_t seed; uint32_t view; };
 hipError_t launch_conv3_infer(const Conv3Variant& v /* route_infer */, int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
                               const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
-                              long long* labels_out, hipStream_t st, const InferNets* nn = nullptr);
+                              long long* labels_out, hipStream_t st, const InferNets* nn = nullptr, const ViewKey* view = nullptr);
 // the head / conv2 part of the backward in the same per-sample workgroup: see conv3_bwd_head
 struct BwdHead {
   const float* dlogits; const float* dfeat; const float* mask; const float* wc; long long p_ns;

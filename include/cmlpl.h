@@ -581,6 +581,70 @@ int cmlpl_ema_update(const float* d_src, float* d_ema, int64_t count, double alp
 int cmlpl_ensemble(const float* d_logits, int members, int64_t member_stride, const float* weights, int n, int K,
                    int64_t* d_labels, float* d_probs, float* d_conf, float* d_entropy, int32_t* d_disagree, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- TEST-TIME AUGMENTATION: prediction from several noisy VIEWS of
+ * each pixel, x + sigma N(0,1), the kind of input the networks were trained on (train.py's --m, which the reference parses
+ * and never uses).
+ *
+ * THE DEFINITION OF A VIEW.  View t (0-based) of scene pixel P (row-major index into the cube) under (seed, sigma), in
+ * the terms of the generator of csrc/common.hpp (noise_hash / noise_normal4 / noise_normal4p / noise_normal8 / noise_ctr):
+ *   window element (window pixel p = i W + j, band b):
+ *     x_view = fmaf(z, sigma, x),  z = component (b & 3) of
+ *              noise_normal4p(seed, step = t, CMLPL_STREAM_TTA_XP, gsample = P, G),  G = p QP + (b >> 2),
+ *              QP = 4 ceil(C / 16)
+ *     (bands 8c .. 8c + 7 of one window pixel are ONE hash call -- noise_normal8 with pair G >> 1: the unit of a gather
+ *      from the band-last cube.  The training streams key the [C][H][W] element order instead, where eight consecutive
+ *      elements are eight pixels of one band.)  G < 2^24 for every window up to 20 x 20 and C up to 256.
+ *   spectrum element k:
+ *     x_view = fmaf(z, sigma, x),  z = component (k & 3) of
+ *              noise_normal4(seed, t, CMLPL_STREAM_TTA_X, noise_ctr(P, k >> 2))
+ *   The streams 0x400 / 0x500 are disjoint from the training streams (0x100, 0x200, 0x300, each + net).
+ *   A view is a property of (seed, t, P) ALONE: every network scores the same views, and neither the position of P in a
+ *   list or chunk nor the kind of launch (pixel range, pixel list, by patches) changes a bit of it.  For a pixel list P is
+ *   d_pix[i] clamped into the scene -- also when the spectra are a split's compact rows (d_spec_row == NULL).
+ *   sigma == 0 is legal everywhere below and gives the clean window / spectrum, the clean forward's bytes.
+ *
+ * cmlpl_infer_cube_tta / cmlpl_infer_pixels_tta: cmlpl_infer_cube / cmlpl_infer_pixels on view `view` of every pixel --
+ *   the same arguments, results, shapes and errors, plus (sigma, seed, view).  The fused forward adds the view's noise
+ *   while it stages its slab from the cube (kernels of their own: the clean launches are untouched); the spectra
+ *   get theirs in a small launch into the workspace in front of the spectral branch.  Workspace:
+ *   cmlpl_infer_tta_workspace_bytes(shape, n) / cmlpl_eval_tta_workspace_bytes(shape, nets, n) (0: not a shape they take).
+ *   CMLPL_E_ARG also for a sigma that is negative or not finite; every error is returned before any launch.
+ *
+ * cmlpl_tta_patches: cmlpl_extract_patches plus the view's noise -- d_out [n][C][w][w] = view `view` of the windows of
+ *   the pixels d_pixel_idx[i] (clamped into the scene), and, when d_spectra_out is not NULL, d_spectra_out [n][bands] =
+ *   the view of their spectra: row d_spec_row[i] of d_spectra, or row i when d_spec_row is NULL.  (d_out may be NULL when
+ *   only the spectra are wanted; then C and w are not looked at.)  It feeds the by-patches path (windows the fused
+ *   forward does not take), and it is the observable form of the definition above.  Errors as cmlpl_extract_patches.
+ *
+ * cmlpl_ensemble_views: cmlpl_ensemble over members x views logit blocks [n][K] (members >= 1, views >= 1, their product
+ *   at most 64): block (m, v) starts at d_logits + m member_stride + v view_stride.
+ *     p = sum_m sum_v w_{m,v} softmax(z_{m,v}),  w_{m,v} = fl32(weights[m] / sum(weights) / views), formed in double on the
+ *     host; the terms are added m ascending and, within m, v ascending, each with cmlpl_ensemble's per-term operation --
+ *     at views == 1 every output equals cmlpl_ensemble's bit for bit.
+ *     label, conf, entropy, p as in cmlpl_ensemble; disagree = the number of (member, view) blocks whose own label differs.
+ *   The same lane scheme (G lanes per pixel, shuffles only, a run-time loop over the blocks, no LDS, no atomics), the same
+ *   bytes on every run.  CMLPL_E_ARG before any launch: what cmlpl_ensemble refuses, members x views outside 1..64, blocks
+ *   that overlap (with B = n K: neither  view_stride >= B and member_stride >= views view_stride  nor
+ *   member_stride >= B and view_stride >= members member_stride;  a stride whose count is 1 is ignored). */
+enum { CMLPL_STREAM_TTA_XP = 0x400, CMLPL_STREAM_TTA_X = 0x500 };
+size_t cmlpl_infer_tta_workspace_bytes(const cmlpl_shape* shape, int n);
+int cmlpl_infer_cube_tta(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
+                         int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
+                         float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
+                         float sigma, uint64_t seed, uint32_t view);
+size_t cmlpl_eval_tta_workspace_bytes(const cmlpl_shape* shape, int nets, int n);
+int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                           const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                           const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                           int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
+                           float sigma, uint64_t seed, uint32_t view);
+int cmlpl_tta_patches(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
+                      float* d_out, const float* d_spectra, const int64_t* d_spec_row, int bands, float* d_spectra_out,
+                      float sigma, uint64_t seed, uint32_t view, void* stream);
+int cmlpl_ensemble_views(const float* d_logits, int members, int views, int64_t member_stride, int64_t view_stride,
+                         const float* weights, int n, int K, int64_t* d_labels, float* d_probs, float* d_conf,
+                         float* d_entropy, int32_t* d_disagree, void* stream);
+
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy
  * computes them.  d_raw [pixels][bands] row-major in its .mat dtype (CMLPL_SCENE_*, converted exactly to fp64 in the

@@ -14,7 +14,10 @@ maximum of their averaged softmax (cmlpl_amd.ensemble; ``ensemble_all`` adds bot
 with the tag ``_ens``; ``--proba`` / ``--confidence`` / ``--entropy`` write the class probabilities float32
 [rows * cols, K], the probability of the label and the entropy float32 [rows * cols] -- of the ensemble, or of a single
 ``--net`` (its own softmax: a one-member ensemble; its label map stays the argmax of its logits).  ``--synthetic SHAPE`` labels the seeded synthetic scene that
-``train.py --synthetic`` evaluates on (datasets are not shipped)."""
+``train.py --synthetic`` evaluates on (datasets are not shipped).  ``--tta M`` predicts from the clean window and M noisy views
+(x + S N(0,1), S = ``--tta_noise``, default the checkpoint's training noise) of every pixel, averaged over the views and
+over the networks of ``--net`` (any single network or ensemble; cmlpl_amd.tta): the label map, the ``Result:`` lines (tag
+``_tta``) and ``--proba`` / ``--confidence`` / ``--entropy`` then describe that prediction."""
 import argparse
 import os
 
@@ -23,7 +26,7 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import DATASETS, SYNTH, ensemble_whole, evaluate_whole
+from train import DATASETS, SYNTH, ensemble_whole, evaluate_whole, tta_whole
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 
@@ -33,6 +36,18 @@ def check_args(args):
     if args.net in ('both', 'ema_both') and (args.proba or args.confidence or args.entropy):
         raise SystemExit("--proba / --confidence / --entropy describe ONE prediction: --net %s writes two label maps "
                          "(name one network, or --net ensemble for the two together)" % args.net)
+    if args.tta is not None:
+        if args.net in ('both', 'ema_both'):
+            raise SystemExit("--tta gives ONE prediction: --net %s writes two label maps (name one network, or --net "
+                             "ensemble for the two together)" % args.net)
+        if args.tta < 1 or args.tta > 63:
+            raise SystemExit("--tta M: 1 .. 63 views")
+        if args.tta_noise is not None and not (0.0 <= args.tta_noise < float("inf")):
+            raise SystemExit("--tta_noise S: a finite S >= 0")
+        if args.tta_seed < 0 or args.tta_seed >= 2 ** 64:
+            raise SystemExit("--tta_seed N: 0 <= N < 2^64")
+    elif args.tta_noise is not None or args.tta_no_clean:
+        raise SystemExit("--tta_noise / --tta_no_clean belong to --tta M")
 
 
 def main(args, device=None):
@@ -67,6 +82,15 @@ def main(args, device=None):
     keys = {0: "Base", 1: "Base1", 'ema0': "Teacher", 'ema1': "Teacher1"}
     extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
     common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
+    if args.tta is not None:
+        from cmlpl_amd.tta import TTA
+        tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
+                  clean=not args.tta_no_clean)
+        out = tta_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device, tta, **common, **extras)
+        save_extras(args, out)
+        if args.out:
+            np.save(args.out, out["labels"])
+        return out["labels"]
     if args.net in ENSEMBLES:
         ens = ensemble_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device, **common, **extras)
         save_extras(args, ens)
@@ -110,6 +134,13 @@ def build_parser():
                         help='write the probability of the predicted class float32 [rows*cols] as .npy')
     parser.add_argument('--entropy', default=None, metavar='FILE',
                         help='write the entropy of the class probabilities float32 [rows*cols] as .npy')
+    parser.add_argument('--tta', type=int, default=None, metavar='M',
+                        help='test-time augmentation: predict from the clean window and M noisy views of every pixel, '
+                             'averaged over the views and the networks of --net (not with both / ema_both)')
+    parser.add_argument('--tta_noise', type=float, default=None, metavar='S',
+                        help="--tta: the views are x + S N(0,1) (default: the checkpoint's training noise)")
+    parser.add_argument('--tta_seed', type=int, default=1088, metavar='N', help='--tta: the seed of the views')
+    parser.add_argument('--tta_no_clean', action='store_true', help='--tta: the noisy views only, without the clean window')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

@@ -50,7 +50,7 @@ from tools.models import BaseNet2
 
 DATASETS = {1: (9, 103), 2: (16, 204), 3: (15, 144), 4: (16, 200)}     # num_classes, num_features (train.py:75-90)
 SYNTH = {"B2": (103, 11, 11, 103, 9), "P": (60, 20, 20, 103, 9), "B4": (200, 11, 11, 200, 16),
-         "B5": (48, 15, 15, 48, 20)}
+         "B5": (48, 15, 15, 48, 20), "W8": (40, 8, 8, 40, 5)}
 
 
 class DeviceLoader:
@@ -117,9 +117,9 @@ def run_ema(args):
 
 
 def saved_args(args):
-    """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble) is left
+    """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta) is left
     out at its default, so a file written without it is byte for byte what it was before the flag existed"""
-    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False}
+    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
@@ -129,7 +129,8 @@ def run_differences(saved, mine):
 
 
 NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
-            'ens': '_ens'}                                         # ensemble_whole: several of them together
+            'ens': '_ens',                                         # ensemble_whole: several of them together
+            'tta': '_tta'}                                         # tta_whole: over noisy views of every pixel
 
 
 def run_ensemble(args):
@@ -174,6 +175,36 @@ def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
     print('ensemble inference time == %.3f s (%d networks)' % (time.time() - t1, len(models)))
     if test_array is not None:
         print_result(NET_TAGS['ens'], out["labels"], test_array, Y_test)
+    return out
+
+
+def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
+              resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+    """``ensemble_whole`` over the noisy views of ``tta`` (cmlpl_amd.tta.TTA): every network of ``nets`` scores every view
+    of every scene pixel, one label map from the average of all their softmaxes (cmlpl_amd.tta.tta_cube).  Same returns;
+    the ``Result:`` lines carry the tag ``_tta``."""
+    from cmlpl_amd.infer import infer_supported
+    from cmlpl_amd.tta import tta_cube
+    source = None
+    if infer_supported(NetShape(*shape)):
+        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
+            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
+    if source is None:
+        raise SystemExit("test-time augmentation needs the scene cube (cube.npy + scene.json in the dataset directory, "
+                         "sample_generation.py) and a square window")
+    models = []
+    for _, sd in nets:
+        model = BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
+                         window=shape[1]).to(device)
+        model.load_state_dict(sd)
+        models.append(model.eval())
+    t1 = time.time()
+    res = tta_cube(models, source.cube, source.spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy)
+    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
+    print('tta inference time == %.3f s (%d networks x %d views%s, noise %g)' %
+          (time.time() - t1, len(models), tta.views, ' + the clean window' if tta.clean else '', tta.sigma))
+    if test_array is not None:
+        print_result(NET_TAGS['tta'], out["labels"], test_array, Y_test)
     return out
 
 
@@ -540,6 +571,10 @@ def main(args, make_engine=None, device=None):
         if ens:
             ensemble_whole(shape, whole, nets[:2], device, synthetic=args.synthetic, dataID=args.dataID,
                            dropout=args.dropout, test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"))
+        if getattr(args, "tta", False):
+            from cmlpl_amd.tta import TTA
+            tta_whole(shape, whole, nets[:2], device, TTA(args.m, args.noise), synthetic=args.synthetic, dataID=args.dataID,
+                      dropout=args.dropout, test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"))
     if world > 1 and make_engine is None:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -569,7 +604,7 @@ def build_parser():
                         help='--ema: the coefficient of the moving average (ignored without --ema)')
     parser.add_argument('--dropout', type=float, default=0.8)
     parser.add_argument('--noise', type=float, default=0.5)
-    parser.add_argument('--m', type=int, default=5, help='number of stochastic augmentations')
+    parser.add_argument('--m', type=int, default=5, help='number of stochastic augmentations (the views of --tta)')
     # this build
     parser.add_argument('--method', choices=('cmlpl', 'cps'), default='cmlpl',
                         help="the training method: 'cmlpl' (the reference's train.py) or 'cps', the cross-pseudo-supervision "
@@ -583,6 +618,10 @@ def build_parser():
                         help="score the two networks TOGETHER as well: the label of their averaged softmax, on the device -- a "
                              "third validation_ens line per --eval_every evaluation (curve_ens in --save_eval) and a third "
                              "Result: block (OA_ens) after the run; --save_best keeps its criterion, network 0's OA")
+    parser.add_argument('--tta', action='store_true',
+                        help="test-time augmentation after the run: Base and Base1 TOGETHER score the clean window and --m "
+                             "noisy views (x + --noise N(0,1)) of every scene pixel, one more Result: block (OA_tta) from "
+                             "the average of all their softmaxes; the run itself is untouched")
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

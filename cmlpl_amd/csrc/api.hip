@@ -1068,128 +1068,95 @@ int cmlpl_extract_patches(const float* d_cube, int rows, int cols, int C, int w,
                                     (hipStream_t)stream));
 }
 
-size_t cmlpl_infer_workspace_bytes(const cmlpl_shape* shape, int n) {
+// ---- inference straight from the scene cube: ONE core under the four entry points.  `nets` networks score n pixels -- a
+// LIST (d_pix, with d_spec_row) or the RANGE from pixel0 on -- clean (view == nullptr) or on a view of test-time
+// augmentation (include/cmlpl.h, "THE DEFINITION OF A VIEW"; sigma == 0: exactly the clean call's launches and writes).
+// Workspace: y = relu(feat_spe(spectrum)) [nets][n][1024], then -- a view call -- the view's spectra rows [n][bands].
+static bool view_args_ok(float sigma) { return sigma >= 0.f && sigma <= 3.0e38f; }   // (a NaN fails both)
+
+static size_t infer_y_bytes(int nets, int n) { return up256((size_t)nets * n * 1024 * 4); }
+
+static size_t infer_workspace(const cmlpl_shape* shape, int nets, int n, bool view) {
   Dims d;
   Conv3Variant v;
-  if (!make_dims(shape, &d) || n < 1 || !route_infer(d.H, d.W, d.C, d.K, &v)) return 0;   // 0: not a shape cmlpl_infer_cube takes
-  return up256((size_t)n * 1024 * 4);                       // y = relu(feat_spe(spectrum)) of the launch's pixels
+  if (!make_dims(shape, &d) || n < 1 || nets < 1 || nets > 2 || !route_infer(d.H, d.W, d.C, d.K, &v)) return 0;   // 0: not a shape the fused forward takes
+  return infer_y_bytes(nets, n) + (view ? up256((size_t)n * shape->bands * 4) : 0);
 }
 
-int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
-                     int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
-                     float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream) {
+static int infer_impl(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride, const float* d_packed,
+                      int64_t packed_stride, const float* d_cube, int rows, int cols, const float* d_spectra, bool listed,
+                      const int64_t* d_spec_row, const int64_t* d_pix, int64_t pixel0, int n, int64_t* d_labels,
+                      float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, const ViewKey* view) {
   Dims d;
   cmlpl_layout_t L;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
   if (!d_params || !d_packed || !d_cube || !d_spectra || !d_labels || !d_workspace || rows < 1 || cols < 1 || n < 1 ||
-      pixel0 < 0 || pixel0 + n > (int64_t)rows * cols)
+      (view && !view_args_ok(view->sigma)))
+    return CMLPL_E_ARG;
+  if (listed ? (!d_pix || nets < 1 || nets > 2 || rows < d.H / 2 || cols < d.W / 2 ||
+                (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
+             : (pixel0 < 0 || pixel0 + n > (int64_t)rows * cols))
     return CMLPL_E_ARG;
   Conv3Variant v;
   if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
-  if (cmlpl_infer_workspace_bytes(shape, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
+  const bool big = (int64_t)rows * cols * d.C >= (1LL << 31);                  // (the gather's 32-bit offsets)
+  if (listed && big) return CMLPL_E_ARG;
+  if (infer_workspace(shape, nets, n, view != nullptr) > workspace_bytes) return CMLPL_E_WORKSPACE;
+  if (view && view->sigma == 0.f) view = nullptr;      // the clean forward, its launches and its bytes
+  if (view && !listed && (big || d.W / 2 > rows || d.W / 2 > cols)) return CMLPL_E_ARG;   // (what the launcher refuses)
   hipStream_t st = (hipStream_t)stream;
   float* y = (float*)d_workspace;
+  const float* sn = listed ? d_spectra : d_spectra + (long long)pixel0 * d.bands;
+  const long long* spec_row = (const long long*)d_spec_row;
   int rc;
-  // spectral branch of the range's pixels (plain rows, canonical weight)
-  if ((rc = chk(launch_spe_fwd(1, n, d.bands, d_spectra + (long long)pixel0 * d.bands, d_params + L.param_off[6],
-                               d_params + L.param_off[7], L.param_total, y, st)))) return rc;
-  FwdTail t;
-  memset(&t, 0, sizeof(t));
-  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
-  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
-  t.y = y; t.logits = d_logits; t.K = d.K;
-  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
-                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
-                                d_params + L.param_off[3], t, (long long*)d_labels, st));
-}
-
-size_t cmlpl_eval_workspace_bytes(const cmlpl_shape* shape, int nets, int n) {
-  Dims d;
-  Conv3Variant v;
-  if (!make_dims(shape, &d) || n < 1 || nets < 1 || nets > 2 || !route_infer(d.H, d.W, d.C, d.K, &v)) return 0;   // 0: not a shape cmlpl_infer_pixels takes
-  return up256((size_t)nets * n * 1024 * 4);                // y = relu(feat_spe(spectrum)) [nets][n][1024]
-}
-
-int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
-                       const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
-                       const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
-                       int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream) {
-  Dims d;
-  cmlpl_layout_t L;
-  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
-  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_pix || !d_labels || !d_workspace || n < 1 || nets < 1 ||
-      nets > 2 || rows < 1 || cols < 1 || rows < d.H / 2 || cols < d.W / 2 ||
-      (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
-    return CMLPL_E_ARG;
-  Conv3Variant v;
-  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
-  if ((int64_t)rows * cols * d.C >= (1LL << 31)) return CMLPL_E_ARG;          // (the gather's 32-bit offsets)
-  if (cmlpl_eval_workspace_bytes(shape, nets, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* y = (float*)d_workspace;
-  int rc;
-  // spectral branch of the list's items, both networks from the same rows (canonical weights)
-  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, d_spectra, d_params + L.param_off[6], d_params + L.param_off[7],
-                               param_stride, y, st, (const long long*)d_spec_row, 0)))) return rc;
+  if (view) {          // every network scores the same view: one set of rows, read by all (network stride 0)
+    float* vrows = (float*)((char*)d_workspace + infer_y_bytes(nets, n));
+    if ((rc = chk(launch_tta_spectra(sn, spec_row, (const long long*)d_pix, pixel0, (long long)rows * cols, n, d.bands, vrows,
+                                     *view, st)))) return rc;
+    sn = vrows;
+    spec_row = nullptr;
+  }
+  // spectral branch of the pixels (canonical weights); the range-fed call is one network on plain rows
+  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, sn, d_params + L.param_off[6], d_params + L.param_off[7],
+                               listed ? (long long)param_stride : L.param_total, y, st, spec_row, listed ? 0 : -1)))) return rc;
   FwdTail t;
   memset(&t, 0, sizeof(t));
   t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
   t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
   t.y = y; t.logits = d_logits; t.K = d.K;
   const InferNets nn = {nets, (long long)param_stride, (long long)packed_stride, (const long long*)d_pix};
-  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
+  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
                                 d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
-                                d_params + L.param_off[3], t, (long long*)d_labels, st, &nn));
+                                d_params + L.param_off[3], t, (long long*)d_labels, st, listed ? &nn : nullptr, view));
 }
 
-// ---- test-time augmentation (include/cmlpl.h, "THE DEFINITION OF A VIEW"): the two entry points above on a noisy view.
-// Workspace: what the clean call takes (y), then the view's spectra rows [n][bands].
-static bool view_args_ok(float sigma) { return sigma >= 0.f && sigma <= 3.0e38f; }   // (a NaN fails both)
+size_t cmlpl_infer_workspace_bytes(const cmlpl_shape* shape, int n) { return infer_workspace(shape, 1, n, false); }
+size_t cmlpl_eval_workspace_bytes(const cmlpl_shape* shape, int nets, int n) { return infer_workspace(shape, nets, n, false); }
+size_t cmlpl_infer_tta_workspace_bytes(const cmlpl_shape* shape, int n) { return infer_workspace(shape, 1, n, true); }
+size_t cmlpl_eval_tta_workspace_bytes(const cmlpl_shape* shape, int nets, int n) { return infer_workspace(shape, nets, n, true); }
 
-size_t cmlpl_infer_tta_workspace_bytes(const cmlpl_shape* shape, int n) {
-  const size_t y = cmlpl_infer_workspace_bytes(shape, n);
-  return y == 0 ? 0 : y + up256((size_t)n * shape->bands * 4);
+int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
+                     int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
+                     float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return infer_impl(shape, 1, d_params, 0, d_packed, 0, d_cube, rows, cols, d_spectra, false, nullptr, nullptr, pixel0, n,
+                    d_labels, d_logits, d_workspace, workspace_bytes, stream, nullptr);
+}
+
+int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                       const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                       const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                       int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return infer_impl(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra, true,
+                    d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, nullptr);
 }
 
 int cmlpl_infer_cube_tta(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
                          int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
                          float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, float sigma,
                          uint64_t seed, uint32_t view) {
-  Dims d;
-  cmlpl_layout_t L;
-  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
-  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_labels || !d_workspace || rows < 1 || cols < 1 || n < 1 ||
-      pixel0 < 0 || pixel0 + n > (int64_t)rows * cols || !view_args_ok(sigma))
-    return CMLPL_E_ARG;
-  Conv3Variant v;
-  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
-  if (cmlpl_infer_tta_workspace_bytes(shape, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
-  if (sigma == 0.f)      // the clean forward, its launches and its bytes
-    return cmlpl_infer_cube(shape, d_params, d_packed, d_cube, rows, cols, d_spectra, pixel0, n, d_labels, d_logits,
-                            d_workspace, workspace_bytes, stream);
-  if ((int64_t)rows * cols * d.C >= (1LL << 31) || d.W / 2 > rows || d.W / 2 > cols) return CMLPL_E_ARG;   // (what the launcher refuses)
-  hipStream_t st = (hipStream_t)stream;
-  float* y = (float*)d_workspace;
-  float* sn = (float*)((char*)d_workspace + cmlpl_infer_workspace_bytes(shape, n));
   const ViewKey key = {sigma, seed, view};
-  int rc;
-  if ((rc = chk(launch_tta_spectra(d_spectra + (long long)pixel0 * d.bands, nullptr, nullptr, pixel0, (long long)rows * cols, n,
-                                   d.bands, sn, key, st)))) return rc;
-  if ((rc = chk(launch_spe_fwd(1, n, d.bands, sn, d_params + L.param_off[6], d_params + L.param_off[7], L.param_total, y,
-                               st)))) return rc;
-  FwdTail t;
-  memset(&t, 0, sizeof(t));
-  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
-  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
-  t.y = y; t.logits = d_logits; t.K = d.K;
-  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, pixel0, d_packed + pack_off_w0b3(d.C, d.bands),
-                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
-                                d_params + L.param_off[3], t, (long long*)d_labels, st, nullptr, &key));
-}
-
-size_t cmlpl_eval_tta_workspace_bytes(const cmlpl_shape* shape, int nets, int n) {
-  const size_t y = cmlpl_eval_workspace_bytes(shape, nets, n);
-  return y == 0 ? 0 : y + up256((size_t)n * shape->bands * 4);
+  return infer_impl(shape, 1, d_params, 0, d_packed, 0, d_cube, rows, cols, d_spectra, false, nullptr, nullptr, pixel0, n,
+                    d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
 }
 
 int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
@@ -1197,39 +1164,9 @@ int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_pa
                            const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
                            int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
                            float sigma, uint64_t seed, uint32_t view) {
-  Dims d;
-  cmlpl_layout_t L;
-  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
-  if (!d_params || !d_packed || !d_cube || !d_spectra || !d_pix || !d_labels || !d_workspace || n < 1 || nets < 1 ||
-      nets > 2 || rows < 1 || cols < 1 || rows < d.H / 2 || cols < d.W / 2 ||
-      (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)) || !view_args_ok(sigma))
-    return CMLPL_E_ARG;
-  Conv3Variant v;
-  if (!route_infer(d.H, d.W, d.C, d.K, &v)) return CMLPL_E_SHAPE;
-  if ((int64_t)rows * cols * d.C >= (1LL << 31)) return CMLPL_E_ARG;          // (the gather's 32-bit offsets)
-  if (cmlpl_eval_tta_workspace_bytes(shape, nets, n) > workspace_bytes) return CMLPL_E_WORKSPACE;
-  if (sigma == 0.f)
-    return cmlpl_infer_pixels(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra,
-                              d_spec_row, d_pix, n, d_labels, d_logits, d_workspace, workspace_bytes, stream);
-  hipStream_t st = (hipStream_t)stream;
-  float* y = (float*)d_workspace;
-  float* sn = (float*)((char*)d_workspace + cmlpl_eval_workspace_bytes(shape, nets, n));
   const ViewKey key = {sigma, seed, view};
-  int rc;
-  // every network scores the same view: one set of rows, read by both (network stride 0)
-  if ((rc = chk(launch_tta_spectra(d_spectra, (const long long*)d_spec_row, (const long long*)d_pix, 0,
-                                   (long long)rows * cols, n, d.bands, sn, key, st)))) return rc;
-  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, sn, d_params + L.param_off[6], d_params + L.param_off[7], param_stride, y,
-                               st, nullptr, 0)))) return rc;
-  FwdTail t;
-  memset(&t, 0, sizeof(t));
-  t.w2f = d_packed + pack_off_b3(d.C, d.bands, 2); t.b2 = d_params + L.param_off[5];
-  t.wc = d_params + L.param_off[8]; t.bc = d_params + L.param_off[9];
-  t.y = y; t.logits = d_logits; t.K = d.K;
-  const InferNets nn = {nets, (long long)param_stride, (long long)packed_stride, (const long long*)d_pix};
-  return chk(launch_conv3_infer(v, n, d.C, d.H, d.W, d_cube, rows, cols, 0, d_packed + pack_off_w0b3(d.C, d.bands),
-                                d_params + L.param_off[1], d_packed + pack_off_b3(d.C, d.bands, 0),
-                                d_params + L.param_off[3], t, (long long*)d_labels, st, &nn, &key));
+  return infer_impl(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra, true,
+                    d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
 }
 
 int cmlpl_tta_patches(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,

@@ -196,6 +196,28 @@ hipError_t launch_ensemble(const EnsArgs& a, hipStream_t st) {
   return launch_g<64>(a, st);
 }
 
+// ---- what the two exported calls check alike
+bool ens_aligned(const float* logits, const int64_t* labels, const float* probs, const float* conf, const float* entropy,
+                 const int32_t* disagree) {
+  return !((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(conf) |
+            reinterpret_cast<uintptr_t>(entropy) | reinterpret_cast<uintptr_t>(disagree)) & 3) &&
+         !(reinterpret_cast<uintptr_t>(labels) & 7);
+}
+
+// w[m] = fl32(weights[m] / sum / views) in double (nullptr: equal weights); false: a weight that is negative or not
+// finite (a NaN fails the comparison), or a sum that is not positive
+bool ens_weights(const float* weights, int members, int views, float* w) {
+  double sum = 0.0;
+  for (int m = 0; m < members; ++m) {
+    const double v = weights ? (double)weights[m] : 1.0;
+    if (!(v >= 0.0) || !std::isfinite(v)) return false;
+    sum += v;
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) return false;
+  for (int m = 0; m < members; ++m) w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum / (double)views);
+  return true;
+}
+
 }  // namespace
 }  // namespace cmlpl
 
@@ -205,18 +227,9 @@ extern "C" int cmlpl_ensemble(const float* d_logits, int members, int64_t member
   if (members < 1 || members > cmlpl::ENS_MAX_MEMBERS || K < 1 || K > 64 || n < 1) return CMLPL_E_ARG;
   if (!d_logits || !d_labels) return CMLPL_E_ARG;
   if (members > 1 && member_stride < (int64_t)n * K) return CMLPL_E_ARG;          // the members' blocks must not overlap
-  if ((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_conf) |
-       reinterpret_cast<uintptr_t>(d_entropy) | reinterpret_cast<uintptr_t>(d_disagree)) & 3) return CMLPL_E_ARG;
-  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  if (!cmlpl::ens_aligned(d_logits, d_labels, d_probs, d_conf, d_entropy, d_disagree)) return CMLPL_E_ARG;
   cmlpl::EnsArgs a = {};
-  double sum = 0.0;
-  for (int m = 0; m < members; ++m) {
-    const double w = weights ? (double)weights[m] : 1.0;
-    if (!(w >= 0.0) || !std::isfinite(w)) return CMLPL_E_ARG;                    // (a NaN fails the comparison)
-    sum += w;
-  }
-  if (!(sum > 0.0) || !std::isfinite(sum)) return CMLPL_E_ARG;
-  for (int m = 0; m < members; ++m) a.w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum);
+  if (!cmlpl::ens_weights(weights, members, 1, a.w)) return CMLPL_E_ARG;
   a.logits = d_logits; a.member_stride = members > 1 ? (long long)member_stride : 0;
   a.members = members; a.n = n; a.K = K;
   a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
@@ -239,18 +252,9 @@ extern "C" int cmlpl_ensemble_views(const float* d_logits, int members, int view
     const bool m_in_v = (members == 1 || ms >= B) && (views == 1 || vs >= (members == 1 ? B : (int64_t)members * ms));
     if (!v_in_m && !m_in_v) return CMLPL_E_ARG;
   }
-  if ((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_conf) |
-       reinterpret_cast<uintptr_t>(d_entropy) | reinterpret_cast<uintptr_t>(d_disagree)) & 3) return CMLPL_E_ARG;
-  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  if (!cmlpl::ens_aligned(d_logits, d_labels, d_probs, d_conf, d_entropy, d_disagree)) return CMLPL_E_ARG;
   cmlpl::EnsViewsArgs a = {};
-  double sum = 0.0;
-  for (int m = 0; m < members; ++m) {
-    const double w = weights ? (double)weights[m] : 1.0;
-    if (!(w >= 0.0) || !std::isfinite(w)) return CMLPL_E_ARG;
-    sum += w;
-  }
-  if (!(sum > 0.0) || !std::isfinite(sum)) return CMLPL_E_ARG;
-  for (int m = 0; m < members; ++m) a.w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum / (double)views);
+  if (!cmlpl::ens_weights(weights, members, views, a.w)) return CMLPL_E_ARG;
   a.logits = d_logits;
   a.member_stride = members > 1 ? (long long)member_stride : 0; a.view_stride = views > 1 ? (long long)view_stride : 0;
   a.members = members; a.views = views; a.n = n; a.K = K;

@@ -7,9 +7,9 @@ the host), ``label`` = the first maximum of ``p`` (a NaN counts as the maximum, 
 ``conf = p[label]``, ``entropy = -sum_c p_c log p_c`` (0 log 0 = 0) and ``disagree`` = how many members' own first-maximum
 label differs from ``label``.  Members are 1..4 networks -- Base and Base1, their EMA teachers, or loaded modules.
 
-``ensemble_logits`` is the launch on logits that exist; ``ensemble_cube`` / ``ensemble_pixels`` run the eval forwards of
-``cmlpl_amd.infer`` chunk by chunk into one reused logits buffer with one launch behind each chunk.  Nothing here
-synchronises; everything runs on the current stream."""
+``ensemble_logits`` is the launch on logits that exist; ``ensemble_cube`` / ``ensemble_pixels`` are ``_ensemble`` -- the
+chunk loop of ``cmlpl_amd.infer`` with a reduction behind each chunk -- on the one clean block, as ``cmlpl_amd.tta`` is on
+the blocks of a ``TTA``.  Nothing here synchronises; everything runs on the current stream."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +18,7 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 
 from . import _lib
-from .infer import _infer_pixels_into, _nets_buffers, check_pixel_list, infer_cube
+from .infer import _check_feed, _check_scene, _Forward, _List, _nets_buffers, _predict, _Range, _same_shape
 
 MAX_MEMBERS = 4
 
@@ -50,12 +50,15 @@ def _alloc(n: int, K: int, dev, probs: bool, conf: bool, entropy: bool, disagree
         torch.empty(n, dtype=torch.int32, device=dev) if disagree else None)
 
 
-def _launch(lib, logits_ptr: int, members: int, stride: int, cw, n: int, K: int, res: EnsembleResult, o: int, stream):
-    """one cmlpl_ensemble over n pixels whose results go to rows o .. o + n - 1 of ``res``"""
+def _reduce(lib, z_ptr: int, M: int, V, ms: int, vs: int, cw, n: int, K: int, res: EnsembleResult, o: int, stream):
+    """one cmlpl_ensemble (``V`` None) or cmlpl_ensemble_views (V views) over n pixels of M members, the blocks ``ms`` /
+    ``vs`` floats apart; the results go to rows o .. o + n - 1 of ``res``"""
     at = lambda t, size: None if t is None else t.data_ptr() + size * o
-    _lib.check("cmlpl_ensemble", lib.cmlpl_ensemble(
-        logits_ptr, members, stride, cw, n, K, at(res.labels, 8), at(res.probs, 4 * K), at(res.conf, 4),
-        at(res.entropy, 4), at(res.disagree, 4), stream))
+    outs = (at(res.labels, 8), at(res.probs, 4 * K), at(res.conf, 4), at(res.entropy, 4), at(res.disagree, 4), stream)
+    if V is None:
+        _lib.check("cmlpl_ensemble", lib.cmlpl_ensemble(z_ptr, M, ms, cw, n, K, *outs))
+    else:
+        _lib.check("cmlpl_ensemble_views", lib.cmlpl_ensemble_views(z_ptr, M, V, ms, vs, cw, n, K, *outs))
 
 
 @torch.no_grad()
@@ -74,7 +77,7 @@ def ensemble_logits(logits: torch.Tensor, weights: Optional[Sequence[float]] = N
         raise ValueError(f"logits: {M} members, the ensemble takes 1 .. {MAX_MEMBERS}")
     res = _alloc(n, K, logits.device, probs, conf, entropy, disagree)
     st = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
-    _launch(_lib.load(), logits.data_ptr(), M, logits.stride(0) if M > 1 else n * K, _weights(weights, M), n, K, res, 0, st)
+    _reduce(_lib.load(), logits.data_ptr(), M, None, logits.stride(0) if M > 1 else n * K, 0, _weights(weights, M), n, K, res, 0, st)
     return res
 
 
@@ -100,39 +103,38 @@ def _groups(nets):
     return groups, members
 
 
+def _ensemble(nets, cube, spectra, feed, keys, chunk, weights, asks) -> EnsembleResult:
+    """``ensemble_*`` (``keys`` None: the one clean block, reduced by cmlpl_ensemble) and ``cmlpl_amd.tta.tta_*`` (``keys``:
+    the view keys of a ``TTA`` for a number of members, reduced by cmlpl_ensemble_views) on a feed of ``cmlpl_amd.infer``:
+    per chunk every block x member forward writes into one reused buffer [blocks, members, chunk, K] and one reduction
+    follows.  The range feed runs one network per forward, the list feed a pair ``(engine, None)`` in one launch chain."""
+    groups, M = _groups(nets)
+    keys = None if keys is None else keys(M)
+    if isinstance(feed, _Range):
+        groups = [(m, 1) for e, k in groups for m in ([(e[0], 0), (e[0], 1)] if k == 2 else [e])]
+    bufs = [_nets_buffers(e) for e, _ in groups]
+    cs = _same_shape(bufs)
+    _check_scene(cube, spectra, cs, whole=isinstance(feed, _Range))
+    n = _check_feed(cube, spectra, feed)
+    cw = _weights(weights, M)
+    lib, dev, K = _lib.load(), cube.device, cs.K
+    V = None if keys is None else len(keys)
+    fwd = _Forward(lib, cs, max(b[1] for b in bufs), cube, spectra, feed, n, chunk, views=keys is not None, labels=False)
+    res = _alloc(n, K, dev, *asks)
+    buf = torch.empty((V or 1) * M * fwd.chunk * K, dtype=torch.float32, device=dev)
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _predict(fwd, bufs, keys or [None], n, buf=buf,
+             reduce=lambda z, o, m: _reduce(lib, z.data_ptr(), M, V, m * K, M * m * K, cw, m, K, res, o, st))
+    return res
+
+
 @torch.no_grad()
 def ensemble_cube(nets, cube: torch.Tensor, spectra: torch.Tensor, pixel0: int = 0, n: Optional[int] = None,
                   chunk: int = 65536, weights: Optional[Sequence[float]] = None, probs: bool = False, conf: bool = False,
                   entropy: bool = False, disagree: bool = False) -> EnsembleResult:
-    """The ensemble of ``nets`` (see ``_groups``) on pixels pixel0 .. pixel0 + n - 1 of the scene (default: all of it):
-    per chunk every member's ``infer_cube(want_logits=True)`` writes its logits into one reused buffer of
-    members x chunk x K floats, and one ``cmlpl_ensemble`` follows.  Every window shape ``infer_supported`` accepts, the
-    by-patches path included.  Asynchronous."""
-    groups, M = _groups(nets)
-    members = []
-    for e, k in groups:
-        members += [(e[0], 0), (e[0], 1)] if k == 2 else [e]
-    if not (cube.is_cuda and cube.dim() == 3):
-        raise ValueError("cube: need contiguous float32 cuda tensor [rows, cols, C]")
-    rows, cols, _ = cube.shape
-    n = rows * cols - pixel0 if n is None else int(n)
-    if pixel0 < 0 or n < 1 or pixel0 + n > rows * cols:
-        raise ValueError("pixel range outside the scene")
-    K = _nets_buffers(members[0])[0].K
-    cw = _weights(weights, M)
-    lib, dev = _lib.load(), cube.device
-    chunk = max(8, min(int(chunk), n))
-    res = _alloc(n, K, dev, probs, conf, entropy, disagree)
-    buf = torch.empty(M * chunk * K, dtype=torch.float32, device=dev)
-    own = torch.empty(chunk, dtype=torch.int64, device=dev)            # a member's own argmax: written, not used
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    for o in range(0, n, chunk):
-        m = min(chunk, n - o)
-        z = buf[:M * m * K].view(M, m, K)
-        for k, net in enumerate(members):
-            infer_cube(net, cube, spectra, pixel0 + o, m, chunk=chunk, want_logits=True, out=(own[:m], z[k]))
-        _launch(lib, z.data_ptr(), M, m * K, cw, m, K, res, o, st)
-    return res
+    """The ensemble of ``nets`` (see ``_groups``) on pixels pixel0 .. pixel0 + n - 1 of the scene (default: all of it).
+    Every window shape ``infer_supported`` accepts, the by-patches path included.  Asynchronous."""
+    return _ensemble(nets, cube, spectra, _Range(pixel0, n), None, chunk, weights, (probs, conf, entropy, disagree))
 
 
 @torch.no_grad()
@@ -144,47 +146,5 @@ def ensemble_pixels(nets, cube: torch.Tensor, spectra: torch.Tensor, pix: torch.
     item i's spectrum is row ``spec_rows[i]`` of ``spectra``, or row i).  ``(engine, None)`` yields both networks in one
     forward launch chain; a list may hold several such entries (``[(eng, None), (eng.teacher, None)]``: four members).
     ``check``: one synchronising range check of the lists, as in ``infer_pixels``.  Asynchronous otherwise."""
-    groups, M = _groups(nets)
-    if not (cube.is_cuda and cube.dtype == torch.float32 and cube.is_contiguous() and cube.dim() == 3):
-        raise ValueError("cube: need contiguous float32 cuda tensor [rows, cols, C]")
-    rows, cols, Cc = cube.shape
-    if not (spectra.is_cuda and spectra.dtype == torch.float32 and spectra.is_contiguous() and spectra.dim() == 2):
-        raise ValueError("spectra: need contiguous float32 cuda tensor [., bands]")
-    bufs = [_nets_buffers(e) for e, _ in groups]
-    cs = bufs[0][0]
-    for b in bufs:
-        if (b[0].C, b[0].H, b[0].W, b[0].bands, b[0].K) != (cs.C, cs.H, cs.W, cs.bands, cs.K):
-            raise ValueError("the networks differ in shape")
-    if Cc != cs.C or spectra.shape[1] != cs.bands:
-        raise ValueError(f"cube has {Cc} channels / spectra {spectra.shape[1]} bands, the network wants {cs.C} / {cs.bands}")
-    if check:
-        check_pixel_list(pix, rows * cols)
-        if spec_rows is not None:
-            check_pixel_list(spec_rows, spectra.shape[0], "spec_rows")
-    n = pix.numel()
-    if (spec_rows is not None and spec_rows.numel() != n) or (spec_rows is None and spectra.shape[0] < n):
-        raise ValueError("spectra / spec_rows do not cover the pixel list")
-    K = cs.K
-    cw = _weights(weights, M)
-    lib, dev = _lib.load(), cube.device
-    chunk = max(8, min(int(chunk), n))
-    res = _alloc(n, K, dev, probs, conf, entropy, disagree)
-    buf = torch.empty(M * chunk * K, dtype=torch.float32, device=dev)
-    own = torch.empty(2 * chunk, dtype=torch.int64, device=dev)        # the members' own argmax: written, not used
-    wss = []
-    for b in bufs:
-        need = lib.cmlpl_eval_workspace_bytes(C.byref(b[0]), b[1], chunk)
-        wss.append(torch.empty(need, dtype=torch.uint8, device=dev) if need else None)      # None: windows go by patches
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    for o in range(0, n, chunk):
-        m = min(chunk, n - o)
-        z = buf[:M * m * K].view(M, m, K)
-        k = 0
-        for (bcs, nn, flat, pstride, packed, kstride, _), ws in zip(bufs, wss):
-            _infer_pixels_into(lib, bcs, nn, flat, pstride, packed, kstride, cube,
-                               spectra if spec_rows is not None else spectra[o:o + m],
-                               None if spec_rows is None else spec_rows[o:o + m], pix[o:o + m],
-                               own[:nn * m].view(nn, m), z[k:k + nn], ws, chunk)
-            k += nn
-        _launch(lib, z.data_ptr(), M, m * K, cw, m, K, res, o, st)
-    return res
+    return _ensemble(nets, cube, spectra, _List(pix, spec_rows, check), None, chunk, weights,
+                     (probs, conf, entropy, disagree))

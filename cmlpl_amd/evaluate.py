@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .infer import _infer_pixels_into, _nets_buffers, check_pixel_list
+from .infer import _check_feed, _check_scene, _Forward, _List, _nets_buffers, _predict
 
 
 class Evaluator:
@@ -31,19 +31,10 @@ class Evaluator:
         self.lib = _lib.load()
         self.shape = shape
         self.cshape = _lib.Shape(shape.C, shape.H, shape.W, shape.bands, shape.K)
-        if not (cube.is_cuda and cube.dtype == torch.float32 and cube.is_contiguous() and cube.dim() == 3
-                and cube.shape[2] == shape.C):
-            raise ValueError("cube: need contiguous float32 cuda tensor [rows, cols, C]")
-        if not (spectra.is_cuda and spectra.dtype == torch.float32 and spectra.is_contiguous() and spectra.dim() == 2
-                and spectra.shape[1] == shape.bands):
-            raise ValueError("spectra: need contiguous float32 cuda tensor [., bands]")
+        _check_scene(cube, spectra, self.cshape)
         rows, cols, _ = cube.shape
-        check_pixel_list(pix, rows * cols)
-        n = pix.numel()
-        if spec_rows is not None:
-            check_pixel_list(spec_rows, spectra.shape[0], "spec_rows")
-        if (spec_rows is not None and spec_rows.numel() != n) or (spec_rows is None and spectra.shape[0] < n):
-            raise ValueError("spectra / spec_rows do not cover the pixel list")
+        feed = _List(pix, spec_rows, True)
+        n = _check_feed(cube, spectra, feed)
         if not (truth.is_cuda and truth.dtype == torch.int64 and truth.is_contiguous() and tuple(truth.shape) == (n,)):
             raise ValueError("truth: need contiguous int64 cuda vector, one label per list entry")
         if rows < shape.H // 2 or cols < shape.W // 2:
@@ -54,9 +45,7 @@ class Evaluator:
         self.labels = torch.empty(2, n, dtype=torch.int64, device=dev)
         self.cm = torch.zeros(2, K, K, dtype=torch.int64, device=dev)
         self.ignored = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.chunk = max(8, min(int(chunk), n))
-        need = self.lib.cmlpl_eval_workspace_bytes(C.byref(self.cshape), 2, self.chunk)
-        self.ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None     # None: windows go by patches
+        self.fwd = _Forward(self.lib, self.cshape, 2, cube, spectra, feed, n, chunk)
         self.logits = self.ens_labels = self.cm_ens = None       # evaluate(ensemble=True) creates them at its first call
 
     @torch.no_grad()
@@ -68,7 +57,8 @@ class Evaluator:
         ``ensemble``: [nets + 1, K, K] -- the same matrices, then the one of the networks' equally weighted ensemble
         (``cmlpl_ensemble`` over the logits of the same forward: the label of the averaged softmax, first maximum).  Its
         buffers (the logits, the ensemble's labels, the matrices) are created at the first such call."""
-        cs, nn, flat, pstride, packed, kstride, _ = _nets_buffers(nets)
+        group = _nets_buffers(nets)
+        cs, nn = group[0], group[1]
         if (cs.C, cs.H, cs.W, cs.bands, cs.K) != tuple(getattr(self.cshape, k) for k in ("C", "H", "W", "bands", "K")):
             raise ValueError("the networks' shape is not the registered split's")
         labels = self.labels[:nn]
@@ -80,8 +70,7 @@ class Evaluator:
                 self.ens_labels = torch.empty(self.n, dtype=torch.int64, device=dev)
                 self.cm_ens = torch.zeros(3, cs.K, cs.K, dtype=torch.int64, device=dev)
             logits = self.logits.view(-1)[:nn * self.n * cs.K].view(nn, self.n, cs.K)
-        _infer_pixels_into(self.lib, cs, nn, flat, pstride, packed, kstride, self.cube, self.spectra, self.spec_rows,
-                           self.pix, labels, logits, self.ws, self.chunk)
+        _predict(self.fwd, [group], [None], self.n, labels, logits)
         cm = self.cm_ens[:nn + 1] if ensemble else self.cm[:nn]
         cm.zero_()
         self.ignored.zero_()

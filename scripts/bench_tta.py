@@ -6,7 +6,8 @@ B2 on a synthetic scene of --scene pixels (PaviaU's 610 x 340 by default), media
     noise while it stages its slab) against one clean ``infer_cube``, the two taken in turn; milliseconds per scene;
   * ``tta_cube`` of two networks x (1 + --views) views against ``ensemble_cube`` of the pair, in turn;
   * ``cmlpl_ensemble_views`` alone at 207,400 x 9 for 2 x (1 + --views) blocks against ``cmlpl_ensemble`` for 2, between
-    event pairs: a burst of launches per pair, microseconds per launch.
+    event pairs: a burst of launches per pair, microseconds per launch; and ``cmlpl_ensemble_views`` at ONE view against
+    ``cmlpl_ensemble`` for 2 and for 4 members, in turn.
 `--parent DIR` (a checkout of the parent commit with its own built library): plain `bench.py --gpus 1` and
 `scripts/bench_infer.py` there and here, in alternation, `--bench-reps` times each -- this tree's median must lie inside
 the parent's own min .. max.  One JSON line."""
@@ -73,6 +74,25 @@ def launches_alone(n, K, views, pairs=20, burst=50):
         moved = 4 * n * K * (blocks + 1) + n * (8 + 4 + 4 + 4)
         res[name + "_us"] = dict(spread(us), blocks=blocks, pixels=n, classes=K, bytes_moved=moved,
                                  gb_per_s_at_median=moved / (statistics.median(us) * 1e-6) / 1e9)
+    # may the views kernel at ONE view stand in for cmlpl_ensemble?  The two in turn, for 2 and 4 members; its median must
+    # lie inside cmlpl_ensemble's own min .. max
+    z4 = (4 * torch.randn(4, n, K, generator=g)).to(DEV)
+    for M in (2, 4):
+        def plain_M():
+            for _ in range(burst):
+                _lib.check("cmlpl_ensemble", lib.cmlpl_ensemble(z4.data_ptr(), M, n * K, None, n, K, *out))
+
+        def one_view_M():
+            for _ in range(burst):
+                _lib.check("cmlpl_ensemble_views", lib.cmlpl_ensemble_views(z4.data_ptr(), M, 1, n * K, n * K, None, n, K, *out))
+        us = {"ensemble": [], "ensemble_views_one_view": []}
+        plain_M(), one_view_M()
+        for _ in range(pairs):
+            for name, fn in (("ensemble", plain_M), ("ensemble_views_one_view", one_view_M)):
+                us[name] += [t / burst * 1e3 for t in timed(fn, 1, warm=0)]
+        r = {k: spread(v) for k, v in us.items()}
+        r["inside_ensembles_spread"] = bool(r["ensemble"]["min"] <= r["ensemble_views_one_view"]["median"] <= r["ensemble"]["max"])
+        res["one_view_%d_members_us" % M] = r
     return res
 
 

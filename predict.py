@@ -73,7 +73,6 @@ def main(args, device=None):
         if os.path.exists(whole.root + 'test_array.npy') and os.path.exists(whole.root + 'Y.npy'):
             test_array = np.load(whole.root + 'test_array.npy')
             Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
-    both = args.net in ('both', 'ema_both')
     which = {'both': [0, 1], 'ema_both': ['ema0', 'ema1'], **ENSEMBLES}.get(args.net) or \
         [args.net if args.net.startswith('ema') else int(args.net)]
     if any(str(k).startswith('ema') for k in which) and ("Teacher" not in ck or "Teacher1" not in ck):
@@ -82,39 +81,27 @@ def main(args, device=None):
     keys = {0: "Base", 1: "Base1", 'ema0': "Teacher", 'ema1': "Teacher1"}
     extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
     common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
+    members = [(k, ck[keys[k]]) for k in which]
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
         tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
                   clean=not args.tta_no_clean)
-        out = tta_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device, tta, **common, **extras)
-        save_extras(args, out)
-        if args.out:
-            np.save(args.out, out["labels"])
-        return out["labels"]
-    if args.net in ENSEMBLES:
-        ens = ensemble_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device, **common, **extras)
-        save_extras(args, ens)
-        if args.out:
-            np.save(args.out, ens["labels"])
-        return ens["labels"]
-    preds = evaluate_whole(shape, whole, [(k, ck[keys[k]]) for k in which], device,
-                           synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"],
-                           val_batch_size=args.val_batch_size, test_array=test_array, Y_test=Y_test)
-    labels = np.stack([preds[k] for k in which]).astype(np.int64)
-    labels = labels if both else labels[0]
-    if any(extras.values()):
+        out = tta_whole(shape, whole, members, device, tta, **common, **extras)
+    elif args.net in ENSEMBLES:
+        out = ensemble_whole(shape, whole, members, device, **common, **extras)
+    else:
+        preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
+        labels = np.stack([preds[k] for k in which]).astype(np.int64)
         # the network's own softmax: a one-member ensemble, silent (the Result: lines above are the argmax of its logits)
-        save_extras(args, ensemble_whole(shape, whole, [(which[0], ck[keys[which[0]]])], device, **dict(common, test_array=None),
-                                         **extras))
-    if args.out:
-        np.save(args.out, labels)
-    return labels
-
-
-def save_extras(args, ens):
+        out = ensemble_whole(shape, whole, members[:1], device, **dict(common, test_array=None), **extras) \
+            if any(extras.values()) else {}
+        out["labels"] = labels if args.net in ('both', 'ema_both') else labels[0]
     for path, key in ((args.proba, "probs"), (args.confidence, "conf"), (args.entropy, "entropy")):
         if path:
-            np.save(path, ens[key])
+            np.save(path, out[key])
+    if args.out:
+        np.save(args.out, out["labels"])
+    return out["labels"]
 
 
 def build_parser():

@@ -43,7 +43,7 @@ import time
 import numpy as np
 import torch
 
-from cmlpl_amd import HyperParams, NetShape
+from cmlpl_amd import HyperParams, NetShape, checkpoint
 from hsi_loader import HSIDataSet, SyntheticHSIDataSet, SyntheticScene
 from tools.hyper_tools import CalAccuracy, test_whole
 from tools.models import BaseNet2
@@ -99,21 +99,13 @@ def run_record(args, hp, shape, from_scene):
     schedule adap_thr(epoch) divides by it), the batch sizes and the data.  --graph, --windows, --eval_every,
     --print_per_batches and the number of GPUs may differ."""
     rec = {k: getattr(args, k) for k in RUN_FLAGS}
-    if run_method(args) != "cmlpl":       # (a CMLPL run's record is what it was before there was a second method)
-        rec["method"] = run_method(args)
-    if run_ema(args):                     # (and a run without a teacher's is what it was before there was one)
+    if args.method != "cmlpl":            # (a CMLPL run's record is what it was before there was a second method)
+        rec["method"] = args.method
+    if args.ema:                          # (and a run without a teacher's is what it was before there was one)
         rec.update(ema=True, teacher_alpha=args.teacher_alpha)
     rec.update(shape=[int(v) for v in shape], data=("synthetic %s%s" % (args.synthetic, " scene" if from_scene else ""))
                if args.synthetic else "dataID %d" % int(args.dataID))
     return rec
-
-
-def run_method(args):
-    return getattr(args, "method", "cmlpl")
-
-
-def run_ema(args):
-    return bool(getattr(args, "ema", False))
 
 
 def saved_args(args):
@@ -128,13 +120,49 @@ def run_differences(saved, mine):
     return ["%s: file %r, here %r" % (k, saved.get(k), mine.get(k)) for k in keys if saved.get(k) != mine.get(k)]
 
 
+class EvalCurve:
+    """One validation curve of --eval_every: the epochs that were scored, a row per evaluation and its confusion matrices.
+    ``nets`` = 2: a row is [net][OA, AA, Kappa] and the matrices are [2, K, K] (the two networks, suffix ''; their EMA
+    teachers, '_ema'); ``nets`` = None: a row is [OA, AA, Kappa] and the matrix [K, K] (the pair together, '_ens').  The
+    suffix names the curve in a checkpoint's ``extra``, in --save_eval and on the printed lines."""
+
+    def __init__(self, suffix, nets):
+        self.suffix, self.nets, self.epochs, self.rows, self.cms = suffix, nets, [], [], []
+
+    def add(self, epoch, row, cm):
+        self.epochs.append(epoch)
+        self.rows.append(row)
+        self.cms.append(cm)
+
+    def restore(self, extra):
+        """the curve so far, from a checkpoint's ``extra``; a file without this curve leaves it empty"""
+        if "eval_curve" + self.suffix in extra:
+            self.epochs = [int(e) for e in extra["eval_epochs" + self.suffix]]
+            self.rows = extra["eval_curve" + self.suffix].tolist()
+            self.cms = list(extra["eval_cms" + self.suffix].numpy())
+
+    def checkpoint_entries(self, num_classes):
+        """eval_epochs / eval_curve (float64 [E, nets, 3]) / eval_cms (int64 [E, nets, K, K]); no ``nets`` axis for the pair"""
+        per = () if self.nets is None else (self.nets,)
+        return {"eval_epochs" + self.suffix: list(self.epochs),
+                "eval_curve" + self.suffix: torch.tensor(self.rows, dtype=torch.float64).reshape(len(self.epochs), *per, 3),
+                "eval_cms" + self.suffix: torch.from_numpy(np.stack(self.cms)) if self.cms else
+                torch.zeros(0, *per, num_classes, num_classes, dtype=torch.int64)}
+
+    def npz_entries(self):
+        """the members of --save_eval, in the order the file has had them (the first curve's differs from the later two's)"""
+        members = dict(curve=np.array(self.rows), cm=np.stack(self.cms), epochs=np.array(self.epochs))
+        return {k + self.suffix: members[k] for k in (("curve", "cm", "epochs") if self.suffix else ("curve", "epochs", "cm"))}
+
+    def best_line(self, net=None):
+        """the ``best validation`` line of network ``net``: the epoch and the OA of its best-scored evaluation (the first of equal bests)"""
+        oa = np.array(self.rows)[..., 0] if net is None else np.array(self.rows)[:, net, 0]
+        return 'best validation%s%s: epoch %d OA = %.2f' % (self.suffix, NET_TAGS[net or 0], self.epochs[int(np.argmax(oa))], oa.max() * 100)
+
+
 NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
             'ens': '_ens',                                         # ensemble_whole: several of them together
             'tta': '_tta'}                                         # tta_whole: over noisy views of every pixel
-
-
-def run_ensemble(args):
-    return bool(getattr(args, "ensemble", False))
 
 
 def print_result(tag, pred, test_array, Y_test):
@@ -146,6 +174,43 @@ def print_result(tag, pred, test_array, Y_test):
     return OA
 
 
+def scene_source(shape, whole, device, synthetic, dataID, resident_cube):
+    """the scene as a ``CubeSource`` for the cube-fed forward, or None: a window shape the per-sample forward does not
+    take, or a dataset directory without its cube.  ``resident_cube``: the scene already on the device."""
+    from cmlpl_amd.infer import infer_supported
+    if not infer_supported(NetShape(*shape)):
+        return None
+    if synthetic:      # (a SyntheticScene is its own scene; a directory without scene.json looks its scene up by dataID)
+        return whole.cube_source(device, resident_cube=resident_cube)
+    return whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
+
+
+def build_nets(shape, nets, device, dropout):
+    """the ``BaseNet2`` modules of ``nets`` = [(key, state_dict)], on ``device``, in that order"""
+    models = [BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
+                       window=shape[1]).to(device) for _ in nets]
+    for model, (_, sd) in zip(models, nets):
+        model.load_state_dict(sd)
+    return models
+
+
+def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube):
+    """the body of ``ensemble_whole`` and ``tta_whole``: ``predict(models, cube, spectra)`` is the library call, ``timing`` its
+    printed line (a format of the seconds and the number of networks), ``tag`` that of its ``Result:`` lines, ``noun`` who asks"""
+    source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
+    if source is None:
+        raise SystemExit("%s needs the scene cube (cube.npy + scene.json in the dataset directory, "
+                         "sample_generation.py) and a square window" % noun)
+    models = [model.eval() for model in build_nets(shape, nets, device, dropout)]
+    t1 = time.time()
+    res = predict(models, source.cube, source.spectra)
+    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
+    print(timing % (time.time() - t1, len(models)))
+    if test_array is not None:
+        print_result(tag, out["labels"], test_array, Y_test)
+    return out
+
+
 def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
                    resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
     """Whole-image ENSEMBLE of ``nets`` = [(key, state_dict)] (1..4 networks, ``evaluate_whole``'s list): the label of their
@@ -155,27 +220,10 @@ def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
     not asked for is absent) and prints the ``Result:`` lines with the tag ``_ens`` when the test pixels are given.  It
     needs the scene as its cube: there is no loader fall-back."""
     from cmlpl_amd.ensemble import ensemble_cube
-    from cmlpl_amd.infer import infer_supported
-    source = None
-    if infer_supported(NetShape(*shape)):
-        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
-            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
-    if source is None:
-        raise SystemExit("the ensemble needs the scene cube (cube.npy + scene.json in the dataset directory, "
-                         "sample_generation.py) and a square window")
-    models = []
-    for _, sd in nets:
-        model = BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
-                         window=shape[1]).to(device)
-        model.load_state_dict(sd)
-        models.append(model.eval())
-    t1 = time.time()
-    res = ensemble_cube(models, source.cube, source.spectra, weights=weights, probs=probs, conf=conf, entropy=entropy)
-    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
-    print('ensemble inference time == %.3f s (%d networks)' % (time.time() - t1, len(models)))
-    if test_array is not None:
-        print_result(NET_TAGS['ens'], out["labels"], test_array, Y_test)
-    return out
+    return together_whole(
+        lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=probs, conf=conf, entropy=entropy),
+        'ensemble inference time == %.3f s (%d networks)', NET_TAGS['ens'], "the ensemble",
+        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
 
 
 def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
@@ -183,36 +231,18 @@ def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout
     """``ensemble_whole`` over the noisy views of ``tta`` (cmlpl_amd.tta.TTA): every network of ``nets`` scores every view
     of every scene pixel, one label map from the average of all their softmaxes (cmlpl_amd.tta.tta_cube).  Same returns;
     the ``Result:`` lines carry the tag ``_tta``."""
-    from cmlpl_amd.infer import infer_supported
     from cmlpl_amd.tta import tta_cube
-    source = None
-    if infer_supported(NetShape(*shape)):
-        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
-            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
-    if source is None:
-        raise SystemExit("test-time augmentation needs the scene cube (cube.npy + scene.json in the dataset directory, "
-                         "sample_generation.py) and a square window")
-    models = []
-    for _, sd in nets:
-        model = BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
-                         window=shape[1]).to(device)
-        model.load_state_dict(sd)
-        models.append(model.eval())
-    t1 = time.time()
-    res = tta_cube(models, source.cube, source.spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy)
-    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
-    print('tta inference time == %.3f s (%d networks x %d views%s, noise %g)' %
-          (time.time() - t1, len(models), tta.views, ' + the clean window' if tta.clean else '', tta.sigma))
-    if test_array is not None:
-        print_result(NET_TAGS['tta'], out["labels"], test_array, Y_test)
-    return out
+    return together_whole(
+        lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy),
+        'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g)' %
+        (tta.views, ' + the clean window' if tta.clean else '', tta.sigma), NET_TAGS['tta'], "test-time augmentation",
+        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
 
 
 def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
                    test_array=None, Y_test=None, resident_cube=None, last_eval=None):
-    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index -- or 'ema0' / 'ema1', a
-    network's EMA teacher --, state_dict)]: the end of a
-    training run, and all of predict.py.  Returns {network index: int64 label per scene pixel}.
+    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index -- or 'ema0' / 'ema1', a network's
+    EMA teacher --, state_dict)]: the end of a training run, and all of predict.py.  Returns {network index: int64 label per scene pixel}.
     The scene stays in HBM as its cube and the forward gathers the windows itself (cmlpl_infer_cube): no 19.9 GB patch
     tensor, no DataLoader (train.py:291-294 streams the materialised patches).  Window shapes the per-sample forward does
     not take, or a dataset directory without the cube, fall back to the loader.  The source is built ONCE for all
@@ -220,18 +250,12 @@ def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
     ``test_array`` / ``Y_test``: the labelled test pixels and their classes -- the ``Result:`` lines are printed when
     they are given.  ``resident_cube``: the scene already on the device (a cube-fed run evaluates on the cube it trained
     from).  ``last_eval``: the [net][OA, AA, Kappa] row of --eval_every when it scored the same parameters."""
-    from cmlpl_amd.infer import infer_supported
-    num_features, num_classes = shape[3], shape[4]
     t_src = time.time()
-    source = None
-    if infer_supported(NetShape(*shape)):
-        source = whole.cube_source(device, resident_cube=resident_cube) if synthetic else \
-            whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
+    source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
     if source is None:
         if synthetic:      # (cut the scene's windows on the device, then the reference's loader path)
             from cmlpl_amd.patches import extract_patches
-            cs = whole.cube_source(device)
-            XPw = extract_patches(cs.cube, torch.arange(len(whole), device=device), shape[1]).cpu()
+            XPw = extract_patches(whole.cube_source(device).cube, torch.arange(len(whole), device=device), shape[1]).cpu()
             source = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(XPw, whole.X),
                                                  batch_size=val_batch_size, shuffle=False)
         else:
@@ -240,10 +264,7 @@ def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
         torch.cuda.synchronize()
     print('evaluation source ready in %.3f s' % (time.time() - t_src))
     preds = {}
-    for net, sd in nets:
-        model = BaseNet2(num_features=num_features, dropout=dropout, num_classes=num_classes,
-                         in_channels=shape[0], window=shape[1]).to(device)
-        model.load_state_dict(sd)
+    for (net, _), model in zip(nets, build_nets(shape, nets, device, dropout)):      # (test_whole sets .eval() itself)
         t1 = time.time()
         pred = preds[net] = test_whole(model, source, print_per_batches=10 ** 9)
         print('inference time == %.3f s' % (time.time() - t1))
@@ -259,170 +280,171 @@ def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
     return preds
 
 
-def main(args, make_engine=None, device=None):
-    """``make_engine`` / ``device`` are test hooks (tests/test_train_loop_gloo.py runs this loop as two gloo ranks
-    on CPU around a stand-in engine); the product path leaves them None."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    method = run_method(args)
-    if method != "cmlpl" and world > 1:      # before any device or communicator work
-        raise SystemExit(f"--method {method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
-                         f"{world} ranks)")
-    if run_ema(args) and world > 1:
-        raise SystemExit(f"--ema runs on one GPU: the sharded engine keeps no EMA teacher (this job has {world} ranks)")
-    if device is None:
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-        torch.cuda.set_device(device)
-    torch.manual_seed(1088)                                         # seed_torch(), train.py:50-58
-    cube_fed = args.windows == 'cube'
+def load_data(run, args):
     if args.synthetic:
-        shape = SYNTH[args.synthetic]
-        num_classes, num_features = shape[4], shape[3]
+        run.shape = shape = SYNTH[args.synthetic]
         # (--windows cube / --synthetic_scene: both splits are seeded pixels of ONE synthetic scene, the evaluation's)
-        from_scene = cube_fed or args.synthetic_scene
-        whole = SyntheticScene(shape, 64, 64, seed=3) if (from_scene or not args.no_eval or args.eval_every > 0) else None   # a 64 x 64 scene cube, every pixel a test pixel
-        labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=whole if from_scene else None)
-        unlabeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'unlabel', seed=2, scene=whole if from_scene else None)
+        run.from_scene = args.windows == 'cube' or args.synthetic_scene
+        if run.from_scene or not args.no_eval or args.eval_every > 0:
+            run.whole = SyntheticScene(shape, 64, 64, seed=3)       # a 64 x 64 scene cube, every pixel a test pixel
+        scene = run.whole if run.from_scene else None
+        run.labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=scene)
+        run.unlabeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'unlabel', seed=2, scene=scene)
         if not args.no_eval:
-            Y_test, test_array = whole.Y.numpy(), np.arange(len(whole))
+            run.Y_test, run.test_array = run.whole.Y.numpy(), np.arange(len(run.whole))
     else:
-        from_scene = False
         num_classes, num_features = DATASETS[int(args.dataID)]
-        labeled = HSIDataSet(int(args.dataID), 'label', max_iters=args.num_unlabel)
-        unlabeled = HSIDataSet(int(args.dataID), 'unlabel', max_iters=args.num_unlabel, num_unlabel=args.num_unlabel)
+        run.labeled = labeled = HSIDataSet(int(args.dataID), 'label', max_iters=args.num_unlabel)
+        run.unlabeled = HSIDataSet(int(args.dataID), 'unlabel', max_iters=args.num_unlabel, num_unlabel=args.num_unlabel)
         if not args.no_eval:
-            whole = HSIDataSet(int(args.dataID), 'wholeset')
-            test_array = np.load(labeled.root + 'test_array.npy')
-            Y_test = (np.load(labeled.root + 'Y.npy') - 1)[test_array]
-        shape = (labeled.XP.shape[1], labeled.XP.shape[2], labeled.XP.shape[3], num_features, num_classes)
+            run.whole = HSIDataSet(int(args.dataID), 'wholeset')
+            run.test_array = np.load(labeled.root + 'test_array.npy')
+            run.Y_test = (np.load(labeled.root + 'Y.npy') - 1)[run.test_array]
+        run.shape = (labeled.XP.shape[1], labeled.XP.shape[2], labeled.XP.shape[3], num_features, num_classes)
 
-    hp = HyperParams(lr=args.lr, num_epochs=args.num_epochs, thr=args.thr, alpha=args.alpha,
-                     queue_batch=args.queue_batch, temperature=args.temperature, dropout=args.dropout,
-                     noise=args.noise)
-    bt, btu = args.labeled_batch_size, args.unlabeled_batch_size
-    ppb = args.print_per_batches
+
+def build_engine(run, args, make_engine):
+    world, device, bt, btu, ppb = run.world, run.device, run.bt, run.btu, args.print_per_batches
+    run.hp = hp = HyperParams(lr=args.lr, num_epochs=args.num_epochs, thr=args.thr, alpha=args.alpha, queue_batch=args.queue_batch,
+                              temperature=args.temperature, dropout=args.dropout, noise=args.noise)
     if world > 1 and (bt % world or btu % world):
         raise SystemExit(f"--labeled_batch_size {bt} / --unlabeled_batch_size {btu} must be multiples of the "
                          f"number of GPUs ({world}): the batch is sharded equally by sample")
     if make_engine is not None:
-        eng = make_engine(NetShape(*shape), bt // world, btu // world, hp, ppb)
+        run.eng = make_engine(NetShape(*run.shape), bt // world, btu // world, hp, ppb)
     elif world > 1:
         from cmlpl_amd.distributed import DistTrainEngine, init_distributed
-        dist = init_distributed("nccl", device)      # checked start-up: one device per local rank, no silent hang
-        eng = DistTrainEngine(NetShape(*shape), bt // world, btu // world, hp, device=device, seed=1088, hist_rows=ppb)
+        init_distributed("nccl", device)             # checked start-up: one device per local rank, no silent hang
+        run.eng = DistTrainEngine(NetShape(*run.shape), bt // world, btu // world, hp, device=device, seed=1088, hist_rows=ppb)
     else:
         from cmlpl_amd import TrainEngine
-        eng = TrainEngine(NetShape(*shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=method,
-                          teacher_alpha=args.teacher_alpha if run_ema(args) else None)
-    eng.init_params_default(1088)
+        run.eng = TrainEngine(NetShape(*run.shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=args.method,
+                              teacher_alpha=args.teacher_alpha if args.ema else None)
+    run.eng.init_params_default(1088)
 
-    gen = torch.Generator().manual_seed(1088)                        # same permutations on every rank
-    if args.save_best and args.eval_every <= 0:
-        raise SystemExit("--save_best keeps the best-VALIDATED epoch: it needs --eval_every")
-    if args.ckpt_every > 0 and not args.save_ckpt:
-        raise SystemExit("--ckpt_every needs --save_ckpt PATH")
-    resumed = None
-    if args.resume:
-        # every rank reads the same file (the state is replicated); what the file was trained with must be what this
-        # run would train with -- the engine checks its own identity record, the flags are compared here
-        from cmlpl_amd import checkpoint
-        resumed = checkpoint.load(args.resume)
-        file_method = checkpoint.identity_method(resumed["identity"])
-        if file_method != method:
-            raise SystemExit("--resume %s: the file was written by --method %s, this run is --method %s" %
-                             (args.resume, file_method, method))
-        diff = run_differences(resumed["extra"].get("run", {}), run_record(args, hp, shape, from_scene))
-        if diff:
-            raise SystemExit("--resume %s: this run differs from the one that wrote the file -- %s" % (args.resume, "; ".join(diff)))
-        try:
-            eng.load_checkpoint_state(resumed)
-        except ValueError as e:
-            raise SystemExit("--resume %s: %s" % (args.resume, e))
-        gen.set_state(resumed["extra"]["gen_state"])
-    cube_kw = {}
-    if cube_fed:
+
+def open_resume(run, args):
+    # every rank reads the same file (the state is replicated); what the file was trained with must be what this
+    # run would train with -- the engine checks its own identity record, the flags are compared here
+    run.resumed = resumed = checkpoint.load(args.resume)
+    file_method = checkpoint.identity_method(resumed["identity"])
+    if file_method != args.method:
+        raise SystemExit("--resume %s: the file was written by --method %s, this run is --method %s" %
+                         (args.resume, file_method, args.method))
+    diff = run_differences(resumed["extra"].get("run", {}), run_record(args, run.hp, run.shape, run.from_scene))
+    if diff:
+        raise SystemExit("--resume %s: this run differs from the one that wrote the file -- %s" % (args.resume, "; ".join(diff)))
+    try:
+        run.eng.load_checkpoint_state(resumed)
+    except ValueError as e:
+        raise SystemExit("--resume %s: %s" % (args.resume, e))
+    run.gen.set_state(resumed["extra"]["gen_state"])
+
+
+def build_loaders(run, args):
+    device, labeled, unlabeled = run.device, run.labeled, run.unlabeled
+    if args.windows == 'cube':
         # the scene goes to the GPU ONCE; a split is its spectra, labels and one scene pixel per row -- no windows
-        if not getattr(eng, "takes_cube", False):
+        if not getattr(run.eng, "takes_cube", False):
             raise SystemExit("--windows cube: this engine has no cube-fed step")
         if labeled.scene_cube is None or unlabeled.scene_cube is None:
             raise SystemExit("--windows cube needs cube.npy + scene.json in the dataset directory (sample_generation.py)")
         cube_dev = torch.from_numpy(np.ascontiguousarray(labeled.scene_cube, dtype=np.float32)).to(device)
         (Xl_, Yl_, lab_pix), (Xu_, Yu_, unl_pix) = labeled.scene_arrays(device), unlabeled.scene_arrays(device)
-        lab_loader = DeviceLoader((None, Xl_, Yl_), bt, gen)
-        unl_loader = DeviceLoader((None, Xu_, Yu_), btu, gen)
-        cube_kw = dict(cube=cube_dev, lab_pix=lab_pix, unl_pix=unl_pix)
+        lab_arrays, unl_arrays = (None, Xl_, Yl_), (None, Xu_, Yu_)
+        run.cube_kw = dict(cube=cube_dev, lab_pix=lab_pix, unl_pix=unl_pix)
     else:
-        lab_loader = DeviceLoader(labeled.device_arrays(device), bt, gen)
-        unl_loader = DeviceLoader(unlabeled.device_arrays(device), btu, gen)
-    evaluator, eval_log, eval_cms = None, [], []          # --eval_every: (epoch, [net][OA, AA, Kappa]) and the matrices
-    ema = run_ema(args)
-    eval_log_ema, eval_cms_ema = [], []                   # --ema: the same two of the teachers, a curve of their own
-    ens = run_ensemble(args)
-    eval_log_ens, eval_cms_ens = [], []                   # --ensemble: (epoch, [OA, AA, Kappa]) and the matrix of the pair
-    if args.eval_every > 0 and rank == 0:
-        # the test split registered once: its pixels, spectra and labels beside the resident cube (rank 0 evaluates, as
-        # after the last epoch; its own generators: no draw of the training streams is consumed)
-        from cmlpl_amd.evaluate import Evaluator
-        if args.synthetic:
-            cube_ev = cube_kw["cube"] if cube_fed else whole.cube.to(device).contiguous()
-            Xt, Yt = whole.X.to(device).contiguous(), whole.Y.to(device).contiguous()
-            pix_t = torch.arange(len(whole), dtype=torch.int64, device=device)
-        else:
-            test_split = HSIDataSet(int(args.dataID), 'test')
-            if test_split.scene_cube is None:
-                raise SystemExit("--eval_every needs cube.npy + scene.json in the dataset directory (sample_generation.py)")
-            cube_ev = cube_kw["cube"] if cube_fed else \
-                torch.from_numpy(np.ascontiguousarray(test_split.scene_cube, dtype=np.float32)).to(device)
-            Xt, Yt, pix_t = test_split.scene_arrays(device)
-        evaluator = Evaluator(NetShape(*shape), cube_ev, Xt, Yt, pix_t)
-    num_batches = min(len(lab_loader), len(unl_loader))              # train.py:134
-    num_steps = args.num_epochs * num_batches                        # train.py:135
-    loss_hist = np.zeros((num_steps, 5))                             # train.py:136
-    start_epoch = 0
-    if resumed is not None:
-        ex = resumed["extra"]
-        start_epoch = int(ex["epoch"])
-        if ex["num_batches"] != num_batches or start_epoch > args.num_epochs:
-            raise SystemExit("--resume %s: the file has %d epochs of %d steps, this run %d epochs of %d" %
-                             (args.resume, start_epoch, ex["num_batches"], args.num_epochs, num_batches))
-        done = start_epoch * num_batches
-        loss_hist[:done] = ex["loss_hist"].numpy()
-        if evaluator is not None:      # (the curve so far: a leg without --eval_every leaves a gap, not an error)
-            eval_log = [(int(e), [[float(v) for v in net] for net in row]) for e, row in zip(ex["eval_epochs"], ex["eval_curve"].tolist())]
-            eval_cms = [cm for cm in ex["eval_cms"].numpy()]
-            if ema and "eval_curve_ema" in ex:
-                eval_log_ema = [(int(e), [[float(v) for v in net] for net in row])
-                                for e, row in zip(ex["eval_epochs_ema"], ex["eval_curve_ema"].tolist())]
-                eval_cms_ema = [cm for cm in ex["eval_cms_ema"].numpy()]
-            if ens and "eval_curve_ens" in ex:
-                eval_log_ens = [(int(e), [float(v) for v in row])
-                                for e, row in zip(ex["eval_epochs_ens"], ex["eval_curve_ens"].tolist())]
-                eval_cms_ens = [cm for cm in ex["eval_cms_ens"].numpy()]
-    index_i = start_epoch * num_batches - 1
-    best_oa, best_state, best_extra = None, None, None               # --save_best
-    if eval_log:
-        best_oa = max(row[0][0] for _, row in eval_log)
+        lab_arrays, unl_arrays = labeled.device_arrays(device), unlabeled.device_arrays(device)
+    run.lab_loader, run.unl_loader = DeviceLoader(lab_arrays, run.bt, run.gen), DeviceLoader(unl_arrays, run.btu, run.gen)
+    run.num_batches = min(len(run.lab_loader), len(run.unl_loader))  # train.py:134
+    run.loss_hist = np.zeros((args.num_epochs * run.num_batches, 5))  # train.py:135-136
 
-    def run_extra(epochs_done):
-        """what this driver adds to a checkpoint written after ``epochs_done`` epochs"""
-        done = epochs_done * num_batches
-        more = {}
-        if ema:
-            more = dict(eval_epochs_ema=[e for e, _ in eval_log_ema],
-                        eval_curve_ema=torch.tensor([r for _, r in eval_log_ema], dtype=torch.float64).reshape(len(eval_log_ema), 2, 3),
-                        eval_cms_ema=torch.from_numpy(np.stack(eval_cms_ema)) if eval_cms_ema else
-                        torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64))
-        if ens:
-            more.update(eval_epochs_ens=[e for e, _ in eval_log_ens],
-                        eval_curve_ens=torch.tensor([r for _, r in eval_log_ens], dtype=torch.float64).reshape(len(eval_log_ens), 3),
-                        eval_cms_ens=torch.from_numpy(np.stack(eval_cms_ens)) if eval_cms_ens else
-                        torch.zeros(0, num_classes, num_classes, dtype=torch.int64))
-        return dict(epoch=epochs_done, num_batches=num_batches, loss_hist=torch.from_numpy(loss_hist[:done].copy()),
-                    eval_epochs=[e for e, _ in eval_log],
-                    eval_curve=torch.tensor([r for _, r in eval_log], dtype=torch.float64).reshape(len(eval_log), 2, 3),
-                    eval_cms=torch.from_numpy(np.stack(eval_cms)) if eval_cms else torch.zeros(0, 2, num_classes, num_classes, dtype=torch.int64),
-                    gen_state=gen.get_state(), args=saved_args(args),
-                    run=run_record(args, hp, shape, from_scene), world=world, **more)
+
+def build_evaluator(run, args):
+    # the test split registered once: its pixels, spectra and labels beside the resident cube (rank 0 evaluates, as
+    # after the last epoch; its own generators: no draw of the training streams is consumed)
+    from cmlpl_amd.evaluate import Evaluator
+    device, whole, cube_fed = run.device, run.whole, args.windows == 'cube'
+    if args.synthetic:
+        cube_ev = run.cube_kw["cube"] if cube_fed else whole.cube.to(device).contiguous()
+        Xt, Yt = whole.X.to(device).contiguous(), whole.Y.to(device).contiguous()
+        pix_t = torch.arange(len(whole), dtype=torch.int64, device=device)
+    else:
+        test_split = HSIDataSet(int(args.dataID), 'test')
+        if test_split.scene_cube is None:
+            raise SystemExit("--eval_every needs cube.npy + scene.json in the dataset directory (sample_generation.py)")
+        cube_ev = run.cube_kw["cube"] if cube_fed else \
+            torch.from_numpy(np.ascontiguousarray(test_split.scene_cube, dtype=np.float32)).to(device)
+        Xt, Yt, pix_t = test_split.scene_arrays(device)
+    run.evaluator = Evaluator(NetShape(*run.shape), cube_ev, Xt, Yt, pix_t)
+
+
+def restore_progress(run, args):
+    ex = run.resumed["extra"]
+    run.start_epoch = int(ex["epoch"])
+    if ex["num_batches"] != run.num_batches or run.start_epoch > args.num_epochs:
+        raise SystemExit("--resume %s: the file has %d epochs of %d steps, this run %d epochs of %d" %
+                         (args.resume, run.start_epoch, ex["num_batches"], args.num_epochs, run.num_batches))
+    run.loss_hist[:run.start_epoch * run.num_batches] = ex["loss_hist"].numpy()
+    if run.evaluator is not None:      # (a leg without --eval_every leaves a gap in the curves, not an error)
+        for curve in run.curves.values():
+            curve.restore(ex)
+    if run.curves[''].epochs:          # --save_best: network 0's best validation so far
+        run.best_oa = max(row[0][0] for row in run.curves[''].rows)
+
+
+def run_extra(run, args, epochs_done):
+    """what this driver adds to a checkpoint written after ``epochs_done`` epochs"""
+    first, *later = (curve.checkpoint_entries(run.shape[4]) for curve in run.curves.values())
+    extra = dict(epoch=epochs_done, num_batches=run.num_batches,
+                 loss_hist=torch.from_numpy(run.loss_hist[:epochs_done * run.num_batches].copy()), **first,
+                 gen_state=run.gen.get_state(), args=saved_args(args),
+                 run=run_record(args, run.hp, run.shape, run.from_scene), world=run.world)
+    for entries in later:
+        extra.update(entries)
+    return extra
+
+
+def validate(run, args, epoch):
+    """--eval_every after ``epoch`` epochs, between two steps (or replays), on their stream: launches + one read-back of nets x K x K integers"""
+    eng, evaluator = run.eng, run.evaluator
+    cms = (evaluator.evaluate((eng, None), ensemble=True) if args.ensemble else evaluator.evaluate((eng, None))).cpu().numpy()
+    scored = {'': cms[:2]}                # in the order of the printed lines
+    if args.ensemble:                     # the pair together: the third matrix of the same call (the averaged softmax's label)
+        scored['_ens'] = cms[2]
+    if args.ema:                          # the teachers: their packed weights are rebuilt here, when they are read
+        scored['_ema'] = evaluator.evaluate((eng.teacher, None)).cpu().numpy()
+    for suffix, cms in scored.items():
+        curve, rows = run.curves[suffix], []
+        for net, cm in enumerate(cms[None] if curve.nets is None else cms):
+            OA, Kappa, _, AA = evaluator.metrics(cm)
+            rows.append((OA, AA, Kappa))
+            print('Epoch %d/%d: validation%s%s OA = %.2f AA = %.2f Kappa = %.2f' %
+                  (epoch, args.num_epochs, suffix, NET_TAGS[net], OA * 100, AA * 100, Kappa * 100))
+        curve.add(epoch, rows[0] if curve.nets is None else rows, cms)
+    oa = run.curves[''].rows[-1][0][0]
+    if args.save_best and (run.best_oa is None or oa > run.best_oa):
+        # network 0's best validation so far (the first of equals): the state is copied on the device, behind
+        # the step that produced it on the stream -- no synchronisation, no file until the run is over
+        run.best_oa = oa
+        run.best_state = eng.checkpoint_state(on_device=True, into=run.best_state)
+        run.best_extra = run_extra(run, args, epoch)
+
+
+def replays(run, epoch, batches, after=-1):
+    """what a captured step replays: (epoch, batch, this rank's offsets) of the epoch's full batches behind batch ``after``"""
+    gbt, gbtu = run.bt // run.world, run.btu // run.world              # rows of a replayed step on this rank
+    return [(epoch, bi, lo + run.rank * gbt, uo + run.rank * gbtu) for bi, ((lo, ls), (uo, us)) in enumerate(batches)
+            if bi > after and ls == run.bt and us == run.btu]
+
+
+def train_epochs(run, args):
+    """the epoch loop (train.py:146-289): the steps, eager or replayed, the read-back of their logged rows and, behind an
+    epoch, its validation and its checkpoint"""
+    eng, world, rank, loss_hist, num_batches = run.eng, run.world, run.rank, run.loss_hist, run.num_batches
+    lab_loader, unl_loader, cube_kw = run.lab_loader, run.unl_loader, run.cube_kw
+    bt, btu, ppb = run.bt, run.btu, args.print_per_batches
+    index_i = run.start_epoch * num_batches - 1
     pending = []                      # loss_hist rows of the steps run since the last read-back of the device ring
 
     def read_back():
@@ -433,17 +455,14 @@ def main(args, make_engine=None, device=None):
     # (a split smaller than one batch has no full batch to replay: such a run stays eager.  Several GPUs: the sharded
     #  step is replayed stage by stage, its collectives eager in between -- DistStepGraph; offsets are this rank's)
     use_graph = bool(args.graph) and by_index and hasattr(eng, "capture") and len(lab_loader.X) >= bt and len(unl_loader.X) >= btu
-    gbt, gbtu = bt // world, btu // world                              # rows of a replayed step on this rank
     graph = None
-    t_start = time.time()
-    steps_before = eng.step_count                                    # (--resume: the steps of the earlier legs)
+    t_start, steps_before = time.time(), eng.step_count              # (--resume: the steps of the earlier legs)
     t_warm, steps_warm = t_start, steps_before
-    for epoch in range(start_epoch, args.num_epochs):                # train.py:146
+    for epoch in range(run.start_epoch, args.num_epochs):            # train.py:146
         batches = list(zip(lab_loader, unl_loader))                  # (offset, size) pairs; draws this epoch's permutations
         if use_graph and graph is not None:
             # the whole epoch's per-step scalars go to the device table at once; full batches are replays
-            graph.program([(epoch, bi, lo + rank * gbt, uo + rank * gbtu) for bi, ((lo, ls), (uo, us)) in enumerate(batches)
-                           if ls == bt and us == btu])
+            graph.program(replays(run, epoch, batches))
         for batch_index, ((lo, ls), (uo, us)) in enumerate(batches):
             index_i += 1                                             # train.py:150
             bl, bul, r = ls, us, 0
@@ -466,10 +485,9 @@ def main(args, make_engine=None, device=None):
             if use_graph and graph is None:
                 # the first step ran eagerly (it sets the kernels' attributes); capture now and hand the rest of this
                 # epoch's full batches to the graph
-                graph = eng.capture(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X,
-                                    lab_loader.perm, unl_loader.perm, gbt, gbtu, capacity=max(num_batches, 1), **cube_kw)
-                rest = [(epoch, bi, lo2 + rank * gbt, uo2 + rank * gbtu) for bi, ((lo2, ls2), (uo2, us2)) in enumerate(batches)
-                        if bi > batch_index and ls2 == bt and us2 == btu]
+                graph = eng.capture(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X, lab_loader.perm,
+                                    unl_loader.perm, bt // world, btu // world, capacity=max(num_batches, 1), **cube_kw)
+                rest = replays(run, epoch, batches, after=batch_index)
                 if rest:
                     graph.program(rest)
             pending.append(index_i)
@@ -483,102 +501,96 @@ def main(args, make_engine=None, device=None):
                                             np.mean(w[:, 0]), np.mean(w[:, 1]), np.mean(w[:, 2]), np.mean(w[:, 3]),
                                             np.mean(w[:, 4]) * 100))
         read_back()                   # rows of the epoch's tail (num_batches % print_per_batches steps)
-        if evaluator is not None and (epoch + 1) % args.eval_every == 0:
-            # between two steps (or replays), on their stream: launches + one read-back of nets x K x K integers
-            cms = (evaluator.evaluate((eng, None), ensemble=True) if ens else evaluator.evaluate((eng, None))).cpu().numpy()
-            row = []
-            for net in range(2):
-                OA, Kappa, _, AA = evaluator.metrics(cms[net])
-                row.append((OA, AA, Kappa))
-                print('Epoch %d/%d: validation%s OA = %.2f AA = %.2f Kappa = %.2f' %
-                      (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
-            eval_log.append((epoch + 1, row))
-            eval_cms.append(cms[:2])
-            if ens:
-                # the pair together: the third matrix of the same call (the averaged softmax's label, counted there)
-                OA, Kappa, _, AA = evaluator.metrics(cms[2])
-                print('Epoch %d/%d: validation_ens OA = %.2f AA = %.2f Kappa = %.2f' %
-                      (epoch + 1, args.num_epochs, OA * 100, AA * 100, Kappa * 100))
-                eval_log_ens.append((epoch + 1, (OA, AA, Kappa)))
-                eval_cms_ens.append(cms[2])
-            if ema:
-                # the teachers: their packed weights are rebuilt here, when they are read, not behind every step
-                cms_t = evaluator.evaluate((eng.teacher, None)).cpu().numpy()
-                row_t = []
-                for net in range(2):
-                    OA, Kappa, _, AA = evaluator.metrics(cms_t[net])
-                    row_t.append((OA, AA, Kappa))
-                    print('Epoch %d/%d: validation_ema%s OA = %.2f AA = %.2f Kappa = %.2f' %
-                          (epoch + 1, args.num_epochs, '' if net == 0 else '1', OA * 100, AA * 100, Kappa * 100))
-                eval_log_ema.append((epoch + 1, row_t))
-                eval_cms_ema.append(cms_t)
-            if args.save_best and (best_oa is None or row[0][0] > best_oa):
-                # network 0's best validation so far (the first of equals): the state is copied on the device, behind
-                # the step that produced it on the stream -- no synchronisation, no file until the run is over
-                best_oa = row[0][0]
-                best_state = eng.checkpoint_state(on_device=True, into=best_state)
-                best_extra = run_extra(epoch + 1)
+        if run.evaluator is not None and (epoch + 1) % args.eval_every == 0:
+            validate(run, args, epoch + 1)
         if rank == 0 and args.save_ckpt and (epoch + 1 == args.num_epochs or
                                              (args.ckpt_every > 0 and (epoch + 1) % args.ckpt_every == 0)):
             # an epoch boundary: every row is read back, no replay is pending
-            from cmlpl_amd import checkpoint
-            checkpoint.save(args.save_ckpt.replace('{epoch}', str(epoch + 1)), eng.checkpoint_state(), run_extra(epoch + 1))
-        if epoch == start_epoch:      # (the read-back has drained the device) what follows runs on warm kernels
+            checkpoint.save(args.save_ckpt.replace('{epoch}', str(epoch + 1)), eng.checkpoint_state(), run_extra(run, args, epoch + 1))
+        if epoch == run.start_epoch:  # (the read-back has drained the device) what follows runs on warm kernels
             t_warm, steps_warm = time.time(), eng.step_count
-    if device.type == "cuda":
+    if run.device.type == "cuda":
         torch.cuda.synchronize()
     if rank == 0:
-        steps = eng.step_count
-        t_end = time.time()
+        steps, t_end = eng.step_count, time.time()
         print('training: %d steps in %.3f s' % (steps - steps_before, t_end - t_start))
         if steps > steps_warm:        # the first epoch carries the one-time loading of the kernels
             print('after the first epoch: %d steps in %.3f s = %.4f ms/step' %
                   (steps - steps_warm, t_end - t_warm, (t_end - t_warm) / (steps - steps_warm) * 1e3))
-        if args.save_loss_hist:
-            np.save(args.save_loss_hist, loss_hist)
-        if best_state is not None:
-            from cmlpl_amd import checkpoint
-            checkpoint.save(args.save_best, best_state, best_extra)
-        if args.report_memory and device.type == "cuda":
-            print('peak device memory: %d bytes' % torch.cuda.max_memory_allocated(device))
-    if rank == 0 and eval_log:
-        curve = np.array([r for _, r in eval_log])                    # [evaluations][nets][OA, AA, Kappa]
-        epochs = np.array([e for e, _ in eval_log])
+
+
+def report(run, args):
+    """rank 0 after the last epoch: the files of the run, the best epochs of its curves, the whole-scene evaluation"""
+    eng, device, curves, base = run.eng, run.device, run.curves, run.curves['']
+    if args.save_loss_hist:
+        np.save(args.save_loss_hist, run.loss_hist)
+    if run.best_state is not None:
+        checkpoint.save(args.save_best, run.best_state, run.best_extra)
+    if args.report_memory and device.type == "cuda":
+        print('peak device memory: %d bytes' % torch.cuda.max_memory_allocated(device))
+    if base.epochs:
         for net in range(2):
-            best = int(np.argmax(curve[:, net, 0]))                   # (the first of equal bests)
-            print('best validation%s: epoch %d OA = %.2f' % ('' if net == 0 else '1', epochs[best], curve[best, net, 0] * 100))
-        if ens and eval_log_ens:
-            curve_ens = np.array([r for _, r in eval_log_ens])        # [evaluations][OA, AA, Kappa]
-            epochs_ens = np.array([e for e, _ in eval_log_ens])
-            best = int(np.argmax(curve_ens[:, 0]))
-            print('best validation_ens: epoch %d OA = %.2f' % (epochs_ens[best], curve_ens[best, 0] * 100))
+            print(base.best_line(net))
+        if args.ensemble and curves['_ens'].epochs:
+            print(curves['_ens'].best_line())
         if args.save_eval:
-            more = {}
-            if ema and eval_log_ema:
-                more = dict(curve_ema=np.array([r for _, r in eval_log_ema]), cm_ema=np.stack(eval_cms_ema),
-                            epochs_ema=np.array([e for e, _ in eval_log_ema]))
-            if ens and eval_log_ens:
-                more.update(curve_ens=curve_ens, cm_ens=np.stack(eval_cms_ens), epochs_ens=epochs_ens)
-            np.savez(args.save_eval, curve=curve, epochs=epochs, cm=np.stack(eval_cms), **more)
-    if rank == 0 and not args.no_eval:
-        nets = [(net, eng.state_dict(net)) for net in range(2)]
-        if ema:
-            nets += [('ema%d' % net, eng.teacher.state_dict(net)) for net in range(2)]
-        evaluate_whole(shape, whole, nets, device, synthetic=args.synthetic,
-                       dataID=args.dataID, dropout=args.dropout, val_batch_size=args.val_batch_size,
-                       test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"),
-                       last_eval=eval_log[-1][1] if eval_log and eval_log[-1][0] == args.num_epochs else None)
-        if ens:
-            ensemble_whole(shape, whole, nets[:2], device, synthetic=args.synthetic, dataID=args.dataID,
-                           dropout=args.dropout, test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"))
-        if getattr(args, "tta", False):
-            from cmlpl_amd.tta import TTA
-            tta_whole(shape, whole, nets[:2], device, TTA(args.m, args.noise), synthetic=args.synthetic, dataID=args.dataID,
-                      dropout=args.dropout, test_array=test_array, Y_test=Y_test, resident_cube=cube_kw.get("cube"))
+            np.savez(args.save_eval, **{k: v for curve in curves.values() if curve.epochs for k, v in curve.npz_entries().items()})
+    if args.no_eval:
+        return
+    nets = [(net, eng.state_dict(net)) for net in range(2)]
+    if args.ema:
+        nets += [('ema%d' % net, eng.teacher.state_dict(net)) for net in range(2)]
+    scene = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=args.dropout, test_array=run.test_array,
+                 Y_test=run.Y_test, resident_cube=run.cube_kw.get("cube"))
+    evaluate_whole(run.shape, run.whole, nets, device, val_batch_size=args.val_batch_size,
+                   last_eval=base.rows[-1] if base.epochs and base.epochs[-1] == args.num_epochs else None, **scene)
+    if args.ensemble:
+        ensemble_whole(run.shape, run.whole, nets[:2], device, **scene)
+    if args.tta:
+        from cmlpl_amd.tta import TTA
+        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise), **scene)
+
+
+def main(args, make_engine=None, device=None):
+    """``make_engine`` / ``device`` are test hooks (tests/test_train_loop_gloo.py runs this loop as two gloo ranks
+    on CPU around a stand-in engine); the product path leaves them None."""
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if args.method != "cmlpl" and world > 1:      # before any device or communicator work
+        raise SystemExit(f"--method {args.method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
+                         f"{world} ranks)")
+    if args.ema and world > 1:
+        raise SystemExit(f"--ema runs on one GPU: the sharded engine keeps no EMA teacher (this job has {world} ranks)")
+    if device is None:
+        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+        torch.cuda.set_device(device)
+    torch.manual_seed(1088)                                         # seed_torch(), train.py:50-58
+    # ``run`` is what the phases hand to one another; beside each is what it adds.  The curves: the two networks'; --ema: the same
+    # of the teachers, a curve of their own; --ensemble: the pair's together.  ``gen``: the same permutations on every rank
+    curves = [EvalCurve(sfx, nets) for sfx, nets, on in (('', 2, True), ('_ema', 2, args.ema), ('_ens', None, args.ensemble)) if on]
+    run = argparse.Namespace(world=world, rank=rank, device=device, bt=args.labeled_batch_size, btu=args.unlabeled_batch_size,
+                             gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
+                             from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
+                             evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None)
+    load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
+    build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
+    if args.save_best and args.eval_every <= 0:
+        raise SystemExit("--save_best keeps the best-VALIDATED epoch: it needs --eval_every")
+    if args.ckpt_every > 0 and not args.save_ckpt:
+        raise SystemExit("--ckpt_every needs --save_ckpt PATH")
+    if args.resume:
+        open_resume(run, args)        # resumed, the file: its state goes into eng and gen
+    build_loaders(run, args)          # lab_loader, unl_loader, num_batches, loss_hist; --windows cube: cube_kw
+    if args.eval_every > 0 and rank == 0:
+        build_evaluator(run, args)    # evaluator
+    if args.resume:
+        restore_progress(run, args)   # start_epoch, its rows of loss_hist, the curves so far and best_oa
+    train_epochs(run, args)
+    if rank == 0:
+        report(run, args)
     if world > 1 and make_engine is None:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
-    return loss_hist
+    return run.loss_hist
 
 
 def build_parser():

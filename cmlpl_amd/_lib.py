@@ -39,6 +39,7 @@ EXPORTS = (
     "cmlpl_packed_flag_offset",
     "cmlpl_cps_loss_workspace_bytes", "cmlpl_cps_loss_fwd_bwd",                  # added after ABI 6, no bump: the CPS baseline
     "cmlpl_debug_conv3_plan", "cmlpl_debug_route", "cmlpl_debug_wgrad3_plan",    # added after ABI 6, no bump: test aids
+    "cmlpl_debug_loss_plan",                                                     # added after ABI 6, no bump: test aid (the loss block)
     "cmlpl_ema_update",                                                          # added after ABI 6, no bump: the EMA teacher
     "cmlpl_ensemble",                                                            # added after ABI 6, no bump: ensemble prediction
     "cmlpl_infer_tta_workspace_bytes", "cmlpl_infer_cube_tta", "cmlpl_eval_tta_workspace_bytes",     # added after ABI 6, no bump:
@@ -289,6 +290,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_debug_conv3_plan.argtypes = [SP, i32, i32, i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_route.argtypes = [SP, i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_wgrad3_plan.argtypes = [SP, i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_loss_plan.argtypes = [SP, C.POINTER(Shard), i32, i32, C.POINTER(i32)]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]

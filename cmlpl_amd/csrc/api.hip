@@ -1414,4 +1414,25 @@ int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out)
   return 0;
 }
 
+int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, int bank_rows, int smooth, int* out) {
+  Dims d;
+  if (!make_dims(shape, &d)) return CMLPL_E_SHAPE;
+  const cmlpl_shard* sh = shard;
+  if (!sh || !out) return CMLPL_E_ARG;
+  if (sh->bt_g < 1 || sh->btu_g < 1 || sh->btu_g > 2048 || sh->nlab < 0 || sh->nunl < 1 || sh->lab0 < 0 ||
+      sh->unl0 < 0 || sh->lab0 + sh->nlab > sh->bt_g || sh->unl0 + sh->nunl > sh->btu_g ||
+      bank_rows < sh->bt_g + sh->btu_g)
+    return CMLPL_E_ARG;                 // (what fill_loss_args refuses)
+  LossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Q = bank_rows; a.bt = sh->bt_g; a.btu = sh->btu_g; a.K = d.K; a.smooth = smooth;
+  a.lab0 = sh->lab0; a.nlab = sh->nlab; a.unl0 = sh->unl0; a.nunl = sh->nunl;
+  LossPlan p;
+  plan_loss_phase1(a, &p);
+  int* o = out;
+  *o++ = p.kernel; *o++ = p.MB; *o++ = p.NBW; *o++ = p.gx; *o++ = p.gy; *o++ = p.ctiles;
+  *o++ = loss_dfeat_lds_shape(a) ? 1 : 0; *o++ = plan_loss_dfeat_lds(a) ? 1 : 0; *o++ = device_cus();
+  return 0;
+}
+
 }  // extern "C"

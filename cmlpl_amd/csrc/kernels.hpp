@@ -339,6 +339,22 @@ struct LossArgs {
 };
 size_t loss_ws_floats(int nlab, int nunl, int btu_g, int K, int Q);
 void loss_ws_carve(LossArgs& a, float* ws);
+// Which kernel forms phase 1's three exp(f . f^T / T) products, and on what grid: decided once per launch by
+// plan_loss_phase1 from the shard's rows, K, the banks' width, the compute-unit count and the CMLPL_PAIR_* switches
+// (host arithmetic); launch_loss_phase1 runs what it says and decides nothing itself (cmlpl_debug_loss_plan shows it).
+enum { LOSS_PAIR16 = 0, LOSS_PAIR32 = 1, LOSS_TALL = 2, LOSS_WIDE = 3 };   // pair_exp16_kernel, pair_exp_kernel, pair_exp_tall_kernel, pair_exp_wide_kernel<MB, 4 / MB, NBW>
+struct LossPlan {
+  int kernel;                             // LOSS_*
+  int MB, NBW;                            // the wide kernel's row blocks (2 or 4) and column blocks per wave (0, 0 otherwise)
+  int ctw;                                // bank columns per partial of rs_part / ep_part
+  int gx, gy;                             // the grid (z = 3: the three products)
+  int ctiles;                             // 32-column tiles of the widest product
+};
+void plan_loss_phase1(const LossArgs& a, LossPlan* p);
+// the shape half of "the feature-gradient GEMMs take their operands through LDS": every row a whole number of 16-byte
+// pieces (the pointers' alignment is the launcher's half)
+bool loss_dfeat_lds_shape(const LossArgs& a);
+bool plan_loss_dfeat_lds(const LossArgs& a);   // ... and CMLPL_DFEAT_LDS does not forbid it: what launch_loss_dfeat asks
 // phase 1 = pair_exp (embeddings and banks only) + the row kernel (this shard's logits); plain mode: the row launch also
 // writes the banks.  Packed mode: the bank write rides with phase 2's graph launch (it needs every rank's probabilities).
 hipError_t launch_loss_phase1(const LossArgs& a, hipStream_t st);

@@ -1219,14 +1219,13 @@ __global__ __launch_bounds__(256) void loss_dfeat_kernel(GemmTN2 t, int gemm_blo
 }
 
 template <int MB, int CG, int NBW>
-static hipError_t launch_pair_wide(const LossArgs& a, int maxc, hipStream_t st, bool attr_only = false) {
+static hipError_t launch_pair_wide(const LossArgs& a, dim3 grid, hipStream_t st, bool attr_only = false) {
   typedef WideCfg<MB, CG, NBW> Cf;
   constexpr size_t lds = Cf::LDS_FL * 4;
   static DevOnce once;
   hipError_t e = ensure_max_lds(once, pair_exp_wide_kernel<MB, CG, NBW>);
   if (e != hipSuccess || attr_only) return e;
-  hipLaunchKernelGGL((pair_exp_wide_kernel<MB, CG, NBW>), dim3((maxc + Cf::NT - 1) / Cf::NT, (a.nunl + Cf::MT - 1) / Cf::MT, 3),
-                     dim3(Cf::NTHR), lds, st, a);
+  hipLaunchKernelGGL((pair_exp_wide_kernel<MB, CG, NBW>), grid, dim3(Cf::NTHR), lds, st, a);
   return hipGetLastError();
 }
 
@@ -1237,19 +1236,15 @@ static hipError_t launch_pair_wide(const LossArgs& a, int maxc, hipStream_t st, 
 hipError_t loss_prepare_capture() {
   const LossArgs a = LossArgs();
   hipError_t e;
-  if ((e = launch_pair_wide<4, 1, 1>(a, 0, nullptr, true)) != hipSuccess) return e;
-  if ((e = launch_pair_wide<4, 1, 2>(a, 0, nullptr, true)) != hipSuccess) return e;
-  if ((e = launch_pair_wide<4, 1, 3>(a, 0, nullptr, true)) != hipSuccess) return e;
-  if ((e = launch_pair_wide<4, 1, 4>(a, 0, nullptr, true)) != hipSuccess) return e;
-  if ((e = launch_pair_wide<2, 2, 1>(a, 0, nullptr, true)) != hipSuccess) return e;
-  return launch_pair_wide<2, 2, 2>(a, 0, nullptr, true);
+  if ((e = launch_pair_wide<4, 1, 1>(a, dim3(), nullptr, true)) != hipSuccess) return e;
+  if ((e = launch_pair_wide<4, 1, 2>(a, dim3(), nullptr, true)) != hipSuccess) return e;
+  if ((e = launch_pair_wide<4, 1, 3>(a, dim3(), nullptr, true)) != hipSuccess) return e;
+  if ((e = launch_pair_wide<4, 1, 4>(a, dim3(), nullptr, true)) != hipSuccess) return e;
+  if ((e = launch_pair_wide<2, 2, 1>(a, dim3(), nullptr, true)) != hipSuccess) return e;
+  return launch_pair_wide<2, 2, 2>(a, dim3(), nullptr, true);
 }
 
-hipError_t launch_loss_phase1(const LossArgs& a_in, hipStream_t st) {
-  hipError_t e;
-  LossArgs a = a_in;
-  a.ctw = 32;
-  const int nl = a.nlab + a.nunl;
+void plan_loss_phase1(const LossArgs& a, LossPlan* p) {
   // (device-side step scalars: whether the banks are read is decided in the kernels, the grid covers them)
   const bool banks = a.smooth || a.sel.dyn.table != nullptr;
   const int maxc = (banks && a.Q > a.btu) ? a.Q : a.btu;
@@ -1266,6 +1261,10 @@ hipError_t launch_loss_phase1(const LossArgs& a_in, hipStream_t st) {
   const int force_tall = switches().pair_tall;
   const bool wide = force_tall <= 0 && wide_mode != 0 && a.K <= 32 && ((ctiles >= 128 && a.nunl <= 128) || wide_mode == 1);
   const bool tall = !wide && (force_tall >= 0 ? force_tall != 0 : (ctiles >= 128 && a.nunl >= 64));
+  p->MB = p->NBW = 0;
+  p->ctw = 32;
+  p->ctiles = ctiles;
+  p->gx = ctiles;
   if (wide) {
     const long long total = (banks ? 2LL * a.Q : 0) + a.btu;                 // columns of the three products
     // 64 x 64 tiles (three workgroups fit a CU) while they make at most one and a half rounds; beyond that 128 x 32 NBW
@@ -1281,18 +1280,39 @@ hipError_t launch_loss_phase1(const LossArgs& a_in, hipStream_t st) {
     if (MB == 2 && a.nunl > 64) NBW = 1;                                     // the 64 x 64 tiles of the rule above
     if (force_nbw > 0) NBW = force_nbw;
     NBW = NBW < 1 ? 1 : NBW > nbw_max ? nbw_max : NBW;
-    a.ctw = 32 * NBW;
-    if (MB == 4) e = NBW == 1 ? launch_pair_wide<4, 1, 1>(a, maxc, st) : NBW == 2 ? launch_pair_wide<4, 1, 2>(a, maxc, st)
-                   : NBW == 3 ? launch_pair_wide<4, 1, 3>(a, maxc, st) : launch_pair_wide<4, 1, 4>(a, maxc, st);
-    else         e = NBW == 1 ? launch_pair_wide<2, 2, 1>(a, maxc, st) : launch_pair_wide<2, 2, 2>(a, maxc, st);
-    if (e != hipSuccess) return e;
+    const int NT = 32 * CG * NBW, MT = 32 * MB;                              // WideCfg<MB, CG, NBW>::NT, ::MT
+    p->kernel = LOSS_WIDE; p->MB = MB; p->NBW = NBW;
+    p->ctw = 32 * NBW;
+    p->gx = (maxc + NT - 1) / NT; p->gy = (a.nunl + MT - 1) / MT;
   } else if (tall) {
-    hipLaunchKernelGGL(pair_exp_tall_kernel, dim3(ctiles, (a.nunl + 127) / 128, 3), dim3(256), 0, st, a);
+    p->kernel = LOSS_TALL; p->gy = (a.nunl + 127) / 128;
   } else if (a.K <= 32 && pair16) {
-    hipLaunchKernelGGL(pair_exp16_kernel, dim3(ctiles, (a.nunl + 15) / 16, 3), dim3(256), 0, st, a);
+    p->kernel = LOSS_PAIR16; p->gy = (a.nunl + 15) / 16;
   } else {
-    dim3 g1(ctiles, (a.nunl + 31) / 32, 3);
-    hipLaunchKernelGGL(pair_exp_kernel, g1, dim3(256), 0, st, a);
+    p->kernel = LOSS_PAIR32; p->gy = (a.nunl + 31) / 32;
+  }
+}
+
+hipError_t launch_loss_phase1(const LossArgs& a_in, hipStream_t st) {
+  hipError_t e;
+  LossArgs a = a_in;
+  LossPlan p;
+  plan_loss_phase1(a, &p);
+  a.ctw = p.ctw;
+  const int nl = a.nlab + a.nunl;
+  const dim3 grid(p.gx, p.gy, 3);
+  if (p.kernel == LOSS_WIDE) {
+    const int NBW = p.NBW;
+    if (p.MB == 4) e = NBW == 1 ? launch_pair_wide<4, 1, 1>(a, grid, st) : NBW == 2 ? launch_pair_wide<4, 1, 2>(a, grid, st)
+                     : NBW == 3 ? launch_pair_wide<4, 1, 3>(a, grid, st) : launch_pair_wide<4, 1, 4>(a, grid, st);
+    else           e = NBW == 1 ? launch_pair_wide<2, 2, 1>(a, grid, st) : launch_pair_wide<2, 2, 2>(a, grid, st);
+    if (e != hipSuccess) return e;
+  } else if (p.kernel == LOSS_TALL) {
+    hipLaunchKernelGGL(pair_exp_tall_kernel, grid, dim3(256), 0, st, a);
+  } else if (p.kernel == LOSS_PAIR16) {
+    hipLaunchKernelGGL(pair_exp16_kernel, grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(pair_exp_kernel, grid, dim3(256), 0, st, a);
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // + one workgroup per row of the global batch for the bank write (plain mode; packed mode: with the graph launch)
@@ -1308,6 +1328,15 @@ hipError_t launch_loss_graph(const LossArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(graph_loss_kernel, dim3(a.nunl + (a.recv_f != nullptr ? a.bt + a.btu : 0)), dim3(256), lds, st, a);
   return hipGetLastError();
 }
+
+// M and lda of the two GEMMs are the local and the global unlabelled rows (G^T is [btu][nunl], G [nunl][btu]); in packed
+// mode fU_w's rows lie in rank-major blocks pack_f floats apart
+bool loss_dfeat_lds_shape(const LossArgs& a) {
+  const long long seg_stride = a.recv_f != nullptr ? a.pack_f : 0;
+  return (a.nunl % 4) == 0 && (a.btu % 4) == 0 && (seg_stride % 4) == 0;
+}
+
+bool plan_loss_dfeat_lds(const LossArgs& a) { return loss_dfeat_lds_shape(a) && switches().dfeat_lds != 0; }
 
 hipError_t launch_loss_dfeat(const LossArgs& a, hipStream_t st) {
   hipError_t e;
@@ -1343,11 +1372,10 @@ hipError_t launch_loss_dfeat(const LossArgs& a, hipStream_t st) {
   t.p[0] = g; t.p[1] = h;
   // operands through LDS wherever every row is a whole number of 16-byte pieces (measured per rank, B2 128 + 128 rows: 6.7 -> 5.2 us
   // on one GPU, 25.9 -> 22.4 us at W = 8); CMLPL_DFEAT_LDS=0: the direct-load tiles always
-  const int lds_mode = switches().dfeat_lds;
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  const bool lds_ok = (g.M % 4) == 0 && (h.M % 4) == 0 && (g.lda % 4) == 0 && (h.lda % 4) == 0 && (g.b_seg_stride % 4) == 0 &&
+  const bool lds_ok = plan_loss_dfeat_lds(a) &&
                       al16(g.A) && al16(g.B) && al16(h.A) && al16(h.B) && al16(g.C) && al16(h.C);   // 16-byte pieces everywhere
-  if (lds_ok && lds_mode != 0) {
+  if (lds_ok) {
     t.nblk0 = dfeat_lds_blocks(g);
     const int gb = t.nblk0 + dfeat_lds_blocks(h);
     hipLaunchKernelGGL(loss_dfeat_lds_kernel, dim3(gb + 1), dim3(256), 0, st, t, gb, a);

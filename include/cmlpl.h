@@ -824,6 +824,23 @@ int cmlpl_debug_route(const cmlpl_shape* shape, int nets, int n, int* out);
 #define CMLPL_WGRAD3_PLAN_INTS 17
 int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out);
 
+/* Added after ABI 6, no bump (nothing existing moves).  Test aid: what the planner of the loss block's first launch
+ * (plan_loss_phase1, the one function launch_loss_phase1 obeys) decides under the current switches for a shard of the
+ * batch (one GPU: {bt, btu, 0, bt, 0, btu}), K classes, banks of `bank_rows` rows and the smoothing gate `smooth`, read
+ * from plain buffers (the sharded step's packed buffers add one condition to [6]: a local labelled row count that is a
+ * multiple of 4).  out[CMLPL_LOSS_PLAN_INTS]:
+ *   [0] the kernel of the three exp(f . f^T / T) products: 0 = pair_exp16_kernel (16 x 32 tiles), 1 = pair_exp_kernel
+ *       (32 x 32 tiles; the only narrow kernel for K > 32), 2 = pair_exp_tall_kernel (128 x 32), 3 = pair_exp_wide_kernel
+ *   [1], [2] the wide kernel's template parameters MB (2 or 4 row blocks) and NBW (column blocks per wave), else 0, 0
+ *   [3], [4] grid x and y (z is 3: the three products)
+ *   [5] 32-column tiles of the widest product
+ *   [6] 1 = the shape allows the feature-gradient GEMMs their operands through LDS (rows in whole 16-byte pieces)
+ *   [7] 1 = [6] and CMLPL_DFEAT_LDS does not forbid it: that launch runs when the call's pointers are 16-byte aligned
+ *   [8] the compute-unit count the plan was made for
+ * Host arithmetic only, nothing is launched.  CMLPL_E_ARG (what cmlpl_loss_fwd_bwd refuses) / CMLPL_E_SHAPE. */
+#define CMLPL_LOSS_PLAN_INTS 9
+int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, int bank_rows, int smooth, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,11 +79,13 @@ def shard_inputs(cb, W, bt, btu, cls_in, with_noise):
 
 @pytest.mark.parametrize("W,shape_name,bt,btu,explicit", [(2, "B2", 32, 32, True), (4, "B2", 64, 64, True),
                                                           (2, "P", 16, 16, True), (2, "B2", 64, 64, False),
-                                                          (8, "B2", 64, 128, False)])
+                                                          (8, "B2", 64, 128, False), (2, "K40", 16, 16, True)])
 def test_sharded_step_equals_single_gpu_step(W, shape_name, bt, btu, explicit):
     from cmlpl_amd import TrainEngine
     from cmlpl_amd.distributed import DistTrainEngine
-    shape = {"B2": O.NetShape(103, 11, 11, 103, 9), "P": O.NetShape(60, 20, 20, 103, 9)}[shape_name]
+    # K40: more than 32 classes on a small window -- the packed-buffer readers meet pair_exp_kernel's shuffle epilogue
+    shape = {"B2": O.NetShape(103, 11, 11, 103, 9), "P": O.NetShape(60, 20, 20, 103, 9),
+             "K40": O.NetShape(16, 8, 8, 12, 40)}[shape_name]
     hp = O.HyperParams()
     p0, p1 = O.closed_form_params(shape, 31), O.closed_form_params(shape, 32)
     ref = TrainEngine(to_shape(shape), bt, btu, to_hp(hp), device=DEV, seed=99)

@@ -6,6 +6,7 @@ Public surface:
   BaseNet2 ..................... drop-in nn.Module (tools/models.py:97-152 of the reference)
   ensemble_logits / _cube / _pixels ... averaged probabilities, label, confidence, entropy of 1..4 networks
   TTA, tta_cube / tta_pixels, views_of ... the same from several noisy views per pixel (test-time augmentation)
+  Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in ("TTA", "tta_cube", "tta_pixels", "views_of"):
         from . import tta
         return getattr(tta, name)
+    if name in ("Smooth", "smooth_probs", "smooth_cube"):
+        from . import smooth
+        return getattr(smooth, name)
     raise AttributeError(name)

@@ -44,6 +44,7 @@ EXPORTS = (
     "cmlpl_ensemble",                                                            # added after ABI 6, no bump: ensemble prediction
     "cmlpl_infer_tta_workspace_bytes", "cmlpl_infer_cube_tta", "cmlpl_eval_tta_workspace_bytes",     # added after ABI 6, no bump:
     "cmlpl_infer_pixels_tta", "cmlpl_tta_patches", "cmlpl_ensemble_views",                           # test-time augmentation
+    "cmlpl_smooth_probs",                                                        # added after ABI 6, no bump: spatial smoothing
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
 
@@ -260,6 +261,7 @@ def load(path: str = LIB_PATH):
                                            f32, u64, u32]
     lib.cmlpl_tta_patches.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, u64, u32, vp]
     lib.cmlpl_ensemble_views.argtypes = [vp, i32, i32, i64, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.cmlpl_smooth_probs.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

@@ -841,6 +841,51 @@ int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out)
 #define CMLPL_LOSS_PLAN_INTS 9
 int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, int bank_rows, int smooth, int* out);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- EDGE-PRESERVING SPATIAL SMOOTHING of class probability maps: the
+ * probabilities of every class are averaged over a small neighbourhood in which a neighbour counts less the farther away
+ * it is and the less its guide vector resembles the centre pixel's (Kang, Li and Benediktsson 2014; the reference has no
+ * counterpart: each of its labels is the product of a single window).
+ *
+ * THE DEFINITION OF A SMOOTHED MAP.  Pixel i = (y, x) of a rows x cols scene; probabilities p[i][c], c < K (d_probs
+ * [rows * cols][K], what cmlpl_ensemble / cmlpl_ensemble_views write); guide vectors g[i][0 .. G - 1] = the first G =
+ * guide_ch floats at d_guide + i guide_stride (the resident cube [rows][cols][C]: its leading principal components;
+ * 0 <= G <= 8, G = 0: no guide, d_guide is not read); radius R, 1 <= R <= 8;
+ *   a = fl32(1 / (2 sigma_s^2)),  b = fl32(1 / (2 sigma_r^2)), formed in double on the host from the fp32 arguments;
+ *   sigma_r = +inf gives b = 0.
+ *     q[i][c] = ( sum_j w_ij p[j][c] ) / ( sum_j w_ij )
+ *     w_ij    = exp( -( (dy^2 + dx^2) a + |g_i - g_j|^2 b ) )
+ *     j = (y + dy, x + dx),  |dy| <= R,  |dx| <= R,  j INSIDE the scene
+ *   Taps outside the scene are left out -- there is no mirror, the normalisation takes care of the border.  The centre
+ *   tap has weight exactly 1, so the denominator is >= 1.
+ *   The fp32 evaluation, in this order and with these operations (every one rounded once):
+ *     taps run dy ascending and, within dy, dx ascending; per tap
+ *       d2 = 0;  for ch = 0 .. G - 1 ascending:  d = g_i[ch] - g_j[ch];  d2 = fmaf(d, d, d2)
+ *       e  = fmaf(d2, b, fl(s a)),  s = (float)(dy^2 + dx^2) (exact);  w = expf(-e)
+ *       den = den + w;  num[c] = fmaf(w, p[j][c], num[c]) for every c
+ *     then q[i][c] = num[c] / den (a correctly rounded division).  G = 0 and sigma_r = +inf give the same bits.
+ *   A pixel's result is therefore a function of the scene alone: it depends neither on the tile the pixel falls in nor on
+ *   the grid, and it is the same bytes on every run.
+ *   NaN: a NaN probability of ANY class of a neighbour inside the scene makes the pixel's WHOLE ROW of q NaN (also where
+ *   the neighbour's weight has underflowed to 0: 0 x NaN is NaN) -- one NaN row of p spoils exactly the pixels within R
+ *   of it, in both directions.  An infinite probability does the same wherever its weight is 0.
+ *   From q, by cmlpl_ensemble's rules: label = the FIRST maximum of q, a NaN counts as the maximum and the first NaN wins
+ *   (a NaN row: 0); conf = q[label]; entropy = 0 - sum_c t_c, t_c = q_c logf(q_c) with 0 log 0 = 0, the sum running c
+ *   ascending from 0 (one thread owns a pixel's row: no butterfly), NaN when q is NaN.
+ *
+ * cmlpl_smooth_probs: one launch of that definition.  d_out_probs [rows * cols][K] (or NULL) = q; d_labels [rows * cols]
+ *   int64, d_conf, d_entropy [rows * cols] (each or NULL).  The filter is NOT in place: d_out_probs must not overlap
+ *   d_probs (several passes ping-pong two buffers).  A workgroup stages a tile of 32 x 8 pixels and its halo once into
+ *   LDS, channel-planar, and every thread walks the taps of its pixel with up to 16 classes in registers (K > 16: chunks
+ *   of 16 over the guide staged once); no atomics, no workspace, no synchronisation (it can be captured in a graph once
+ *   an eager call has set the kernels' LDS attribute).
+ *   CMLPL_E_ARG before any launch: K outside 1..64, radius outside 1..8, guide_ch outside 0..8, rows or cols < 1 (or
+ *   rows * cols past 2^31 - 1); guide_ch > 0 with a null d_guide or guide_stride < guide_ch; sigma_s not finite or <= 0;
+ *   sigma_r <= 0 or NaN; a sigma so small that a or b is not finite in fp32; a null d_probs; d_out_probs and d_labels both
+ *   null; a misaligned pointer; d_out_probs overlapping d_probs. */
+int cmlpl_smooth_probs(const float* d_probs, const float* d_guide, int64_t guide_stride, int guide_ch,
+                       int rows, int cols, int K, int radius, float sigma_s, float sigma_r,
+                       float* d_out_probs, int64_t* d_labels, float* d_conf, float* d_entropy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,11 @@ with the tag ``_ens``; ``--proba`` / ``--confidence`` / ``--entropy`` write the 
 ``train.py --synthetic`` evaluates on (datasets are not shipped).  ``--tta M`` predicts from the clean window and M noisy views
 (x + S N(0,1), S = ``--tta_noise``, default the checkpoint's training noise) of every pixel, averaged over the views and
 over the networks of ``--net`` (any single network or ensemble; cmlpl_amd.tta): the label map, the ``Result:`` lines (tag
-``_tta``) and ``--proba`` / ``--confidence`` / ``--entropy`` then describe that prediction."""
+``_tta``) and ``--proba`` / ``--confidence`` / ``--entropy`` then describe that prediction.  ``--smooth R`` smooths the class
+probability maps of that prediction over the scene -- an edge-preserving filter of radius R guided by the cube's leading
+channels (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``), with any single
+network or ensemble, with or without ``--tta``: the ``Result:`` block above is printed as it is, a second one follows with
+``_smooth`` appended to its tag, and ``--out`` / ``--proba`` / ``--confidence`` / ``--entropy`` describe the SMOOTHED prediction."""
 import argparse
 import os
 
@@ -26,7 +30,7 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import DATASETS, SYNTH, ensemble_whole, evaluate_whole, tta_whole
+from train import DATASETS, NET_TAGS, SYNTH, add_smooth_flags, ensemble_whole, evaluate_whole, smooth_of, smooth_whole, tta_whole
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 
@@ -48,6 +52,9 @@ def check_args(args):
             raise SystemExit("--tta_seed N: 0 <= N < 2^64")
     elif args.tta_noise is not None or args.tta_no_clean:
         raise SystemExit("--tta_noise / --tta_no_clean belong to --tta M")
+    if smooth_of(args) is not None and args.net in ('both', 'ema_both'):
+        raise SystemExit("--smooth gives ONE prediction: --net %s writes two label maps (name one network, or --net "
+                         "ensemble for the two together)" % args.net)
 
 
 def main(args, device=None):
@@ -82,13 +89,21 @@ def main(args, device=None):
     extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
     common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
     members = [(k, ck[keys[k]]) for k in which]
+    smooth, tta = smooth_of(args), None
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
         tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
                   clean=not args.tta_no_clean)
+    if smooth is not None and (tta is not None or args.net in ENSEMBLES):
+        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=NET_TAGS['ens' if tta is None else 'tta'],
+                           raw_block=True, **common, **extras)
+    elif tta is not None:
         out = tta_whole(shape, whole, members, device, tta, **common, **extras)
     elif args.net in ENSEMBLES:
         out = ensemble_whole(shape, whole, members, device, **common, **extras)
+    elif smooth is not None:        # one network: its Result: block as ever, then its own softmax (a one-member ensemble) smoothed
+        evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
+        out = smooth_whole(shape, whole, members, device, smooth, tag=NET_TAGS[which[0]], **common, **extras)
     else:
         preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
         labels = np.stack([preds[k] for k in which]).astype(np.int64)
@@ -128,6 +143,7 @@ def build_parser():
                         help="--tta: the views are x + S N(0,1) (default: the checkpoint's training noise)")
     parser.add_argument('--tta_seed', type=int, default=1088, metavar='N', help='--tta: the seed of the views')
     parser.add_argument('--tta_no_clean', action='store_true', help='--tta: the noisy views only, without the clean window')
+    add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

@@ -32,6 +32,10 @@ Differences from the reference that are deliberate, MI355X-first choices:
     (cmlpl_amd.ensemble, one launch behind the eval forward): a third ``validation_ens`` line per ``--eval_every``
     evaluation, a curve of its own in ``--save_eval`` and the checkpoints, a third ``Result:`` block (``OA_ens``) after
     the run.  It reads the networks and changes nothing they compute: ``loss_hist`` is what it is without the flag.
+  * ``--smooth R``: after the run Base and Base1 are scored together once more with their class probability maps
+    SMOOTHED over the scene -- an edge-preserving filter of radius R guided by the cube's leading principal components
+    (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``): one more
+    ``Result:`` block (``OA_ens_smooth``).  The run itself is untouched.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -109,9 +113,9 @@ def run_record(args, hp, shape, from_scene):
 
 
 def saved_args(args):
-    """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta) is left
-    out at its default, so a file written without it is byte for byte what it was before the flag existed"""
-    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False}
+    """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
+    its sub-flags) is left out at its default, so a file written without it is byte for byte what it was before the flag existed"""
+    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS}}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
@@ -163,6 +167,40 @@ class EvalCurve:
 NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
             'ens': '_ens',                                         # ensemble_whole: several of them together
             'tta': '_tta'}                                         # tta_whole: over noisy views of every pixel
+SMOOTH_TAG = '_smooth'                                             # smooth_whole: appended to the tag of what it smooths
+SMOOTH_FLAGS = ('smooth', 'smooth_sigma_s', 'smooth_sigma_r', 'smooth_guide', 'smooth_iters')
+
+
+def add_smooth_flags(parser, what):
+    """``--smooth R`` and its sub-flags (train.py and predict.py); every default is None: the flag was not given"""
+    parser.add_argument('--smooth', type=int, default=None, metavar='R',
+                        help='edge-preserving spatial smoothing of the class probability maps of %s, radius R (1 .. 8), guided '
+                             'by the leading channels of the scene cube: one more Result: block, tag ..._smooth' % what)
+    parser.add_argument('--smooth_sigma_s', type=float, default=None, metavar='S',
+                        help='--smooth: the spatial width in pixels (default R / 2)')
+    parser.add_argument('--smooth_sigma_r', type=float, default=None, metavar='S',
+                        help="--smooth: the width in the guide's z-scored units (default 0.5; inf: the guide does not count)")
+    parser.add_argument('--smooth_guide', type=int, default=None, metavar='G',
+                        help='--smooth: how many leading channels of the cube guide the filter (default 3, 0 .. 8; 0: none)')
+    parser.add_argument('--smooth_iters', type=int, default=None, metavar='N', help='--smooth: passes of the filter (default 1)')
+
+
+def smooth_of(args):
+    """the ``cmlpl_amd.smooth.Smooth`` of the command line, or None without ``--smooth``; what it cannot mean is a SystemExit
+    before anything is loaded"""
+    given = [k for k in SMOOTH_FLAGS[1:] if getattr(args, k, None) is not None]
+    if getattr(args, 'smooth', None) is None:
+        if given:
+            raise SystemExit("%s belong%s to --smooth R" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
+        return None
+    from cmlpl_amd.smooth import Smooth
+    asked = {k: getattr(args, 'smooth_' + k, None) for k in ('sigma_s', 'sigma_r', 'guide', 'iters')}
+    smooth = Smooth(args.smooth, **{k: v for k, v in asked.items() if v is not None})
+    try:
+        smooth.params()
+    except ValueError as e:
+        raise SystemExit("--smooth: %s" % str(e).replace("Smooth: ", ""))
+    return smooth
 
 
 def print_result(tag, pred, test_array, Y_test):
@@ -194,9 +232,12 @@ def build_nets(shape, nets, device, dropout):
     return models
 
 
-def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube):
-    """the body of ``ensemble_whole`` and ``tta_whole``: ``predict(models, cube, spectra)`` is the library call, ``timing`` its
-    printed line (a format of the seconds and the number of networks), ``tag`` that of its ``Result:`` lines, ``noun`` who asks"""
+def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
+                   then=None, raw_block=True):
+    """the body of ``ensemble_whole``, ``tta_whole`` and ``smooth_whole``: ``predict(models, cube, spectra)`` is the library call,
+    ``timing`` its printed line (a format of the seconds and the number of networks), ``tag`` that of its ``Result:`` lines
+    (``raw_block`` False: not printed), ``noun`` who asks.  ``then`` = (timing, tag, call): a second stage ``call(result, cube)``
+    on the first one's result, with a line and a block of its own; its outputs are then the ones returned."""
     source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
     if source is None:
         raise SystemExit("%s needs the scene cube (cube.npy + scene.json in the dataset directory, "
@@ -206,8 +247,16 @@ def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synth
     res = predict(models, source.cube, source.spectra)
     out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
     print(timing % (time.time() - t1, len(models)))
-    if test_array is not None:
+    if test_array is not None and raw_block:
         print_result(tag, out["labels"], test_array, Y_test)
+    if then is not None:
+        timing, tag, call = then
+        t1 = time.time()
+        res = call(res, source.cube)
+        out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
+        print(timing % (time.time() - t1))
+        if test_array is not None:
+            print_result(tag, out["labels"], test_array, Y_test)
     return out
 
 
@@ -237,6 +286,31 @@ def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout
         'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g)' %
         (tta.views, ' + the clean window' if tta.clean else '', tta.sigma), NET_TAGS['tta'], "test-time augmentation",
         shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
+
+
+def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None, dataID=1,
+                 dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+    """``ensemble_whole`` (``tta``: ``tta_whole``) followed by the edge-preserving spatial smoothing of its class probability
+    maps under the guide of the scene cube (``smooth``: a cmlpl_amd.smooth.Smooth; what cmlpl_amd.smooth.smooth_cube
+    does, in its two halves).  Same returns, of the SMOOTHED prediction; its ``Result:`` lines carry ``tag`` + ``_smooth``.
+    ``raw_block``: the ``Result:`` block of the un-smoothed prediction is printed in front of it, under ``tag``."""
+    from cmlpl_amd.smooth import smooth_probs
+    if tta is None:
+        from cmlpl_amd.ensemble import ensemble_cube
+        raw = lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=True)
+        timing = 'ensemble inference time == %.3f s (%d networks)'
+    else:
+        from cmlpl_amd.tta import tta_cube
+        raw = lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True)
+        timing = 'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g)' % (
+            tta.views, ' + the clean window' if tta.clean else '', tta.sigma)
+    R, ss, sr, G, iters = smooth.params()
+    return together_whole(
+        raw, timing, tag, "spatial smoothing", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
+        then=('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
+              (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
+              lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy)),
+        raw_block=raw_block)
 
 
 def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
@@ -549,12 +623,15 @@ def report(run, args):
     if args.tta:
         from cmlpl_amd.tta import TTA
         tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise), **scene)
+    if run.smooth is not None:
+        smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene)
 
 
 def main(args, make_engine=None, device=None):
     """``make_engine`` / ``device`` are test hooks (tests/test_train_loop_gloo.py runs this loop as two gloo ranks
     on CPU around a stand-in engine); the product path leaves them None."""
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    smooth = smooth_of(args)                                        # (refused before any device or communicator work)
     if args.method != "cmlpl" and world > 1:      # before any device or communicator work
         raise SystemExit(f"--method {args.method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
                          f"{world} ranks)")
@@ -570,7 +647,7 @@ def main(args, make_engine=None, device=None):
     run = argparse.Namespace(world=world, rank=rank, device=device, bt=args.labeled_batch_size, btu=args.unlabeled_batch_size,
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
-                             evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None)
+                             evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth)
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -634,6 +711,7 @@ def build_parser():
                         help="test-time augmentation after the run: Base and Base1 TOGETHER score the clean window and --m "
                              "noisy views (x + --noise N(0,1)) of every scene pixel, one more Result: block (OA_tta) from "
                              "the average of all their softmaxes; the run itself is untouched")
+    add_smooth_flags(parser, 'Base and Base1 together after the run')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

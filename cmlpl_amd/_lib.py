@@ -45,8 +45,17 @@ EXPORTS = (
     "cmlpl_infer_tta_workspace_bytes", "cmlpl_infer_cube_tta", "cmlpl_eval_tta_workspace_bytes",     # added after ABI 6, no bump:
     "cmlpl_infer_pixels_tta", "cmlpl_tta_patches", "cmlpl_ensemble_views",                           # test-time augmentation
     "cmlpl_smooth_probs",                                                        # added after ABI 6, no bump: spatial smoothing
+    "cmlpl_infer_cube_tta_sym", "cmlpl_infer_pixels_tta_sym", "cmlpl_tta_patches_sym",   # added after ABI 6, no bump: flip / rotate views
 )
-METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved (CMLPL_METHOD_*)
+METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
+SPATIAL = {"none": 0, "flips": 1, "d4": 2}    # cmlpl_step_io.reserved, bits 8..9 (CMLPL_SYM_*); 1, 4, 8 elements
+
+
+def spatial_elements(mode: str) -> int:
+    """the number S of spatial elements of a mode (include/cmlpl.h, "THE DEFINITION OF A SPATIAL ELEMENT")"""
+    if mode not in SPATIAL:
+        raise ValueError(f"spatial mode {mode!r}: one of {sorted(SPATIAL)}")
+    return (1, 4, 8)[SPATIAL[mode]]
 
 KERNEL_NAMES = ("augment", "conv0_fwd", "conv1_fwd", "conv2_fwd", "spe_fwd", "head_fwd", "loss", "head_bwd",
                 "cls_wgrad", "spe_wgrad", "conv2_dgrad", "conv2_wgrad", "conv2_wred", "conv1_dgrad", "conv1_wgrad",
@@ -260,6 +269,9 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_infer_pixels_tta.argtypes = [SP, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp,
                                            f32, u64, u32]
     lib.cmlpl_tta_patches.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, u64, u32, vp]
+    lib.cmlpl_infer_cube_tta_sym.argtypes = lib.cmlpl_infer_cube_tta.argtypes + [u32]
+    lib.cmlpl_infer_pixels_tta_sym.argtypes = lib.cmlpl_infer_pixels_tta.argtypes + [u32]
+    lib.cmlpl_tta_patches_sym.argtypes = lib.cmlpl_tta_patches.argtypes + [u32]
     lib.cmlpl_ensemble_views.argtypes = [vp, i32, i32, i64, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
     lib.cmlpl_smooth_probs.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]

@@ -32,11 +32,12 @@ class CheckpointError(RuntimeError):
 
 
 def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_hash: str, abi: int,
-                  method: str = "cmlpl", teacher_alpha: Optional[float] = None) -> Dict[str, Any]:
+                  method: str = "cmlpl", teacher_alpha: Optional[float] = None, aug_spatial: str = "none") -> Dict[str, Any]:
     """the record ``check_identity`` compares: plain dicts and numbers (``NetShape`` / ``HyperParams`` by field).  The
     training ``method`` is part of it; a CMLPL record carries no ``method`` key (what it held before there was a second
     method: such files still load, and a record without the key reads as ``cmlpl``).  ``teacher_alpha``: the coefficient of
-    an engine that keeps an EMA teacher -- a key only such an engine's record has (without one the record is what it was)."""
+    an engine that keeps an EMA teacher -- a key only such an engine's record has (without one the record is what it was).
+    ``aug_spatial``: the flip / rotate augmentation of the cube-fed step, a key only when it is not "none"."""
     from dataclasses import asdict
     rec = dict(shape={k: int(v) for k, v in asdict(shape).items()},
                hp={k: (int(v) if isinstance(v, int) and not isinstance(v, bool) else float(v)) for k, v in asdict(hp).items()},
@@ -45,6 +46,8 @@ def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_has
         rec["method"] = str(method)
     if teacher_alpha is not None:
         rec["teacher_alpha"] = float(teacher_alpha)
+    if aug_spatial != "none":
+        rec["aug_spatial"] = str(aug_spatial)
     return rec
 
 
@@ -59,6 +62,8 @@ def identity_differences(saved: Dict[str, Any], mine: Dict[str, Any]) -> List[st
     out = []
     if identity_method(saved) != identity_method(mine):
         out.append(f"method: file {identity_method(saved)!r}, here {identity_method(mine)!r}")
+    if saved.get("aug_spatial", "none") != mine.get("aug_spatial", "none"):
+        out.append(f"aug_spatial: file {saved.get('aug_spatial', 'none')!r}, here {mine.get('aug_spatial', 'none')!r}")
     for group in ("shape", "hp"):
         a, b = saved.get(group, {}), mine.get(group, {})
         for k in sorted(set(a) | set(b)):

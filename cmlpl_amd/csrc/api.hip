@@ -501,7 +501,7 @@ namespace {
 int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_batch* batch, const cmlpl_shard* shard,
                  const float* d_params, const float* d_packed, const float* d_dropmask, int train, uint64_t seed,
                  uint64_t step, float* d_logits, float* d_feat, float* d_labels_f, void* d_workspace,
-                 size_t workspace_bytes, void* stream, DynRef dyn, int parts = 3) {
+                 size_t workspace_bytes, void* stream, DynRef dyn, int parts = 3, int sym_mode = 0) {
   Dims d;
   cmlpl_layout_t L;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
@@ -556,7 +556,7 @@ int forward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_
         (rc = TIMED(CMLPL_K_CUBE_FEED, chk(launch_cube_feed(batch->d_cube, batch->cube_rows, batch->cube_cols, d.C, d.W,
                                   (const long long*)batch->d_lab_pix, (const long long*)batch->d_unl_pix, batch->bt,
                                   batch->btu, lab0, unl_base, batch->noise8, hp->noise_sigma, seed, step, sw.xn, &sel,
-                                  st))))) return rc;
+                                  st, sym_mode))))) return rc;
     return fwd_core(d, r, L, 2, n, d_params, L.param_total, d_packed,
                     xsrc_plain(sw.xn, 2, n, (long long)d.C * d.HW, seed, step, shard, dyn),
                     spe_fused ? &xspec : nullptr, sw.sn, (const long long*)batch->d_labels, d_labels_f, sw.xn, sw.sn,
@@ -900,8 +900,13 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
       !io->d_packed || !io->d_logits || !io->d_feat || !io->d_scalars || !io->d_labels)
     return CMLPL_E_ARG;
   if (io->apply_update && (!io->d_m || !io->d_v)) return CMLPL_E_ARG;
-  if (io->reserved != CMLPL_METHOD_CMLPL && io->reserved != CMLPL_METHOD_CPS) return CMLPL_E_ARG;
-  const bool cps = io->reserved == CMLPL_METHOD_CPS;
+  // reserved: bits 0..7 the method, bits 8..9 the spatial augmentation of the cube-fed rows (CMLPL_SYM_*), no other bit
+  const int method = io->reserved & 0xff, sym_mode = (io->reserved >> 8) & 3;
+  if ((io->reserved & ~0x3ff) != 0 || sym_mode > CMLPL_SYM_D4 ||
+      (method != CMLPL_METHOD_CMLPL && method != CMLPL_METHOD_CPS))
+    return CMLPL_E_ARG;
+  if (sym_mode != CMLPL_SYM_NONE && io->d_cube == nullptr) return CMLPL_E_ARG;
+  const bool cps = method == CMLPL_METHOD_CPS;
   const int n = io->bt + io->btu;
   NetRoute r;
   NetWs nw;
@@ -919,7 +924,8 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
                              io->d_lab_idx, io->d_unl_idx, io->d_cube, io->cube_rows, io->cube_cols, io->d_lab_pix,
                              io->d_unl_pix};
   if ((rc = forward_impl(shape, hp, &batch, &sh, io->d_params, io->d_packed, io->d_dropmask, train, io->seed,
-                         io->step, io->d_logits, io->d_feat, nullptr, io->d_workspace, io->workspace_bytes, stream, dyn)))
+                         io->step, io->d_logits, io->d_feat, nullptr, io->d_workspace, io->workspace_bytes, stream, dyn, 3,
+                         sym_mode)))
     return rc;
   const RowSel sel = batch_sel(&batch, dyn);
   if (cps) {
@@ -1073,6 +1079,11 @@ int cmlpl_extract_patches(const float* d_cube, int rows, int cols, int C, int w,
 // augmentation (include/cmlpl.h, "THE DEFINITION OF A VIEW"; sigma == 0: exactly the clean call's launches and writes).
 // Workspace: y = relu(feat_spe(spectrum)) [nets][n][1024], then -- a view call -- the view's spectra rows [n][bands].
 static bool view_args_ok(float sigma) { return sigma >= 0.f && sigma <= 3.0e38f; }   // (a NaN fails both)
+// the spatial element of a view ("THE DEFINITION OF A SPATIAL ELEMENT"): 0, or the error of one a h x w window does not take
+static int view_sym_check(uint32_t sym, int h, int w) {
+  if (sym > 7u) return CMLPL_E_ARG;
+  return ((sym & 4u) && h != w) ? CMLPL_E_SHAPE : 0;
+}
 
 static size_t infer_y_bytes(int nets, int n) { return up256((size_t)nets * n * 1024 * 4); }
 
@@ -1089,10 +1100,12 @@ static int infer_impl(const cmlpl_shape* shape, int nets, const float* d_params,
                       float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, const ViewKey* view) {
   Dims d;
   cmlpl_layout_t L;
+  if (view && view->sym > 7u) return CMLPL_E_ARG;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
   if (!d_params || !d_packed || !d_cube || !d_spectra || !d_labels || !d_workspace || rows < 1 || cols < 1 || n < 1 ||
       (view && !view_args_ok(view->sigma)))
     return CMLPL_E_ARG;
+  if (view) if (int src = view_sym_check(view->sym, d.H, d.W)) return src;
   if (listed ? (!d_pix || nets < 1 || nets > 2 || rows < d.H / 2 || cols < d.W / 2 ||
                 (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
              : (pixel0 < 0 || pixel0 + n > (int64_t)rows * cols))
@@ -1102,7 +1115,7 @@ static int infer_impl(const cmlpl_shape* shape, int nets, const float* d_params,
   const bool big = (int64_t)rows * cols * d.C >= (1LL << 31);                  // (the gather's 32-bit offsets)
   if (listed && big) return CMLPL_E_ARG;
   if (infer_workspace(shape, nets, n, view != nullptr) > workspace_bytes) return CMLPL_E_WORKSPACE;
-  if (view && view->sigma == 0.f) view = nullptr;      // the clean forward, its launches and its bytes
+  if (view && view->sigma == 0.f && view->sym == 0u) view = nullptr;      // the clean forward, its launches and its bytes
   if (view && !listed && (big || d.W / 2 > rows || d.W / 2 > cols)) return CMLPL_E_ARG;   // (what the launcher refuses)
   hipStream_t st = (hipStream_t)stream;
   float* y = (float*)d_workspace;
@@ -1150,13 +1163,31 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
                     d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, nullptr);
 }
 
+int cmlpl_infer_cube_tta_sym(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
+                             int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
+                             float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, float sigma,
+                             uint64_t seed, uint32_t view, uint32_t sym) {
+  const ViewKey key = {sigma, seed, view, sym};
+  return infer_impl(shape, 1, d_params, 0, d_packed, 0, d_cube, rows, cols, d_spectra, false, nullptr, nullptr, pixel0, n,
+                    d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
+}
+
 int cmlpl_infer_cube_tta(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
                          int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
                          float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, float sigma,
                          uint64_t seed, uint32_t view) {
-  const ViewKey key = {sigma, seed, view};
-  return infer_impl(shape, 1, d_params, 0, d_packed, 0, d_cube, rows, cols, d_spectra, false, nullptr, nullptr, pixel0, n,
-                    d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
+  return cmlpl_infer_cube_tta_sym(shape, d_params, d_packed, d_cube, rows, cols, d_spectra, pixel0, n, d_labels, d_logits,
+                                  d_workspace, workspace_bytes, stream, sigma, seed, view, 0);
+}
+
+int cmlpl_infer_pixels_tta_sym(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                               const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                               const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                               int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes,
+                               void* stream, float sigma, uint64_t seed, uint32_t view, uint32_t sym) {
+  const ViewKey key = {sigma, seed, view, sym};
+  return infer_impl(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra, true,
+                    d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
 }
 
 int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
@@ -1164,19 +1195,27 @@ int cmlpl_infer_pixels_tta(const cmlpl_shape* shape, int nets, const float* d_pa
                            const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
                            int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
                            float sigma, uint64_t seed, uint32_t view) {
-  const ViewKey key = {sigma, seed, view};
-  return infer_impl(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols, d_spectra, true,
-                    d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, &key);
+  return cmlpl_infer_pixels_tta_sym(shape, nets, d_params, param_stride, d_packed, packed_stride, d_cube, rows, cols,
+                                    d_spectra, d_spec_row, d_pix, n, d_labels, d_logits, d_workspace, workspace_bytes, stream,
+                                    sigma, seed, view, 0);
 }
 
 int cmlpl_tta_patches(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
                       float* d_out, const float* d_spectra, const int64_t* d_spec_row, int bands, float* d_spectra_out,
                       float sigma, uint64_t seed, uint32_t view, void* stream) {
+  return cmlpl_tta_patches_sym(d_cube, rows, cols, C, w, d_pixel_idx, n, d_out, d_spectra, d_spec_row, bands, d_spectra_out,
+                               sigma, seed, view, stream, 0);
+}
+
+int cmlpl_tta_patches_sym(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
+                          float* d_out, const float* d_spectra, const int64_t* d_spec_row, int bands, float* d_spectra_out,
+                          float sigma, uint64_t seed, uint32_t view, void* stream, uint32_t sym) {
+  if (sym > 7u) return CMLPL_E_ARG;      // (the windows are square: every element applies)
   if (!d_pixel_idx || (!d_out && !d_spectra_out) || rows < 1 || cols < 1 || n < 1 || !view_args_ok(sigma)) return CMLPL_E_ARG;
   if (d_out && (!d_cube || C < 1 || w < 1)) return CMLPL_E_ARG;
   if (d_spectra_out && (!d_spectra || bands < 1)) return CMLPL_E_ARG;
   if (d_out && (w / 2 > rows || w / 2 > cols || tta_patches_lds(C, w) > LDS_MAX)) return CMLPL_E_SHAPE;
-  const ViewKey key = {sigma, seed, view};
+  const ViewKey key = {sigma, seed, view, sym};
   int rc;
   if (d_out && (rc = chk(launch_tta_patches(d_cube, rows, cols, C, w, (const long long*)d_pixel_idx, n, d_out, key,
                                             (hipStream_t)stream)))) return rc;

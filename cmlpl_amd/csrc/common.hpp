@@ -171,6 +171,16 @@ constexpr uint32_t STREAM_DROPOUT = 0x300;    // + net
 // the views of test-time augmentation (include/cmlpl.h, "views"): the same for every network, disjoint from the training streams
 constexpr uint32_t STREAM_TTA_XP = CMLPL_STREAM_TTA_XP;   // 0x400: windows
 constexpr uint32_t STREAM_TTA_X = CMLPL_STREAM_TTA_X;     // 0x500: spectra
+// the spatial element of a training row (include/cmlpl.h, "THE DEFINITION OF A SPATIAL ELEMENT"): the same for both networks
+constexpr uint32_t STREAM_SYM = CMLPL_STREAM_SYM;         // 0x600
+
+// Spatial element g (0..7) of an h x w window (h == w where g transposes): output position (i, j) takes the window's own
+// position (si, sj).  g == 0 is the identity; every operand but (i, j) is uniform where g is.
+__device__ __forceinline__ void sym_source(int g, int h, int w, int i, int j, int& si, int& sj) {
+  const int a = (g & 4) ? j : i, b = (g & 4) ? i : j;
+  si = (g & 2) ? h - 1 - a : a;
+  sj = (g & 1) ? w - 1 - b : b;
+}
 
 // Counter of the Philox block that carries the noise of elements 4g .. 4g+3 of one sample's patch (or spectrum):
 // (GLOBAL sample index, group) -- the same in the augmentation kernel, the fused forward and the fused data

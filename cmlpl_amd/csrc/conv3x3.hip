@@ -157,7 +157,8 @@ struct Conv3Args {
   const float* w0t; const float* b0; float* a0out;
   long long w0t_ns, b0_ns;
   int C;
-  float* xn_out;                                  // MODE 2, optional: the augmented rows [net][n][C*HW], kept for the backward pass
+  int sym;                                        // TTA views: the spatial element 0..7 (in what was padding: no other field's kernel-argument offset moves)
+  float* xn_out;                                 // MODE 2, optional: the augmented rows [net][n][C*HW], kept for the backward pass
   // MODE 3 (conv0 weight gradient fused into the conv1 data gradient): da0 never leaves the workgroup; the input
   // slab is re-formed from `xs` (same noise as the forward: counter-based)
   float* part0; long long part0_ns;
@@ -1080,7 +1081,12 @@ __device__ __forceinline__ void conv3_stage(const Conv3Args& a, float* smem, int
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
           const int g = item_g(k), pw = (g < CH4l ? g : 0) >> 2;
-          const int wi = (pw * magicp) >> 16, wj = pw - wi * W;
+          int wi = (pw * magicp) >> 16, wj = pw - wi * W;
+          if constexpr (TTA) {                            // the view's spatial element: window pixel pw shows the window's own T_sym(pw) (H == W when it transposes)
+            int si, sj;
+            sym_source(a.sym, H, W, wi, wj, si, sj);
+            wi = si; wj = sj;
+          }
           int rr = pr + wi - (H >> 1), cc = pc + wj - hwin;
           rr = rr < 0 ? -rr - 1 : (rr >= a.crows ? 2 * a.crows - 1 - rr : rr);
           cc = cc < 0 ? -cc - 1 : (cc >= a.ccols ? 2 * a.ccols - 1 - cc : cc);
@@ -3393,8 +3399,11 @@ hipError_t launch_conv3_infer(const Conv3Variant& v, int n, int C, int H, int W,
     a.pix = nn->pix;
   }
   const dim3 grid(8 * ((n + 7) / 8), nets);
-  if (view != nullptr && view->sigma != 0.f) {      // a noisy view: the entries of their own (sigma == 0 is the clean launch)
-    a.xs.sigma = view->sigma; a.xs.seed = view->seed; a.xs.step = view->view;
+  if (view != nullptr && view->sym > 7u) return hipErrorInvalidValue;
+  if (view != nullptr && (view->sym & 4u) && H != W) return hipErrorInvalidValue;
+  // a noisy or a transformed view: the entries of their own (sigma == 0 with the identity is the clean launch)
+  if (view != nullptr && (view->sigma != 0.f || view->sym != 0u)) {
+    a.xs.sigma = view->sigma; a.xs.seed = view->seed; a.xs.step = view->view; a.sym = (int)view->sym;
     return launch_conv3_variant(2, a.pix != nullptr ? 5 : 4, v, a, grid, st);
   }
   return launch_conv3_variant(2, a.pix != nullptr ? 3 : 2, v, a, grid, st);

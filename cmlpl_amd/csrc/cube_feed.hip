@@ -13,6 +13,10 @@
 //            the fused forward form from the same counters), or the explicit draws of parity mode are read; one row is
 //            stored per network, 16 bytes at a time.  (The tile reads of a wave hit 4 banks -- lane stride 8 pixels --
 //            which costs ~1.5 k LDS cycles per row against ~5 k cycles of generator work per SIMD: not the bound.)
+//            With a spatial mode (sym_mask: include/cmlpl.h, "THE DEFINITION OF A SPATIAL ELEMENT") the row takes one
+//            element g of the dihedral group -- one hash call per workgroup, the same for both networks -- and output
+//            pixel pix reads the tile at T_g(pix): the gather above stays the contiguous one, the noise stays keyed by
+//            the output position, and without a mode (g == 0, uniform) the reads are the ones they were.
 // The forward then takes xn as already-augmented plain rows (xsrc_plain) and does not write it again; the backward reads
 // it as it always does.
 #include "common.hpp"
@@ -28,6 +32,7 @@ struct CubeFeedArgs {
   int bt, btu, lab0, unl_base;                            // local rows and their global sample indices
   float sigma; uint64_t seed, step;
   RowSel sel;
+  int sym_mask;                                           // spatial elements per row less one: 0 none, 3 flips, 7 d4 (include/cmlpl.h)
 };
 
 __device__ __forceinline__ int mirror_index(int v, int n) { return v < 0 ? -v - 1 : (v >= n ? 2 * n - 1 - v : v); }
@@ -122,13 +127,27 @@ __global__ __launch_bounds__(512) void cube_feed_kernel(CubeFeedArgs a) {
   if (expl) { nz0 += (long long)sl * per; nz1 += (long long)sl * per; }
   float* d0 = a.xn + (long long)s * per;
   float* d1 = d0 + n_all * per;
+  // the row's spatial element (workgroup-uniform, the same for both networks): output pixel pix reads the tile at
+  // T_g(pix); the noise below stays keyed by the output position
+  int g = 0;
+  if (a.sym_mask != 0)
+    g = __builtin_amdgcn_readfirstlane((int)((noise_hash(a.seed, rstep, STREAM_SYM, noise_ctr(gs, 0)).x >> 29) & (uint32_t)a.sym_mask));
   for (int p = tid; p < npair; p += 512) {
     const int e0 = 8 * p;
     int ch = e0 / ww, pix = e0 - ch * ww;
+    int wi = 0, wj = 0;
+    if (g != 0) { wi = pix / w; wj = pix - wi * w; }
     float x[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      x[q] = tile[(e0 + q < per) ? pix * CS + ch : 0];
+      int sp = pix;
+      if (g != 0) {
+        int si, sj;
+        sym_source(g, w, w, wi, wj, si, sj);
+        sp = si * w + sj;
+        if (++wj == w) { wj = 0; if (++wi == w) wi = 0; }
+      }
+      x[q] = tile[(e0 + q < per) ? sp * CS + ch : 0];
       if (++pix == ww) { pix = 0; ++ch; }
     }
     const bool full = e0 + 8 <= per;
@@ -176,9 +195,9 @@ size_t cube_feed_lds(int C, int w) { return (size_t)w * w * (C | 1) * 4; }
 hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w, const long long* lab_pix,
                             const long long* unl_pix, int bt, int btu, int lab0, int unl_base,
                             const float* const* noise8, float sigma, uint64_t seed, uint64_t step, float* xn,
-                            const RowSel* sel, hipStream_t st) {
+                            const RowSel* sel, hipStream_t st, int sym_mode) {
   const size_t lds = cube_feed_lds(C, w);
-  if (lds > LDS_MAX || bt + btu < 1) return hipErrorInvalidValue;
+  if (lds > LDS_MAX || bt + btu < 1 || sym_mode < 0 || sym_mode > 2) return hipErrorInvalidValue;
   static DevOnce attr_once;
   {
     hipError_t e = ensure_max_lds(attr_once, cube_feed_kernel);
@@ -194,6 +213,7 @@ hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w,
   a.xn = xn; a.bt = bt; a.btu = btu; a.lab0 = lab0; a.unl_base = unl_base;
   a.sigma = sigma; a.seed = seed; a.step = step;
   a.sel = sel != nullptr ? *sel : RowSel();
+  a.sym_mask = sym_mode == 0 ? 0 : (sym_mode == 1 ? 3 : 7);
   hipLaunchKernelGGL(cube_feed_kernel, dim3(bt + btu), dim3(512), lds, st, a);
   return hipGetLastError();
 }

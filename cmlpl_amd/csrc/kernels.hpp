@@ -103,7 +103,7 @@ size_t cube_feed_lds(int C, int w);
 hipError_t launch_cube_feed(const float* cube, int rows, int cols, int C, int w, const long long* lab_pix,
                             const long long* unl_pix, int bt, int btu, int lab0, int unl_base,
                             const float* const* noise8, float sigma, uint64_t seed, uint64_t step, float* xn,
-                            const RowSel* sel, hipStream_t st);
+                            const RowSel* sel, hipStream_t st, int sym_mode = 0 /* 0 none, 1 flips, 2 d4: a spatial element per row */);
 
 // ---- conv3x3.hip
 hipError_t launch_pack_weights(int nets, const float* params, long long pstride, const PackInfo& pi, float* packed,
@@ -156,7 +156,8 @@ hipError_t launch_conv3_fused(const NetRoute& r, int nets, int n, int C, int H, 
 // and, when pix is set, sample s = scene pixel pix[s].
 struct InferNets { int nets; long long param_ns, packed_ns; const long long* pix; };
 // view `view` of every scene pixel under (seed, sigma) -- test-time augmentation, include/cmlpl.h; sigma == 0: the clean window
-struct ViewKey { float sigma; uint64_t seed; uint32_t view; };
+// sym: the view's spatial element 0..7 (include/cmlpl.h, "THE DEFINITION OF A SPATIAL ELEMENT"); with sym != 0, sigma == 0 is a view of its own
+struct ViewKey { float sigma; uint64_t seed; uint32_t view; uint32_t sym = 0; };
 hipError_t launch_conv3_infer(const Conv3Variant& v /* route_infer */, int n, int C, int H, int W, const float* cube, int crows, int ccols, long long pix0,
                               const float* w0t, const float* b0, const float* wpk, const float* bias, const FwdTail& t,
                               long long* labels_out, hipStream_t st, const InferNets* nn = nullptr, const ViewKey* view = nullptr);

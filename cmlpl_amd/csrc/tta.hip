@@ -3,7 +3,8 @@
 // slab (conv3x3.hip: conv3x3_kernel with TAIL 4 / 5) and never needs the window tensor; these two kernels serve
 //   tta_patches_kernel : the by-patches path (windows the fused forward does not take, the reference's 20 x 20 x 60) and
 //                        whoever wants to LOOK at a view -- cmlpl_extract_patches plus the view's noise,
-//                        out[s][ch][i][j] = cube[mirror(r + i - hw)][mirror(c + j - hw)][ch] + sigma z
+//                        out[s][ch][i][j] = cube[mirror(r + i' - hw)][mirror(c + j' - hw)][ch] + sigma z,
+//                        (i', j') = the view's spatial element applied to (i, j) (sym_source; the identity by default)
 //   tta_spectra_kernel : the spectral branch's rows of a view, [n][bands], into the workspace in front of launch_spe_fwd.
 // One workgroup per list entry.  The gather's item is EIGHT consecutive bands of one window pixel -- contiguous in the
 // band-last cube, and by the definition one hash call (noise_normal8: pair p QP / 2 + octet) -- into an LDS tile
@@ -18,6 +19,7 @@ struct TtaPatchArgs {
   const long long* pix; int n;
   float* out;
   float sigma; uint64_t seed; uint32_t view;
+  int sym;                                                // the view's spatial element, 0..7
 };
 
 __global__ __launch_bounds__(256) void tta_patches_kernel(TtaPatchArgs a) {
@@ -35,7 +37,9 @@ __global__ __launch_bounds__(256) void tta_patches_kernel(TtaPatchArgs a) {
   const float sigma = a.sigma;
   for (int it = tid; it < ww * NO; it += 256) {
     const int p = it / NO, o = it - p * NO, i = p / w, j = p - i * w;
-    int rr = r + i - hw, cc = c + j - hw;
+    int si, sj;                                             // output pixel p shows the window's own pixel T_sym(p); the noise stays keyed by p
+    sym_source(a.sym, w, w, i, j, si, sj);
+    int rr = r + si - hw, cc = c + sj - hw;
     rr = rr < 0 ? -rr - 1 : (rr >= rows ? 2 * rows - 1 - rr : rr);
     cc = cc < 0 ? -cc - 1 : (cc >= cols ? 2 * cols - 1 - cc : cc);
     const float* src = a.cube + ((long long)rr * cols + cc) * C;
@@ -98,7 +102,7 @@ hipError_t launch_tta_patches(const float* cube, int rows, int cols, int C, int 
   }
   TtaPatchArgs a;
   a.cube = cube; a.rows = rows; a.cols = cols; a.C = C; a.w = w; a.pix = pix; a.n = n; a.out = out;
-  a.sigma = view.sigma; a.seed = view.seed; a.view = view.view;
+  a.sigma = view.sigma; a.seed = view.seed; a.view = view.view; a.sym = (int)(view.sym & 7u);
   hipLaunchKernelGGL(tta_patches_kernel, dim3(n), dim3(256), lds, st, a);
   return hipGetLastError();
 }

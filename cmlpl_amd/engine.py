@@ -43,6 +43,11 @@ def _chk_f32(t: torch.Tensor, shape, name):
                          f"got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+def check_spatial(mode: str) -> str:
+    _lib.spatial_elements(mode)
+    return mode
+
+
 class Teacher:
     """The averaged weights of an engine built with ``teacher_alpha`` (``eng.teacher``), with what
     ``cmlpl_amd.infer._nets_buffers`` / ``_net_buffers`` read from an engine: ``(eng.teacher, None)`` and
@@ -97,6 +102,13 @@ class TrainEngine:
     ``batch_index`` of ``step`` play no part, ``hp.w_mutual`` is set to the reference's cross-loss weight 0.1, and
     ``loss_row`` / ``loss_window`` give the reference's row ``[con, total, cls, con, acc]`` (trian_CPS.py:254-258).
 
+    ``aug_spatial``: flip / rotate augmentation of the CUBE-FED step's windows -- "flips" (4 elements, the reference's
+    ``flip``) or "d4" (8: ``flip`` after ``Random_rot``, hsi_loader.py:58-88): every batch row takes one spatial element,
+    a function of (seed, step, global sample) alone and the same for both networks (``include/cmlpl.h``, "THE DEFINITION
+    OF A SPATIAL ELEMENT"), applied inside the gather launch -- no window tensor exists.  Eager and captured steps, both
+    methods; a split-fed step of such an engine raises.  "none" (the default): the step and a checkpoint are what they are
+    without the feature.
+
     ``teacher_alpha``: keep an exponential moving average of both networks' weights, the reference's
     ``WeightEMA_BN(Base, Ensemble, alpha)`` (tools/models.py:155-164) applied to the whole flat parameter block -- dead
     tensors and padding too -- behind every step that applies its update: one ``cmlpl_ema_update`` launch on the step's
@@ -110,8 +122,10 @@ class TrainEngine:
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
-                 hist_rows: int = 1, method: str = "cmlpl", teacher_alpha: Optional[float] = None):
+                 hist_rows: int = 1, method: str = "cmlpl", teacher_alpha: Optional[float] = None,
+                 aug_spatial: str = "none"):
         self.method = check_method(method)
+        self.aug_spatial = check_spatial(aug_spatial)
         if teacher_alpha is not None and not 0.0 <= float(teacher_alpha) <= 1.0:       # (a NaN fails both comparisons)
             raise ValueError(f"teacher_alpha {teacher_alpha!r}: a coefficient in [0, 1]")
         self.teacher_alpha = None if teacher_alpha is None else float(teacher_alpha)
@@ -279,7 +293,8 @@ class TrainEngine:
         W = getattr(self, "world", 1)
         return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
                              self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method,
-                             teacher_alpha=getattr(self, "teacher_alpha", None))
+                             teacher_alpha=getattr(self, "teacher_alpha", None),
+                             aug_spatial=getattr(self, "aug_spatial", "none"))
 
     def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
         """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
@@ -473,7 +488,13 @@ class TrainEngine:
         io.d_logits, io.d_feat = self.logits.data_ptr(), self.feat.data_ptr()
         io.d_workspace, io.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         io.seed = self.seed
-        io.reserved = _lib.METHODS[self.method]        # cmlpl_step_io.reserved: the method (0 = CMLPL)
+        # cmlpl_step_io.reserved: the method (0 = CMLPL) in bits 0..7, the spatial augmentation (0 = none) in bits 8..9
+        io.reserved = _lib.METHODS[self.method] | (_lib.SPATIAL[getattr(self, "aug_spatial", "none")] << 8)
+
+    def _refuse_split_fed(self) -> None:
+        if getattr(self, "aug_spatial", "none") != "none":
+            raise ValueError(f"aug_spatial={self.aug_spatial!r} needs cube-fed steps (cube=, lab_pix=, unl_pix=): the "
+                             "window's spatial element is applied in the gather from the scene")
 
     def _advance(self, n, apply_update=True):
         """host copy of the step bookkeeping: bank pointers (train.py:234,237 -- ptr1 follows ptr0, reference quirk
@@ -516,6 +537,7 @@ class TrainEngine:
                 raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
             bt, btu = self._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx)
         else:
+            self._refuse_split_fed()
             bt, btu = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
         if _CHECK_INDICES and lab_idx is not None:
             self.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
@@ -631,6 +653,8 @@ class StepGraph:
                  cube=None, lab_pix=None, unl_pix=None):
         import numpy as np
         self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
+        if cube is None and lab_pix is None and unl_pix is None:
+            eng._refuse_split_fed()
         if lab_idx is None or unl_idx is None:
             raise ValueError("a captured step reads its rows through index buffers")
         if lab_idx.shape[0] < bt or unl_idx.shape[0] < btu:

@@ -140,7 +140,7 @@ def _first_max(z):
 
 class _Forward:
     """The eval forward of one chunk of a feed (``_Range`` or ``_List``) for a clean call (key None) or a view key (sigma,
-    seed, view) when ``views``.  Asks the library once whether the window shape is fused, and owns what either way needs
+    seed, view, spatial element) when ``views``.  Asks the library once whether the window shape is fused, and owns what either way needs
     for chunks of up to ``self.chunk`` pixels: the
     fused calls' workspace (``nets``: the most networks one group holds), or -- windows of more than 256 pixels, the
     reference's 20 x 20 -- the by-patches buffers: ``chunk`` (4096 at the most) windows cut on the device
@@ -158,10 +158,10 @@ class _Forward:
         if pixel0 is not None:
             if nets != 1:
                 raise ValueError("the range-fed forward takes one network per call")
-            self.name = "cmlpl_infer_cube_tta" if views else "cmlpl_infer_cube"
+            self.name = "cmlpl_infer_cube_tta_sym" if views else "cmlpl_infer_cube"
             need = (lib.cmlpl_infer_tta_workspace_bytes if views else lib.cmlpl_infer_workspace_bytes)(C.byref(cs), chunk)
         else:
-            self.name = "cmlpl_infer_pixels_tta" if views else "cmlpl_infer_pixels"
+            self.name = "cmlpl_infer_pixels_tta_sym" if views else "cmlpl_infer_pixels"
             need = (lib.cmlpl_eval_tta_workspace_bytes if views else lib.cmlpl_eval_workspace_bytes)(C.byref(cs), nets, chunk)
         self.fused = need > 0
         if self.fused:
@@ -199,10 +199,10 @@ class _Forward:
                 self.rows_x = self.spectra[o:o + m] if sr is None else self.spectra[sr[o:o + m]].contiguous()
                 self.x_ptr = self.rows_x.data_ptr()
         else:
-            _lib.check("cmlpl_tta_patches", self.lib.cmlpl_tta_patches(
+            _lib.check("cmlpl_tta_patches_sym", self.lib.cmlpl_tta_patches_sym(
                 cube.data_ptr(), rows, cols, cs.C, cs.H, self.pix.data_ptr() + 8 * o, m, self.xp.data_ptr(),
                 self.spectra.data_ptr() + (0 if sr is not None else 4 * cs.bands * o),
-                None if sr is None else sr.data_ptr() + 8 * o, cs.bands, self.x.data_ptr(), *key, st))
+                None if sr is None else sr.data_ptr() + 8 * o, cs.bands, self.x.data_ptr(), *key[:3], st, key[3]))
             self.x_ptr = self.x.data_ptr()
 
     def run(self, group, key, o: int, m: int, labels, logits, at: int) -> None:

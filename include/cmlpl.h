@@ -356,7 +356,9 @@ typedef struct cmlpl_step_io {
   uint64_t seed, step;          /* key / counter of the in-kernel random streams         */
   int32_t apply_update;         /* 0 = stop after the gradients                          */
   int32_t reserved;             /* the training METHOD (named after ABI 6, no bump: every earlier caller passes 0):
-                                   CMLPL_METHOD_CMLPL = 0, CMLPL_METHOD_CPS = 1 -- see cmlpl_cps_loss_fwd_bwd     */
+                                   CMLPL_METHOD_CMLPL = 0, CMLPL_METHOD_CPS = 1 -- see cmlpl_cps_loss_fwd_bwd --
+                                   in bits 0..7; bits 8..9: the spatial augmentation of a cube-fed step's rows,
+                                   CMLPL_SYM_NONE / _FLIPS / _D4 ("THE DEFINITION OF A SPATIAL ELEMENT"); no other bit */
   /* ABI 3 */
   const int64_t* d_lab_idx; const int64_t* d_unl_idx;   /* as in cmlpl_batch; NULL = consecutive rows */
   const cmlpl_dyn* d_dyn_table; int32_t* d_dyn_cursor;   /* NULL = the by-value fields above are used  */
@@ -644,6 +646,55 @@ int cmlpl_tta_patches(const float* d_cube, int rows, int cols, int C, int w, con
 int cmlpl_ensemble_views(const float* d_logits, int members, int views, int64_t member_stride, int64_t view_stride,
                          const float* weights, int n, int K, int64_t* d_labels, float* d_probs, float* d_conf,
                          float* d_entropy, int32_t* d_disagree, void* stream);
+
+/* Added after ABI 6, no bump (no struct and no signature changes) -- SPATIAL AUGMENTATION: flipped and rotated windows
+ * for the cube-fed training step and as views of test-time augmentation (the reference's `flip` and `Random_rot`,
+ * hsi_loader.py:58-88).  No window tensor appears in HBM: a spatial element is a remap of the window index in front of the
+ * source address of the gathers that exist (cube_feed_kernel, the TTA forwards' slab staging, tta_patches_kernel).
+ *
+ * THE DEFINITION OF A SPATIAL ELEMENT.  An element g in 0..7 of the dihedral group D4 acts on the index grid of a square
+ * w x w window `win` -- not on scene offsets: the transformed window is a permutation of the SAME w w scene pixels, for
+ * even w too; no other scene pixel is read and the mirror rule of the margin is untouched:
+ *     out[ch][i][j] = win[ch][i'][j'],   (a, b) = (g & 4) ? (j, i) : (i, j),
+ *                                        i' = (g & 2) ? w - 1 - a : a,
+ *                                        j' = (g & 1) ? w - 1 - b : b
+ *   g = 0  the window as it is                 g = 4  the transpose
+ *   g = 1  flip(-1)  (left-right)              g = 5  the quarter turn rot90(k=1)  (counter-clockwise, numpy / torch)
+ *   g = 2  flip(-2)  (up-down)                 g = 6  the quarter turn rot90(k=3) = rot90(k=-1)  (clockwise)
+ *   g = 3  the rotation by 180 degrees         g = 7  the anti-transpose
+ *   Modes: CMLPL_SYM_NONE  S = 1 (g = 0);  CMLPL_SYM_FLIPS  S = 4, g in 0..3 (the four outcomes of the reference's `flip`);
+ *          CMLPL_SYM_D4  S = 8 (what `flip` after `Random_rot` generates).
+ *   Noise is added AFTER the remap and stays keyed by the OUTPUT position, so no noise stream moves:
+ *     training  x = fmaf(z, sigma, win[T_g(p)]) with the counters of the patch noise as they are;
+ *     a view    the z of window pixel p = i W + j of "THE DEFINITION OF A VIEW".
+ *   The spectrum of a row or of a view is not touched.
+ *   TRAINING.  The row with GLOBAL sample index gs at step counter `step` (the cmlpl_dyn row's in a graph replay) takes
+ *     g = (noise_hash(seed, step, CMLPL_STREAM_SYM, noise_ctr(gs, 0)).x >> 29) & (S - 1)
+ *   (the TOP three bits of the word: noise_ctr leaves the low 24 bits of the counter zero, and the low bits of a pcg4d word
+ *   depend on the low bits of its inputs alone -- `.x & (S - 1)` is one element for 256 consecutive samples)
+ *   -- the same for both networks (they see one geometry and differ in noise and dropout, as the reference's two networks
+ *   read one window), a property of the global sample and so independent of sharding.  The mode travels in
+ *   cmlpl_step_io.reserved, bits 8..9 (cmlpl_train_step, cmlpl_step_graph_create); any bit above 9, a mode of 3, or a mode
+ *   with d_cube == NULL: CMLPL_E_ARG.  The sharded step (cmlpl_dist_step) does not take it.
+ *   TEST-TIME AUGMENTATION.  cmlpl_infer_cube_tta_sym / cmlpl_infer_pixels_tta_sym / cmlpl_tta_patches_sym: the functions
+ *   without _sym plus a trailing element `sym`; those are these with sym = 0.  sigma == 0 with sym != 0 is a view of its
+ *   own, pure geometry (sigma == 0 with sym == 0 stays the clean forward's launches and bytes).  sym > 7: CMLPL_E_ARG;
+ *   H != W with sym & 4: CMLPL_E_SHAPE; both before any launch.  The workspace sizes are those of the functions without
+ *   _sym. */
+enum { CMLPL_STREAM_SYM = 0x600 };
+enum { CMLPL_SYM_NONE = 0, CMLPL_SYM_FLIPS = 1, CMLPL_SYM_D4 = 2 };
+int cmlpl_infer_cube_tta_sym(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
+                             int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
+                             float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream,
+                             float sigma, uint64_t seed, uint32_t view, uint32_t sym);
+int cmlpl_infer_pixels_tta_sym(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                               const float* d_packed, int64_t packed_stride, const float* d_cube, int rows, int cols,
+                               const float* d_spectra, const int64_t* d_spec_row, const int64_t* d_pix, int n,
+                               int64_t* d_labels, float* d_logits, void* d_workspace, size_t workspace_bytes,
+                               void* stream, float sigma, uint64_t seed, uint32_t view, uint32_t sym);
+int cmlpl_tta_patches_sym(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
+                          float* d_out, const float* d_spectra, const int64_t* d_spec_row, int bands, float* d_spectra_out,
+                          float sigma, uint64_t seed, uint32_t view, void* stream, uint32_t sym);
 
 /* ABI 5 -- the scene itself (reference sample_generation.py:21-73 -> tools/hyper_tools.py:285-292 SampleGen): the z-scored
  * PCA cube the two calls above read, and the z-scored spectra, computed on the device from the raw scene in fp64 as numpy

@@ -17,7 +17,9 @@ with the tag ``_ens``; ``--proba`` / ``--confidence`` / ``--entropy`` write the 
 ``train.py --synthetic`` evaluates on (datasets are not shipped).  ``--tta M`` predicts from the clean window and M noisy views
 (x + S N(0,1), S = ``--tta_noise``, default the checkpoint's training noise) of every pixel, averaged over the views and
 over the networks of ``--net`` (any single network or ensemble; cmlpl_amd.tta): the label map, the ``Result:`` lines (tag
-``_tta``) and ``--proba`` / ``--confidence`` / ``--entropy`` then describe that prediction.  ``--smooth R`` smooths the class
+``_tta``) and ``--proba`` / ``--confidence`` / ``--entropy`` then describe that prediction.  ``--tta_spatial flips | d4`` makes
+the views flipped (and rotated) windows as well -- what ``train.py --aug_spatial`` trains on; ``--tta 7 --tta_noise 0
+--tta_spatial d4`` is the plain orbit of the eight elements -- and the tag ``_tta_flips`` / ``_tta_d4``.  ``--smooth R`` smooths the class
 probability maps of that prediction over the scene -- an edge-preserving filter of radius R guided by the cube's leading
 channels (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``), with any single
 network or ensemble, with or without ``--tta``: the ``Result:`` block above is printed as it is, a second one follows with
@@ -30,7 +32,8 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import DATASETS, NET_TAGS, SYNTH, add_smooth_flags, ensemble_whole, evaluate_whole, smooth_of, smooth_whole, tta_whole
+from train import (DATASETS, NET_TAGS, SPATIAL_MODES, SYNTH, add_smooth_flags, ensemble_whole, evaluate_whole, smooth_of,
+                   smooth_whole, tta_tag, tta_whole)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 
@@ -50,8 +53,8 @@ def check_args(args):
             raise SystemExit("--tta_noise S: a finite S >= 0")
         if args.tta_seed < 0 or args.tta_seed >= 2 ** 64:
             raise SystemExit("--tta_seed N: 0 <= N < 2^64")
-    elif args.tta_noise is not None or args.tta_no_clean:
-        raise SystemExit("--tta_noise / --tta_no_clean belong to --tta M")
+    elif args.tta_noise is not None or args.tta_no_clean or args.tta_spatial != 'none':
+        raise SystemExit("--tta_noise / --tta_no_clean / --tta_spatial belong to --tta M")
     if smooth_of(args) is not None and args.net in ('both', 'ema_both'):
         raise SystemExit("--smooth gives ONE prediction: --net %s writes two label maps (name one network, or --net "
                          "ensemble for the two together)" % args.net)
@@ -93,9 +96,9 @@ def main(args, device=None):
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
         tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
-                  clean=not args.tta_no_clean)
+                  clean=not args.tta_no_clean, spatial=args.tta_spatial)
     if smooth is not None and (tta is not None or args.net in ENSEMBLES):
-        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=NET_TAGS['ens' if tta is None else 'tta'],
+        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=NET_TAGS['ens'] if tta is None else tta_tag(tta),
                            raw_block=True, **common, **extras)
     elif tta is not None:
         out = tta_whole(shape, whole, members, device, tta, **common, **extras)
@@ -143,6 +146,10 @@ def build_parser():
                         help="--tta: the views are x + S N(0,1) (default: the checkpoint's training noise)")
     parser.add_argument('--tta_seed', type=int, default=1088, metavar='N', help='--tta: the seed of the views')
     parser.add_argument('--tta_no_clean', action='store_true', help='--tta: the noisy views only, without the clean window')
+    parser.add_argument('--tta_spatial', choices=SPATIAL_MODES, default='none',
+                        help="--tta: the views are also flipped ('flips': 4 elements) or flipped and rotated ('d4': 8) windows, "
+                             "view t under element (t + 1) mod 4 / 8 (t mod 4 / 8 with --tta_no_clean); with --tta_noise 0 pure "
+                             "geometry; the Result: tag becomes _tta_flips / _tta_d4")
     add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')

@@ -36,6 +36,10 @@ Differences from the reference that are deliberate, MI355X-first choices:
     SMOOTHED over the scene -- an edge-preserving filter of radius R guided by the cube's leading principal components
     (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``): one more
     ``Result:`` block (``OA_ens_smooth``).  The run itself is untouched.
+  * ``--aug_spatial flips | d4``: flip (and rotate) augmentation of the training windows, the reference's ``flip`` /
+    ``Random_rot`` (hsi_loader.py:58-88): every batch row takes one element of the dihedral group per step, the same for
+    both networks, applied inside the gather of ``--windows cube`` (which it needs; one GPU).  ``--tta --tta_spatial
+    flips | d4`` scores such views after the run (``OA_tta_flips`` / ``OA_tta_d4``).
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -107,6 +111,8 @@ def run_record(args, hp, shape, from_scene):
         rec["method"] = args.method
     if args.ema:                          # (and a run without a teacher's is what it was before there was one)
         rec.update(ema=True, teacher_alpha=args.teacher_alpha)
+    if args.aug_spatial != "none":        # (and a run on windows as they are)
+        rec["aug_spatial"] = args.aug_spatial
     rec.update(shape=[int(v) for v in shape], data=("synthetic %s%s" % (args.synthetic, " scene" if from_scene else ""))
                if args.synthetic else "dataID %d" % int(args.dataID))
     return rec
@@ -114,13 +120,15 @@ def run_record(args, hp, shape, from_scene):
 
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
-    its sub-flags) is left out at its default, so a file written without it is byte for byte what it was before the flag existed"""
-    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS}}
+    its sub-flags, --aug_spatial, --tta_spatial) is left out at its default, so a file written without it is byte for byte what it
+    was before the flag existed"""
+    late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
+            'aug_spatial': 'none', 'tta_spatial': 'none'}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
 def run_differences(saved, mine):
-    keys = list(mine) + [k for k in ("ema", "teacher_alpha") if k in saved and k not in mine]     # --ema: both ways
+    keys = list(mine) + [k for k in ("ema", "teacher_alpha", "aug_spatial") if k in saved and k not in mine]     # --ema, --aug_spatial: both ways
     return ["%s: file %r, here %r" % (k, saved.get(k), mine.get(k)) for k in keys if saved.get(k) != mine.get(k)]
 
 
@@ -167,6 +175,7 @@ class EvalCurve:
 NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
             'ens': '_ens',                                         # ensemble_whole: several of them together
             'tta': '_tta'}                                         # tta_whole: over noisy views of every pixel
+SPATIAL_MODES = ('none', 'flips', 'd4')                            # --aug_spatial / --tta_spatial (cmlpl_amd._lib.SPATIAL)
 SMOOTH_TAG = '_smooth'                                             # smooth_whole: appended to the tag of what it smooths
 SMOOTH_FLAGS = ('smooth', 'smooth_sigma_s', 'smooth_sigma_r', 'smooth_guide', 'smooth_iters')
 
@@ -201,6 +210,18 @@ def smooth_of(args):
     except ValueError as e:
         raise SystemExit("--smooth: %s" % str(e).replace("Smooth: ", ""))
     return smooth
+
+
+def tta_tag(tta):
+    """the tag of a TTA prediction's ``Result:`` lines: ``_tta``, with ``_flips`` / ``_d4`` behind it when its views are spatial"""
+    return NET_TAGS['tta'] + ('' if tta.spatial == 'none' else '_' + tta.spatial)
+
+
+def tta_timing(tta):
+    """the timing line of a TTA prediction (a format of the seconds and the number of networks)"""
+    return 'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g%s)' % (
+        tta.views, ' + the clean window' if tta.clean else '', tta.sigma,
+        '' if tta.spatial == 'none' else ', spatial ' + tta.spatial)
 
 
 def print_result(tag, pred, test_array, Y_test):
@@ -279,12 +300,11 @@ def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout
               resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
     """``ensemble_whole`` over the noisy views of ``tta`` (cmlpl_amd.tta.TTA): every network of ``nets`` scores every view
     of every scene pixel, one label map from the average of all their softmaxes (cmlpl_amd.tta.tta_cube).  Same returns;
-    the ``Result:`` lines carry the tag ``_tta``."""
+    the ``Result:`` lines carry the tag ``_tta`` (``_tta_flips`` / ``_tta_d4`` when the views are spatial, ``tta_tag``)."""
     from cmlpl_amd.tta import tta_cube
     return together_whole(
         lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy),
-        'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g)' %
-        (tta.views, ' + the clean window' if tta.clean else '', tta.sigma), NET_TAGS['tta'], "test-time augmentation",
+        tta_timing(tta), tta_tag(tta), "test-time augmentation",
         shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
 
 
@@ -302,8 +322,7 @@ def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens
     else:
         from cmlpl_amd.tta import tta_cube
         raw = lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True)
-        timing = 'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g)' % (
-            tta.views, ' + the clean window' if tta.clean else '', tta.sigma)
+        timing = tta_timing(tta)
     R, ss, sr, G, iters = smooth.params()
     return together_whole(
         raw, timing, tag, "spatial smoothing", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
@@ -392,8 +411,9 @@ def build_engine(run, args, make_engine):
         run.eng = DistTrainEngine(NetShape(*run.shape), bt // world, btu // world, hp, device=device, seed=1088, hist_rows=ppb)
     else:
         from cmlpl_amd import TrainEngine
+        spatial = {} if args.aug_spatial == "none" else dict(aug_spatial=args.aug_spatial)
         run.eng = TrainEngine(NetShape(*run.shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=args.method,
-                              teacher_alpha=args.teacher_alpha if args.ema else None)
+                              teacher_alpha=args.teacher_alpha if args.ema else None, **spatial)
     run.eng.init_params_default(1088)
 
 
@@ -405,6 +425,10 @@ def open_resume(run, args):
     if file_method != args.method:
         raise SystemExit("--resume %s: the file was written by --method %s, this run is --method %s" %
                          (args.resume, file_method, args.method))
+    file_spatial = resumed["identity"].get("aug_spatial", "none")
+    if file_spatial != args.aug_spatial:
+        raise SystemExit("--resume %s: the file was written by --aug_spatial %s, this run is --aug_spatial %s" %
+                         (args.resume, file_spatial, args.aug_spatial))
     diff = run_differences(resumed["extra"].get("run", {}), run_record(args, run.hp, run.shape, run.from_scene))
     if diff:
         raise SystemExit("--resume %s: this run differs from the one that wrote the file -- %s" % (args.resume, "; ".join(diff)))
@@ -622,9 +646,22 @@ def report(run, args):
         ensemble_whole(run.shape, run.whole, nets[:2], device, **scene)
     if args.tta:
         from cmlpl_amd.tta import TTA
-        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise), **scene)
+        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise, spatial=args.tta_spatial), **scene)
     if run.smooth is not None:
         smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene)
+
+
+def check_spatial_args(args, world=1):
+    """what --aug_spatial / --tta_spatial cannot mean, said before any device or communicator work"""
+    if args.aug_spatial != "none":
+        if world > 1:
+            raise SystemExit(f"--aug_spatial {args.aug_spatial} runs on one GPU: the sharded step does not take it (this job "
+                             f"has {world} ranks)")
+        if args.windows != "cube":
+            raise SystemExit(f"--aug_spatial {args.aug_spatial} needs --windows cube: the window's spatial element is applied "
+                             "in the gather from the scene")
+    if args.tta_spatial != "none" and not args.tta:
+        raise SystemExit("--tta_spatial belongs to --tta")
 
 
 def main(args, make_engine=None, device=None):
@@ -635,6 +672,7 @@ def main(args, make_engine=None, device=None):
     if args.method != "cmlpl" and world > 1:      # before any device or communicator work
         raise SystemExit(f"--method {args.method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
                          f"{world} ranks)")
+    check_spatial_args(args, world)
     if args.ema and world > 1:
         raise SystemExit(f"--ema runs on one GPU: the sharded engine keeps no EMA teacher (this job has {world} ranks)")
     if device is None:
@@ -711,6 +749,13 @@ def build_parser():
                         help="test-time augmentation after the run: Base and Base1 TOGETHER score the clean window and --m "
                              "noisy views (x + --noise N(0,1)) of every scene pixel, one more Result: block (OA_tta) from "
                              "the average of all their softmaxes; the run itself is untouched")
+    parser.add_argument('--tta_spatial', choices=SPATIAL_MODES, default='none',
+                        help="--tta: the views are also flipped ('flips': 4 elements) or flipped and rotated ('d4': 8) windows, "
+                             "view t under element (t + 1) mod 4 / 8; the Result: tag becomes _tta_flips / _tta_d4")
+    parser.add_argument('--aug_spatial', choices=SPATIAL_MODES, default='none',
+                        help="flip ('flips') or flip-and-rotate ('d4') augmentation of the training windows: every batch row "
+                             "takes one spatial element per step, the same for both networks, applied in the gather from the "
+                             "scene (needs --windows cube; one GPU)")
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')

@@ -7,6 +7,7 @@ Public surface:
   ensemble_logits / _cube / _pixels ... averaged probabilities, label, confidence, entropy of 1..4 networks
   TTA, tta_cube / tta_pixels, views_of ... the same from several noisy views per pixel (test-time augmentation)
   Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
+  PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name in ("Smooth", "smooth_probs", "smooth_cube"):
         from . import smooth
         return getattr(smooth, name)
+    if name in ("PLCounts", "pl_stats_host", "pl_stats_hard_host"):
+        from . import plstats
+        return getattr(plstats, name)
     raise AttributeError(name)

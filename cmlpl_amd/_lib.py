@@ -46,8 +46,10 @@ EXPORTS = (
     "cmlpl_infer_pixels_tta", "cmlpl_tta_patches", "cmlpl_ensemble_views",                           # test-time augmentation
     "cmlpl_smooth_probs",                                                        # added after ABI 6, no bump: spatial smoothing
     "cmlpl_infer_cube_tta_sym", "cmlpl_infer_pixels_tta_sym", "cmlpl_tta_patches_sym",   # added after ABI 6, no bump: flip / rotate views
+    "cmlpl_pl_stats", "cmlpl_pl_stats_hard",                                     # added after ABI 6, no bump: the pseudo-label monitor
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
+PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
 SPATIAL = {"none": 0, "flips": 1, "d4": 2}    # cmlpl_step_io.reserved, bits 8..9 (CMLPL_SYM_*); 1, 4, 8 elements
 
 
@@ -274,6 +276,8 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_tta_patches_sym.argtypes = lib.cmlpl_tta_patches.argtypes + [u32]
     lib.cmlpl_ensemble_views.argtypes = [vp, i32, i32, i64, i64, C.POINTER(f32), i32, i32, vp, vp, vp, vp, vp, vp]
     lib.cmlpl_smooth_probs.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
+    lib.cmlpl_pl_stats.argtypes = [vp, i32, i32, vp, vp, f32, f32, f32, vp, vp]
+    lib.cmlpl_pl_stats_hard.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

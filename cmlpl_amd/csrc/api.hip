@@ -1388,6 +1388,12 @@ int cmlpl_debug_region(const cmlpl_shape* shape, int nets, int n, const char* na
     *byte_offset = (size_t)((const char*)sw.probs - base); *bytes = (size_t)2 * n * 8;
     return 0;
   }
+  if (!strcmp(name, "probs") && nets == 2) {   // a CMLPL step's probabilities: p_w, p_s, p_w0, p_s0 as [4][btu][K] at the region's start (n covers them)
+    StepWs sw;
+    carve_step(d, n, n, base + w.bytes, &sw);
+    *byte_offset = (size_t)((const char*)sw.probs - base); *bytes = (size_t)4 * n * d.K * 4;
+    return 0;
+  }
   return CMLPL_E_ARG;
 }
 

@@ -362,7 +362,7 @@ class DistTrainEngine(TrainEngine):
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, comm=None, hist_rows: int = 1,
-                 alias_single: bool = True, method: str = "cmlpl", aug_spatial: str = "none"):
+                 alias_single: bool = True, method: str = "cmlpl", aug_spatial: str = "none", pl_monitor: bool = False):
         """``alias_single=False`` keeps the REAL collectives at world size 1 (separate send / receive buffers, four
         torch.distributed calls per step): what scripts/dist_overhead.py measures the host cost of the calls with."""
         if method != "cmlpl":      # before any device or communicator work
@@ -370,6 +370,9 @@ class DistTrainEngine(TrainEngine):
         if aug_spatial != "none":
             raise ValueError(f"aug_spatial {aug_spatial!r}: the sharded step does not take a spatial augmentation -- run "
                              "--aug_spatial on one GPU")
+        if pl_monitor:
+            raise ValueError("pl_monitor: the sharded step has no pseudo-label monitor (its counters would need an "
+                             "all-reduce over the ranks) -- run --pl_stats on one GPU")
         if comm is None:
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized()):

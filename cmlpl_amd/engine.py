@@ -116,6 +116,14 @@ class TrainEngine:
     step after construction, ``load_state_dict`` or ``init_params_default`` (``teacher_reset()`` makes it on demand);
     ``eng.teacher`` (``Teacher``) is what evaluates and saves it.  None (the default): no buffer, no launch, and a
     checkpoint is byte for byte what it is without the feature.
+
+    ``pl_monitor``: score every step's pseudo-labels against the TRUTH of its unlabelled rows (``step(..., unl_truth=)``,
+    ``capture(..., unl_truth=)``: the unlabelled split's labels, indexed the way ``Xu`` is) -- one ``cmlpl_pl_stats`` launch
+    (CPS: ``cmlpl_pl_stats_hard`` on the step's hard labels) on the step's stream behind every step, eager or behind a
+    graph replay, adding to a block of int64 counters (include/cmlpl.h, "THE DEFINITION OF THE PSEUDO-LABEL COUNTERS"):
+    ``pl_counts()`` reads it (``cmlpl_amd.plstats.PLCounts``), ``pl_reset()`` zeroes it.  The launch reads what the step has
+    left in its workspace and writes only its own block: the step, captured or not, is the code it is without it.  False
+    (the default): no buffer, no launch.
     """
     takes_indices = True      # step(..., lab_idx=, unl_idx=): batches as row indices into the resident splits
     takes_cube = True         # step(None, Xl, Y, None, Xu, ..., cube=, lab_pix=, unl_pix=): windows gathered from the scene
@@ -123,7 +131,7 @@ class TrainEngine:
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
                  hist_rows: int = 1, method: str = "cmlpl", teacher_alpha: Optional[float] = None,
-                 aug_spatial: str = "none"):
+                 aug_spatial: str = "none", pl_monitor: bool = False):
         self.method = check_method(method)
         self.aug_spatial = check_spatial(aug_spatial)
         if teacher_alpha is not None and not 0.0 <= float(teacher_alpha) <= 1.0:       # (a NaN fails both comparisons)
@@ -183,6 +191,9 @@ class TrainEngine:
         self.teacher_params = z(2, self.P) if self.teacher_alpha is not None else None
         self.teacher = Teacher(self) if self.teacher_alpha is not None else None
         self._teacher_stale = True
+        # the pseudo-label monitor: int64 counts[PL_HEAD + 2 K K], added to by one launch behind every step
+        self.pl_block = torch.zeros(_lib.PL_HEAD + 2 * shape.K * shape.K, dtype=torch.int64, device=dev) if pl_monitor else None
+        self._pl_off = {}           # n -> byte offset of the step's targets inside the workspace (asked of the library)
 
     @property
     def scalars(self) -> torch.Tensor:
@@ -259,6 +270,46 @@ class TrainEngine:
         _lib.check("cmlpl_ema_update", self.lib.cmlpl_ema_update(_ptr(self.params), _ptr(self.teacher_params),
                                                                  2 * self.P, self.teacher_alpha, stream))
         self.teacher._dirty = True
+
+    # ------------------------------------------------------------------ the pseudo-label monitor
+    def _pl_truth(self, unl_truth, rows: int) -> torch.Tensor:
+        if unl_truth is None:
+            raise ValueError("an engine built with pl_monitor scores every step: pass unl_truth (the unlabelled rows' labels)")
+        t = unl_truth
+        if t.dtype != torch.int64 or tuple(t.shape) != (rows,) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"unl_truth: need a contiguous int64 cuda vector, one label per unlabelled row ({rows})")
+        return t
+
+    def _pl_update(self, stream, truth: torch.Tensor, idx_ptr, btu: int, adap_mask: float) -> None:
+        """behind a step of ``self._last_n`` rows: its targets, still in the workspace, against ``truth`` (read at
+        ``idx_ptr[r]``, or at r); ``adap_mask``: the float32 value that step compared with"""
+        n, K = self._last_n, self.shape.K
+        region = "probs" if self.method == "cmlpl" else "cps_pseudo"
+        if n not in self._pl_off:
+            off, nbytes = C.c_size_t(), C.c_size_t()
+            _lib.check("cmlpl_debug_region", self.lib.cmlpl_debug_region(
+                C.byref(self.cshape), 2, n, region.encode(), C.byref(off), C.byref(nbytes)))
+            self._pl_off[n] = int(off.value)
+        src = C.c_void_p(self.workspace.data_ptr() + self._pl_off[n])
+        if self.method == "cmlpl":
+            _lib.check("cmlpl_pl_stats", self.lib.cmlpl_pl_stats(
+                src, btu, K, _ptr(truth), idx_ptr, adap_mask, self._chp.pos_thr, self._chp.neg_thr, _ptr(self.pl_block), stream))
+        else:
+            _lib.check("cmlpl_pl_stats_hard", self.lib.cmlpl_pl_stats_hard(src, btu, K, _ptr(truth), idx_ptr,
+                                                                           _ptr(self.pl_block), stream))
+
+    def pl_counts(self):
+        """the counters since the last ``pl_reset()`` as a ``cmlpl_amd.plstats.PLCounts`` (a synchronising read)"""
+        if self.pl_block is None:
+            raise RuntimeError("pl_counts(): an engine built with pl_monitor")
+        from .plstats import PLCounts
+        return PLCounts(self.pl_block.cpu().numpy(), self.shape.K)
+
+    def pl_reset(self) -> None:
+        """zero the counters (a stream-ordered memset: behind every launch enqueued so far)"""
+        if self.pl_block is None:
+            raise RuntimeError("pl_reset(): an engine built with pl_monitor")
+        self.pl_block.zero_()
 
     def _ensure_packed(self, stream) -> None:
         if self._packed_dirty:
@@ -512,7 +563,7 @@ class TrainEngine:
              dropmask: Optional[torch.Tensor] = None, apply_update: bool = True,
              lab_idx: Optional[torch.Tensor] = None, unl_idx: Optional[torch.Tensor] = None,
              cube: Optional[torch.Tensor] = None, lab_pix: Optional[torch.Tensor] = None,
-             unl_pix: Optional[torch.Tensor] = None) -> None:
+             unl_pix: Optional[torch.Tensor] = None, unl_truth: Optional[torch.Tensor] = None) -> None:
         """One training step; asynchronous.  Results land in ``self.scalars`` (device),
         ``self.logits`` / ``self.feat`` ([2][n][..]) and ``self.grads``.
 
@@ -525,6 +576,8 @@ class TrainEngine:
                    resident scene [rows][cols][C]; the patch row of a batch row is the H x W window (mirror index of
                    ExtractPatches) of scene pixel lab_pix[r] (unl_pix[r]), r = the split row Xl / Y (Xu) are read at.
                    Bit-identical to the step on ``extract_patches(cube, pix)``.
+        unl_truth : an engine built with ``pl_monitor`` only (others ignore it): the labels of the unlabelled rows, int64,
+                   indexed the way Xu is -- the whole split's when unl_idx is given, the batch's otherwise
         """
         s = self.shape
         g = self._graph() if self._graph is not None else None
@@ -543,6 +596,8 @@ class TrainEngine:
             self.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
             self.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
         n = bt + btu
+        if self.pl_block is not None:
+            unl_truth = self._pl_truth(unl_truth, Xu.shape[0] if unl_idx is not None else btu)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._ensure_packed(stream)
         self._teacher_begin()
@@ -575,13 +630,16 @@ class TrainEngine:
             self._teacher_update(stream)
         self._advance(n, apply_update)
         self._last_btu = btu
+        if self.pl_block is not None:     # one launch behind the step, on its stream; io.adap_mask: the float32 the step read
+            self._pl_update(stream, unl_truth, _ptr(unl_idx), btu, io.adap_mask)
 
     def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
-                cube=None, lab_pix=None, unl_pix=None) -> "StepGraph":
+                cube=None, lab_pix=None, unl_pix=None, unl_truth=None) -> "StepGraph":
         """The step captured ONCE as a hipGraph over the resident splits and two index buffers (lab_idx / unl_idx: the
         epoch's permutations, re-filled in place by the caller); see StepGraph.  Cube-fed (cube / lab_pix / unl_pix
-        given, XPl = XPu = None): over the resident scene instead of the window tensors."""
-        return StepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix)
+        given, XPl = XPu = None): over the resident scene instead of the window tensors.  ``unl_truth``: the unlabelled
+        split's labels, for an engine built with ``pl_monitor`` (its launch follows every replay; it is not captured)."""
+        return StepGraph(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix, unl_truth)
 
     def outputs(self):
         """(logits [2][n][K], feat [2][n][1024]) of the last step."""
@@ -650,13 +708,15 @@ class StepGraph:
     """
 
     def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
-                 cube=None, lab_pix=None, unl_pix=None):
+                 cube=None, lab_pix=None, unl_pix=None, unl_truth=None):
         import numpy as np
         self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
+        self._programmed = 0
         if cube is None and lab_pix is None and unl_pix is None:
             eng._refuse_split_fed()
         if lab_idx is None or unl_idx is None:
             raise ValueError("a captured step reads its rows through index buffers")
+        self._pl_truth = eng._pl_truth(unl_truth, Xu.shape[0]) if getattr(eng, "pl_block", None) is not None else None
         if lab_idx.shape[0] < bt or unl_idx.shape[0] < btu:
             raise ValueError("index buffers shorter than one batch")
         for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
@@ -747,7 +807,7 @@ class StepGraph:
         k = (k + 1) * 64
         self.table[:k].copy_(self.host[:k], non_blocking=True)
         self.cursor.fill_(1)
-        self.pending = len(steps)
+        self.pending = self._programmed = len(steps)
         eng._graph = weakref.ref(self)
         # (the pinned staging rows may be rewritten only after that copy has run)
         self._copied = torch.cuda.Event()
@@ -767,6 +827,13 @@ class StepGraph:
         eng._cur_row = eng.step_count % eng.hist_rows
         eng._advance(self.bt + self.btu, True)
         eng._last_btu = self.btu
+        if eng.pl_block is not None:
+            # one eager launch behind the replay: the threshold and the batch's place in the index buffer are those of
+            # the programmed row this replay has just run (the float32 the step read, not a value formed anew)
+            row = self.rows[self._programmed - self.pending]
+            unl_idx = self._keep[6]
+            eng._pl_update(stream, self._pl_truth, C.c_void_p(unl_idx.data_ptr() + 8 * int(row["unl_off"])), self.btu,
+                           float(row["adap_mask"]))
         self.pending -= 1
 
     def close(self) -> None:

@@ -817,7 +817,10 @@ int cmlpl_timing_end(double* ms_sum /*[CMLPL_K_COUNT]*/, int64_t* launches /*[CM
  * masks [nets][n][P][64] u8 (bit (h&1)*2+(w&1) = relu(z) > 0 at that pixel of the 2x2 pool
  * window); "y" spectral ReLU output [nets][n][1024] f32; "catd","dropgen" [nets][n][cls_in];
  * "dy","dp2","dp1","da0" backward intermediates; with nets = 2 also "xn": the augmented patch rows [2][n][C*H*W] a
- * step's forward keeps for its backward (cmlpl_forward / cmlpl_train_step).  Returns CMLPL_E_ARG for an unknown name. */
+ * step's forward keeps for its backward (cmlpl_forward / cmlpl_train_step); "cps_pseudo": a CPS step's hard labels,
+ * int64 [2][btu] at the region's start; "probs": the probability region of cmlpl_train_step, 4 n K floats, of which a
+ * CMLPL step fills the front as [4][btu][K] = p_w, p_s (both smoothed once the gate is open), p_w0, p_s0 (the plain
+ * softmaxes) -- what cmlpl_pl_stats reads.  Returns CMLPL_E_ARG for an unknown name. */
 int cmlpl_debug_region(const cmlpl_shape* shape, int nets, int n, const char* name,
                        size_t* byte_offset, size_t* bytes);
 
@@ -936,6 +939,57 @@ int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, in
 int cmlpl_smooth_probs(const float* d_probs, const float* d_guide, int64_t guide_stride, int guide_ch,
                        int rows, int cols, int K, int radius, float sigma_s, float sigma_r,
                        float* d_out_probs, int64_t* d_labels, float* d_conf, float* d_entropy, void* stream);
+
+/* Added after ABI 6, no bump (nothing existing moves) -- the PSEUDO-LABEL MONITOR: a step's targets scored against the
+ * truth of its unlabelled rows (the reference's loader carries the unlabelled split's labels and never reads them).
+ *
+ * THE DEFINITION OF THE PSEUDO-LABEL COUNTERS.  The counter block is int64 counts[CMLPL_PL_HEAD + 2 K K].  Every launch
+ * ADDS to it and nothing else writes it (the caller zeroes a fresh one).
+ *   Direction d = 0 is Base's targets: p = p_w (block 0 of d_probs), p0 = p_w0 (block 2), both made by Base1; direction
+ *   d = 1 is Base1's targets: p = p_s (block 1), p0 = p_s0 (block 3).  p is what the step trains against (smoothed over
+ *   the memory bank once the gate is open), p0 the plain softmax.
+ *   Row r has truth t = d_truth[d_idx ? d_idx[r] : r]; it is KNOWN iff 0 <= t < K.  A row whose truth is not known
+ *   contributes nothing anywhere.
+ *   counts[8 d + s], per direction:
+ *     s = 0 rows      rows with known truth
+ *         1 nan_rows  rows where any entry of p[r] or p0[r] is NaN (they count in `rows` and nowhere else)
+ *         2 sel       rows with m = 1
+ *         3 hit_raw   l0 == t
+ *         4 hit       l == t
+ *         5 sel_hit   m and l == t
+ *         6 fixed     l0 != t and l == t
+ *         7 broken    l0 == t and l != t
+ *   where, for a NaN-free row, l0 = the FIRST index of the maximum of p0[r], l = the first index of the maximum of p[r],
+ *   m = (p[r][l] >= adap_mask) compared in fp32 -- the step's mask.
+ *   cm[d][t][l] += 1 for every selected row, at counts[CMLPL_PL_HEAD + (d K + t) K + l].
+ *   counts[16 .. 23], over ORDERED pairs (i, j), i != j, both truths known:
+ *     16 pairs      pairs considered
+ *     17 nan_pairs  q is NaN; the pair counts nowhere else
+ *     18 pos        q >= pos_thr
+ *     19 pos_same   positive and t_i == t_j
+ *     20 neg        q <= neg_thr
+ *     21 neg_diff   negative and t_i != t_j
+ *     22 launches   launches folded in
+ *     23 reserved, stays 0
+ *   q = the step's pseudo-label graph entry, in its fp32 evaluation: q = 0; for k ascending: q = fmaf(p_s[i][k],
+ *   p_w[j][k], q).  counts[24 .. 31] are reserved and stay 0.
+ *   For one step with every truth known and no NaN: sel[0] = n_mask_w, sel[1] = n_mask_s, pos + btu = n_pos (the step
+ *   counts its diagonal, which it sets to 1), neg = n_neg -- the step's own logged scalars.
+ *   Hard labels (CPS: d_pseudo int64 [2][btu], row 0 = Base's targets): a label outside [0, K) goes to nan_rows; every
+ *   other row is selected; hit_raw = hit = sel_hit, fixed = broken = 0; cm as above; no graph part; `launches` counts.
+ *
+ * cmlpl_pl_stats / cmlpl_pl_stats_hard: one launch each of that definition.  K <= 64, any btu >= 1.  One wavefront per
+ *   row (lanes = classes for the row part, lanes striding j for the pair part), counts by ballot and popcount, at most
+ *   one 64-bit integer atomic per non-zero head counter and workgroup, one per selected row into cm: integer atomics
+ *   only, so the result is exact and independent of the order of arrival.  No workspace, no synchronisation.  d_idx is
+ *   followed without a bounds check, as the step follows it.  CMLPL_E_ARG: a null d_probs / d_pseudo / d_truth /
+ *   d_counts, btu < 1, K outside 1 .. 64, a misaligned pointer. */
+#define CMLPL_PL_HEAD 32
+int cmlpl_pl_stats(const float* d_probs /* [4][btu][K] */, int btu, int K, const int64_t* d_truth,
+                   const int64_t* d_idx /* or NULL */, float adap_mask, float pos_thr, float neg_thr,
+                   int64_t* d_counts, void* stream);
+int cmlpl_pl_stats_hard(const int64_t* d_pseudo /* [2][btu] */, int btu, int K, const int64_t* d_truth,
+                        const int64_t* d_idx /* or NULL */, int64_t* d_counts, void* stream);
 
 #ifdef __cplusplus
 }

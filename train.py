@@ -40,6 +40,13 @@ Differences from the reference that are deliberate, MI355X-first choices:
     ``Random_rot`` (hsi_loader.py:58-88): every batch row takes one element of the dihedral group per step, the same for
     both networks, applied inside the gather of ``--windows cube`` (which it needs; one GPU).  ``--tta --tta_spatial
     flips | d4`` scores such views after the run (``OA_tta_flips`` / ``OA_tta_d4``).
+  * ``--pl_stats``: the pseudo-label monitor -- every step's targets are scored against the TRUTH of its unlabelled rows (the
+    loader carries the unlabelled split's labels; the reference never reads them), on the device, one launch behind every
+    step, eager or replayed (``TrainEngine(pl_monitor=True)``).  After every epoch one ``pl_stats`` line: per direction
+    (Base's targets, then Base1's, suffix ``1``) the rows the mask selected, the accuracy of the selected pseudo-labels, of
+    all of them and of the plain softmax's (what memory-bank smoothing changed); for CMLPL also the positive and negative
+    edges of the pseudo-label graph and their precision.  ``--save_pl PATH``: the per-epoch counter blocks.  One GPU.  The
+    run itself is untouched: ``loss_hist`` is what it is without the flag.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -120,10 +127,10 @@ def run_record(args, hp, shape, from_scene):
 
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
-    its sub-flags, --aug_spatial, --tta_spatial) is left out at its default, so a file written without it is byte for byte what it
+    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl) is left out at its default, so a file written without it is byte for byte what it
     was before the flag existed"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
-            'aug_spatial': 'none', 'tta_spatial': 'none'}
+            'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
@@ -412,8 +419,9 @@ def build_engine(run, args, make_engine):
     else:
         from cmlpl_amd import TrainEngine
         spatial = {} if args.aug_spatial == "none" else dict(aug_spatial=args.aug_spatial)
+        monitor = dict(pl_monitor=True) if args.pl_stats else {}
         run.eng = TrainEngine(NetShape(*run.shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=args.method,
-                              teacher_alpha=args.teacher_alpha if args.ema else None, **spatial)
+                              teacher_alpha=args.teacher_alpha if args.ema else None, **spatial, **monitor)
     run.eng.init_params_default(1088)
 
 
@@ -487,6 +495,8 @@ def restore_progress(run, args):
     if run.evaluator is not None:      # (a leg without --eval_every leaves a gap in the curves, not an error)
         for curve in run.curves.values():
             curve.restore(ex)
+    if args.pl_stats and "pl_curve" in ex:      # (a leg without --pl_stats leaves a gap in the curve, not an error)
+        run.pl_curve = list(ex["pl_curve"].numpy())
     if run.curves[''].epochs:          # --save_best: network 0's best validation so far
         run.best_oa = max(row[0][0] for row in run.curves[''].rows)
 
@@ -500,6 +510,9 @@ def run_extra(run, args, epochs_done):
                  run=run_record(args, run.hp, run.shape, run.from_scene), world=run.world)
     for entries in later:
         extra.update(entries)
+    if args.pl_stats:                 # the monitor's counter block of every epoch so far, int64 [epochs][32 + 2 K K]
+        size = 32 + 2 * run.shape[4] ** 2
+        extra["pl_curve"] = torch.from_numpy(np.stack(run.pl_curve)) if run.pl_curve else torch.zeros(0, size, dtype=torch.int64)
     return extra
 
 
@@ -529,6 +542,19 @@ def validate(run, args, epoch):
         run.best_extra = run_extra(run, args, epoch)
 
 
+def pl_line(epoch, num_epochs, c, graph_part):
+    """the ``pl_stats`` line of one epoch's counters (a cmlpl_amd.plstats.PLCounts): per direction the selected rows and
+    three accuracies in per cent; ``graph_part``: the edges of the pseudo-label graph and their precision behind them"""
+    parts = []
+    for d, tag in enumerate(('', '1')):
+        parts.append('sel%s = %d/%d acc_sel%s = %.2f acc%s = %.2f acc_raw%s = %.2f' %
+                     (tag, c.sel[d], c.rows[d], tag, c.acc_sel[d] * 100, tag, c.acc[d] * 100, tag, c.acc_raw[d] * 100))
+    if graph_part:
+        parts.append('pos = %d pos_precision = %.2f neg = %d neg_precision = %.2f' %
+                     (c.pos, c.pos_precision * 100, c.neg, c.neg_precision * 100))
+    return 'Epoch %d/%d: pl_stats %s' % (epoch, num_epochs, ' '.join(parts))
+
+
 def replays(run, epoch, batches, after=-1):
     """what a captured step replays: (epoch, batch, this rank's offsets) of the epoch's full batches behind batch ``after``"""
     gbt, gbtu = run.bt // run.world, run.btu // run.world              # rows of a replayed step on this rank
@@ -550,6 +576,7 @@ def train_epochs(run, args):
             loss_hist[pending] = eng.loss_window(len(pending))
             pending.clear()
     by_index = getattr(eng, "takes_indices", False)
+    truth_kw = dict(unl_truth=unl_loader.Y) if args.pl_stats else {}      # --pl_stats: the unlabelled split's labels
     # (a split smaller than one batch has no full batch to replay: such a run stays eager.  Several GPUs: the sharded
     #  step is replayed stage by stage, its collectives eager in between -- DistStepGraph; offsets are this rank's)
     use_graph = bool(args.graph) and by_index and hasattr(eng, "capture") and len(lab_loader.X) >= bt and len(unl_loader.X) >= btu
@@ -575,16 +602,17 @@ def train_epochs(run, args):
             elif by_index:
                 eng.step(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X, epoch, batch_index,
                          lab_idx=lab_loader.perm[lo + r * bl:lo + (r + 1) * bl],
-                         unl_idx=unl_loader.perm[uo + r * bul:uo + (r + 1) * bul], **cube_kw)
+                         unl_idx=unl_loader.perm[uo + r * bul:uo + (r + 1) * bul], **cube_kw, **truth_kw)
             else:
                 XPl, Xl, Yl = (t[r * bl:(r + 1) * bl].contiguous() for t in lab_loader.rows(lo, ls))
-                XPu, Xu, _ = (t[r * bul:(r + 1) * bul].contiguous() for t in unl_loader.rows(uo, us))
-                eng.step(XPl, Xl, Yl, XPu, Xu, epoch, batch_index)
+                XPu, Xu, Yu = (t[r * bul:(r + 1) * bul].contiguous() for t in unl_loader.rows(uo, us))
+                eng.step(XPl, Xl, Yl, XPu, Xu, epoch, batch_index, **(dict(unl_truth=Yu) if args.pl_stats else {}))
             if use_graph and graph is None:
                 # the first step ran eagerly (it sets the kernels' attributes); capture now and hand the rest of this
                 # epoch's full batches to the graph
                 graph = eng.capture(lab_loader.XP, lab_loader.X, lab_loader.Y, unl_loader.XP, unl_loader.X, lab_loader.perm,
-                                    unl_loader.perm, bt // world, btu // world, capacity=max(num_batches, 1), **cube_kw)
+                                    unl_loader.perm, bt // world, btu // world, capacity=max(num_batches, 1), **cube_kw,
+                                    **truth_kw)
                 rest = replays(run, epoch, batches, after=batch_index)
                 if rest:
                     graph.program(rest)
@@ -599,6 +627,11 @@ def train_epochs(run, args):
                                             np.mean(w[:, 0]), np.mean(w[:, 1]), np.mean(w[:, 2]), np.mean(w[:, 3]),
                                             np.mean(w[:, 4]) * 100))
         read_back()                   # rows of the epoch's tail (num_batches % print_per_batches steps)
+        if args.pl_stats:             # the epoch's counters: read, zeroed for the next epoch, one line
+            counts = eng.pl_counts()
+            eng.pl_reset()
+            run.pl_curve.append(counts.counts)
+            print(pl_line(epoch + 1, args.num_epochs, counts, args.method == 'cmlpl'))
         if run.evaluator is not None and (epoch + 1) % args.eval_every == 0:
             validate(run, args, epoch + 1)
         if rank == 0 and args.save_ckpt and (epoch + 1 == args.num_epochs or
@@ -622,6 +655,8 @@ def report(run, args):
     eng, device, curves, base = run.eng, run.device, run.curves, run.curves['']
     if args.save_loss_hist:
         np.save(args.save_loss_hist, run.loss_hist)
+    if args.save_pl:
+        np.save(args.save_pl, np.stack(run.pl_curve) if run.pl_curve else np.zeros((0, 32 + 2 * run.shape[4] ** 2), np.int64))
     if run.best_state is not None:
         checkpoint.save(args.save_best, run.best_state, run.best_extra)
     if args.report_memory and device.type == "cuda":
@@ -675,6 +710,10 @@ def main(args, make_engine=None, device=None):
     check_spatial_args(args, world)
     if args.ema and world > 1:
         raise SystemExit(f"--ema runs on one GPU: the sharded engine keeps no EMA teacher (this job has {world} ranks)")
+    if args.pl_stats and world > 1:
+        raise SystemExit(f"--pl_stats runs on one GPU: the sharded engine has no pseudo-label monitor (this job has {world} ranks)")
+    if args.save_pl and not args.pl_stats:
+        raise SystemExit("--save_pl belongs to --pl_stats")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -685,7 +724,8 @@ def main(args, make_engine=None, device=None):
     run = argparse.Namespace(world=world, rank=rank, device=device, bt=args.labeled_batch_size, btu=args.unlabeled_batch_size,
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
-                             evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth)
+                             evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth,
+                             pl_curve=[])
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -695,6 +735,8 @@ def main(args, make_engine=None, device=None):
     if args.resume:
         open_resume(run, args)        # resumed, the file: its state goes into eng and gen
     build_loaders(run, args)          # lab_loader, unl_loader, num_batches, loss_hist; --windows cube: cube_kw
+    if args.pl_stats and run.unl_loader.Y is None:
+        raise SystemExit("--pl_stats needs the labels of the unlabelled split")
     if args.eval_every > 0 and rank == 0:
         build_evaluator(run, args)    # evaluator
     if args.resume:
@@ -756,6 +798,15 @@ def build_parser():
                         help="flip ('flips') or flip-and-rotate ('d4') augmentation of the training windows: every batch row "
                              "takes one spatial element per step, the same for both networks, applied in the gather from the "
                              "scene (needs --windows cube; one GPU)")
+    parser.add_argument('--pl_stats', action='store_true',
+                        help="the pseudo-label monitor: score every step's targets against the truth of its unlabelled rows, on "
+                             "the device (one launch behind every step), and print one pl_stats line per epoch -- the rows the "
+                             "mask selects, the accuracy of their pseudo-labels, what memory-bank smoothing changed, the "
+                             "precision of the graph's positive and negative edges (one GPU).  The labels of plain --synthetic "
+                             "are random: it needs --synthetic_scene (or --windows cube) for meaningful numbers")
+    parser.add_argument('--save_pl', default=None, metavar='PATH',
+                        help='--pl_stats: write the per-epoch counter blocks as one int64 .npy [epochs][32 + 2 K K] '
+                             '(cmlpl_amd.plstats.PLCounts names the fields)')
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')

@@ -8,6 +8,7 @@ Public surface:
   TTA, tta_cube / tta_pixels, views_of ... the same from several noisy views per pixel (test-time augmentation)
   Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
+  Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -33,4 +34,8 @@ def __getattr__(name):
     if name in ("PLCounts", "pl_stats_host", "pl_stats_hard_host"):
         from . import plstats
         return getattr(plstats, name)
+    if name in ("Reliability", "reliability", "temper_probs", "fit_temperature", "reliability_host", "temper_host",
+                "nll_temps_host"):
+        from . import calibrate
+        return getattr(calibrate, name)
     raise AttributeError(name)

@@ -47,9 +47,11 @@ EXPORTS = (
     "cmlpl_smooth_probs",                                                        # added after ABI 6, no bump: spatial smoothing
     "cmlpl_infer_cube_tta_sym", "cmlpl_infer_pixels_tta_sym", "cmlpl_tta_patches_sym",   # added after ABI 6, no bump: flip / rotate views
     "cmlpl_pl_stats", "cmlpl_pl_stats_hard",                                     # added after ABI 6, no bump: the pseudo-label monitor
+    "cmlpl_reliability", "cmlpl_temper_probs", "cmlpl_nll_temps",                # added after ABI 6, no bump: calibration
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
+REL_HEAD = 16                         # CMLPL_REL_HEAD: the head of the reliability counter block, in front of its 3 B bin words
 SPATIAL = {"none": 0, "flips": 1, "d4": 2}    # cmlpl_step_io.reserved, bits 8..9 (CMLPL_SYM_*); 1, 4, 8 elements
 
 
@@ -278,6 +280,9 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_smooth_probs.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.cmlpl_pl_stats.argtypes = [vp, i32, i32, vp, vp, f32, f32, f32, vp, vp]
     lib.cmlpl_pl_stats_hard.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.cmlpl_reliability.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.cmlpl_temper_probs.argtypes = [vp, i32, i32, f32, vp, vp, vp, vp, vp]
+    lib.cmlpl_nll_temps.argtypes = [vp, i32, vp, vp, i32, C.POINTER(f32), i32, vp, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]

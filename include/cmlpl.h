@@ -991,6 +991,90 @@ int cmlpl_pl_stats(const float* d_probs /* [4][btu][K] */, int btu, int K, const
 int cmlpl_pl_stats_hard(const int64_t* d_pseudo /* [2][btu] */, int btu, int K, const int64_t* d_truth,
                         const int64_t* d_idx /* or NULL */, int64_t* d_counts, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- CALIBRATION: does a written confidence mean what it says?  The
+ * reliability counters of a probability map against the truth of listed pixels, the map at another temperature, and the
+ * negative log-likelihood at many candidate temperatures in one launch (temperature scaling: Guo et al., "On Calibration of
+ * Modern Neural Networks", ICML 2017).  The reference has no counterpart.
+ *
+ * THE DEFINITION OF THE RELIABILITY COUNTERS.  The block is int64 counts[CMLPL_REL_HEAD + 3 B] for B bins.  Every launch
+ * ADDS to it and nothing else writes it (the caller zeroes a fresh one); chunks of a list, or several launches, sum to the
+ * launch over the whole list, bit for bit.
+ *   Item i < n scores row r = d_row ? d_row[i] : i of d_probs [rows][K] against t = d_truth[i].
+ *   It is KNOWN iff 0 <= t < K; otherwise it counts in `ignored` and nowhere else.
+ *   label = the FIRST maximum of the row; a NaN counts as the maximum and the first NaN wins (cmlpl_ensemble's rule).
+ *   conf = p[label].  A known row whose conf is NaN (a row that holds a NaN) counts in `nan` and in no bin and no sum.
+ *   Every other known row is SCORED: hit = (label == t); its bin is b = min(B - 1, (int)(conf * (float)B)) -- ONE fp32
+ *   multiply, truncated: conf == 1 lands in the last bin, conf exactly on an edge k / B in the upper bin k; a product that
+ *   is negative goes to bin 0, one >= B (conf > 1, +inf) to bin B - 1.
+ *   counts[0] items      n of the launch
+ *         [1] known
+ *         [2] ignored
+ *         [3] nan
+ *         [4] hits       scored rows with hit
+ *         [5] sum_conf   sum over scored rows of fix24(conf)
+ *         [6] sum_nll    sum over scored rows with p[t] > 0 of fix24(nll), nll = -logf(p[t])
+ *         [7] n_inf      scored rows with p[t] <= 0: they are kept out of sum_nll
+ *         [8] sum_brier  sum over scored rows of fix24(brier), brier = sum_c (p_c - [c == t])^2 in fp32: d_c = p_c - 1 for
+ *                        c == t, p_c otherwise; s_c = fl32(d_c d_c) (a product of its own, never fused into the sum), s_c = 0
+ *                        for K <= c < G, G the smallest power of two >= K; then the butterfly of cmlpl_ensemble: for o = G / 2,
+ *                        G / 4 .. 1: s_c = s_c + s_(c xor o), all c at once; brier = s_0
+ *         [9 .. 15]      reserved, stay 0 (CMLPL_REL_HEAD = 16)
+ *   counts[16 + b] count[b], counts[16 + B + b] hits[b], counts[16 + 2 B + b] conf_sum[b] = sum of fix24(conf) of bin b.
+ *   Every real-valued sum is FIXED POINT: a row contributes fix24(x) = llrintf(x * 2^24), rounded to nearest, ties to even;
+ *   the product is exact (a power of two).  For the probabilities this is made for, x <= 104 (the -logf of the smallest
+ *   positive fp32 is 103.3; conf <= 1, brier <= 2), so a row adds less than 2^31 and, with n < 2^31 rows, an int64 sum
+ *   stays below 2^62: it cannot overflow.  (Rows that are no probabilities are binned as said above; their sums are defined
+ *   only while |x| < 2^38.)  So the whole block is integer additions: order-free, exact, the same bytes on every run.
+ *
+ * cmlpl_reliability: one launch of that definition.  K 1 .. 64, bins 1 .. 1024, n >= 1.  cmlpl_ensemble's lane scheme: a
+ *   group of G lanes per item, shuffle butterflies; a workgroup keeps count / hits (int32) and conf_sum (int64) of every bin in
+ *   LDS (16 KB at 1024 bins), one LDS atomic each per scored row, then one 64-bit global integer atomic per NON-ZERO word;
+ *   the head counts are ballots and popcounts.  (A launch has n < 2^31 items: an int32 cell cannot overflow.)  No float atomics, no
+ *   workspace, no synchronisation.  d_row is followed without a bounds check.  CMLPL_E_ARG: a null d_probs / d_truth /
+ *   d_counts, n < 1, K outside 1 .. 64, bins outside 1 .. 1024, a misaligned pointer. */
+#define CMLPL_REL_HEAD 16
+int cmlpl_reliability(const float* d_probs /* [rows][K] */, int K, const int64_t* d_row /* [n] or NULL */,
+                      const int64_t* d_truth /* [n] */, int n, int bins, int64_t* d_counts, void* stream);
+
+/* cmlpl_temper_probs: q = softmax(beta log p), that is p^beta renormalised, of every row of d_probs [n][K].  For one
+ *   network this is its softmax at temperature T = 1 / beta; for an ensemble, a TTA average or a smoothed map it is the same
+ *   operation on the mixture: it is defined behind every stage that produces probabilities.  beta = fl32(1 / T) is formed in
+ *   double by the caller.  THE fp32 CHAIN of a row:
+ *     l_c = logf(p_c)                     (a zero gives -inf)
+ *     m   = max_c l_c
+ *     e_c = expf(fl32(beta * fl32(l_c - m)))   (an -inf l_c gives exactly 0)
+ *     s   = sum_c e_c in cmlpl_ensemble's butterfly order (e_c = 0 for K <= c < G; for o = G / 2 .. 1: e_c = e_c + e_(c xor o))
+ *     q_c = e_c / s
+ *   A row with a NaN, a negative entry, a +inf or no positive entry is NaN everywhere.  label = the first maximum of the
+ *   INPUT row p under cmlpl_ensemble's rule (a NaN counts as the maximum, the first NaN wins): the chain is monotone, so
+ *   q[label] is a maximum of q, and a temperature never moves a label, not even where rounding makes two q_c equal.
+ *   conf = q[label]; entropy = -sum_c q_c logf(q_c) (0 log 0 = 0, NaN when q is NaN; the same butterfly).  ANY output pointer may be NULL.  d_out_probs may BE d_probs (in place: a group reads its whole row before it
+ *   stores and touches no other row); it may not overlap it otherwise.  One launch in cmlpl_ensemble's lane scheme, no LDS,
+ *   no atomics, no workspace; the same bytes on every run, and a row's bytes do not depend on where in the launch it lies.
+ *   CMLPL_E_ARG: a null d_probs, n < 1, K outside 1 .. 64, a beta that is not finite or not positive, a misaligned pointer. */
+int cmlpl_temper_probs(const float* d_probs, int n, int K, float beta, float* d_out_probs, int64_t* d_labels,
+                       float* d_conf, float* d_entropy, void* stream);
+
+/* cmlpl_nll_temps: the negative log-likelihood of the listed pixels at S candidate values of beta = 1 / T, one launch.
+ *   Items as in cmlpl_reliability (row r = d_row ? d_row[i] : i against t = d_truth[i]); an item of unknown truth is
+ *   skipped (its d_row entry is followed all the same, without a bounds check).  `betas` is a HOST array [S], read during the call (passed on by value, as cmlpl_ensemble's weights); S is
+ *   1 .. 64 and every beta lies in [1/16, 16].  A known item is LEFT OUT when p_t is not positive (zero, negative, NaN) or
+ *   its row holds a NaN, a negative entry or a +inf; it then counts in d_sums[S + s] for every s.  Every other known item
+ *   adds llrintf(nll(beta_s) * 2^20) (to nearest, ties to even; the product is exact) to d_sums[s], where, in fp32,
+ *     l_c = logf(p_c), m = max_c l_c,
+ *     z   = 0; for c ASCENDING: z = z + expf(fl32(beta * fl32(l_c - m)))
+ *     nll = logf(z) - fl32(beta * fl32(l_t - m))          (no product is fused into a sum)
+ *   nll < 2^11 (beta <= 16, l_t - m >= -104, logf(z) <= logf(64)), and 2^11 2^20 2^31 = 2^62: the int64 cannot overflow.
+ *   d_sums is int64 [2][S]; the launch ADDS to it (the caller zeroes a fresh one), so chunks and launches add up bit for
+ *   bit like the reliability counters.  Lanes = candidates, one wavefront per row at a time: lane c < K takes the logf of
+ *   class c once for the whole wave, lane s walks its own chain and keeps its int64 in registers over the wave's rows; one
+ *   LDS fold per workgroup, one 64-bit global integer atomic per non-zero word.  No float atomics, no workspace.
+ *   CMLPL_E_ARG: a null d_probs / d_truth / betas / d_sums, n < 1, K outside 1 .. 64, S outside 1 .. 64, a beta outside
+ *   [1/16, 16] (a NaN too), a misaligned pointer. */
+int cmlpl_nll_temps(const float* d_probs /* [rows][K] */, int K, const int64_t* d_row /* [n] or NULL */,
+                    const int64_t* d_truth /* [n] */, int n, const float* betas /* host, [S] */, int S,
+                    int64_t* d_sums /* [2][S] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,16 @@ the views flipped (and rotated) windows as well -- what ``train.py --aug_spatial
 probability maps of that prediction over the scene -- an edge-preserving filter of radius R guided by the cube's leading
 channels (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``), with any single
 network or ensemble, with or without ``--tta``: the ``Result:`` block above is printed as it is, a second one follows with
-``_smooth`` appended to its tag, and ``--out`` / ``--proba`` / ``--confidence`` / ``--entropy`` describe the SMOOTHED prediction."""
+``_smooth`` appended to its tag, and ``--out`` / ``--proba`` / ``--confidence`` / ``--entropy`` describe the SMOOTHED prediction.
+``--reliability`` prints, behind every ``Result:`` block of ONE prediction (the raw one, ``_ens``, ``_tta..``, ``.._smooth``, ``.._T``),
+one line ``Reliability<tag>: ECE=.. MCE=.. NLL=.. Brier=.. conf=.. acc=..`` over the labelled test pixels -- whether a written
+confidence means what it says (cmlpl_amd.calibrate: integer counters on the device, ``--rel_bins`` bins, default 15;
+``--save_reliability FILE`` writes the int64 blocks as .npz, one entry ``Reliability<tag>`` per line); for a single ``--net`` the
+probabilities are its own softmax.  ``--temperature T`` tempers the FINAL probabilities of the prediction (behind TTA and
+smoothing), ``q = softmax(log p / T)``: a further ``Result:`` block follows with ``_T`` appended to the tag, and ``--out`` /
+``--proba`` / ``--confidence`` / ``--entropy`` describe the tempered prediction.  ``--temperature fit`` finds T itself, the least
+NLL on a seeded random share (``--calib_frac``, default 0.5; ``--calib_seed``, default 1088) of the labelled test pixels; every
+``Reliability`` line of such a run is counted on the held-out remainder only, and says so."""
 import argparse
 import os
 
@@ -32,10 +41,25 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import (DATASETS, NET_TAGS, SPATIAL_MODES, SYNTH, add_smooth_flags, ensemble_whole, evaluate_whole, smooth_of,
-                   smooth_whole, tta_tag, tta_whole)
+from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SPATIAL_MODES, SYNTH, RelScore, add_smooth_flags, calibration_split,
+                   ensemble_whole, evaluate_whole, smooth_of, smooth_whole, temper_stage, tta_tag, tta_whole)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
+CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
+
+
+def temperature_of(args):
+    """--temperature: None (not given), 'fit', or a finite T > 0; anything else is a SystemExit"""
+    t = getattr(args, 'temperature', None)
+    if t is None or t == 'fit':
+        return t
+    try:
+        t = float(t)
+    except ValueError:
+        t = float('nan')
+    if not (0.0 < t < float('inf')):
+        raise SystemExit("--temperature T: a finite T > 0, or 'fit'")
+    return t
 
 
 def check_args(args):
@@ -55,6 +79,20 @@ def check_args(args):
             raise SystemExit("--tta_seed N: 0 <= N < 2^64")
     elif args.tta_noise is not None or args.tta_no_clean or args.tta_spatial != 'none':
         raise SystemExit("--tta_noise / --tta_no_clean / --tta_spatial belong to --tta M")
+    temperature = temperature_of(args)
+    if args.net in ('both', 'ema_both') and (args.reliability or temperature is not None):
+        raise SystemExit("--reliability / --temperature describe ONE prediction: --net %s writes two label maps (name one "
+                         "network, or --net ensemble for the two together)" % args.net)
+    if not args.reliability and (args.rel_bins is not None or args.save_reliability):
+        raise SystemExit("--rel_bins / --save_reliability belong to --reliability")
+    if args.rel_bins is not None and not 1 <= args.rel_bins <= 1024:
+        raise SystemExit("--rel_bins B: 1 .. 1024 bins")
+    if temperature != 'fit' and (args.calib_frac is not None or args.calib_seed is not None):
+        raise SystemExit("--calib_frac / --calib_seed belong to --temperature fit")
+    if args.calib_frac is not None and not (0.0 < args.calib_frac < 1.0):
+        raise SystemExit("--calib_frac F: a share 0 < F < 1 of the labelled test pixels")
+    if args.calib_seed is not None and args.calib_seed < 0:
+        raise SystemExit("--calib_seed N: N >= 0")
     if smooth_of(args) is not None and args.net in ('both', 'ema_both'):
         raise SystemExit("--smooth gives ONE prediction: --net %s writes two label maps (name one network, or --net "
                          "ensemble for the two together)" % args.net)
@@ -85,6 +123,10 @@ def main(args, device=None):
             Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
     which = {'both': [0, 1], 'ema_both': ['ema0', 'ema1'], **ENSEMBLES}.get(args.net) or \
         [args.net if args.net.startswith('ema') else int(args.net)]
+    temperature = temperature_of(args)
+    if test_array is None and (args.reliability or temperature == 'fit'):
+        raise SystemExit("--reliability / --temperature fit need the labelled test pixels (test_array.npy and Y.npy in the "
+                         "dataset directory)")
     if any(str(k).startswith('ema') for k in which) and ("Teacher" not in ck or "Teacher1" not in ck):
         raise SystemExit("--net %s: %s holds no EMA teacher (\"Teacher\" / \"Teacher1\"): it was written by a run "
                          "without train.py --ema" % (args.net, args.ckpt))
@@ -97,16 +139,40 @@ def main(args, device=None):
         from cmlpl_amd.tta import TTA
         tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
                   clean=not args.tta_no_clean, spatial=args.tta_spatial)
-    if smooth is not None and (tta is not None or args.net in ENSEMBLES):
-        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=NET_TAGS['ens'] if tta is None else tta_tag(tta),
-                           raw_block=True, **common, **extras)
+    # calibration (no keyword at all without its flags): the Reliability line behind every block, the tempering stage behind the last
+    together = tta is not None or args.net in ENSEMBLES
+    tag = (NET_TAGS['ens'] if tta is None else tta_tag(tta)) if together else NET_TAGS[which[0]]
+    calib, score = {}, None
+    if args.reliability or temperature is not None:
+        fit = held = None
+        if temperature == 'fit':
+            fit, held = calibration_split(len(test_array), CALIB_FRAC if args.calib_frac is None else args.calib_frac,
+                                          CALIB_SEED if args.calib_seed is None else args.calib_seed)
+            if len(fit) < 1 or len(held) < 1:
+                raise SystemExit("--temperature fit: the calibration share or its remainder is empty (%d labelled test pixels)" % len(test_array))
+            on = lambda v: torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.int64)[fit])).to(device)
+            fit = (on(test_array), on(Y_test))
+        if args.reliability:
+            score = calib['score'] = RelScore(test_array, Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins, held)
+        if temperature is not None:
+            calib['then'] = [temper_stage(tag + (SMOOTH_TAG if smooth is not None else ''), None if temperature == 'fit' else temperature,
+                                          fit=fit, **dict(extras, probs=extras['probs'] or args.reliability))]
+    if smooth is not None and together:
+        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=tag, raw_block=True, **common, **extras, **calib)
     elif tta is not None:
-        out = tta_whole(shape, whole, members, device, tta, **common, **extras)
+        out = tta_whole(shape, whole, members, device, tta, **common, **extras, **calib)
     elif args.net in ENSEMBLES:
-        out = ensemble_whole(shape, whole, members, device, **common, **extras)
+        out = ensemble_whole(shape, whole, members, device, **common, **extras, **calib)
     elif smooth is not None:        # one network: its Result: block as ever, then its own softmax (a one-member ensemble) smoothed
         evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
-        out = smooth_whole(shape, whole, members, device, smooth, tag=NET_TAGS[which[0]], **common, **extras)
+        out = smooth_whole(shape, whole, members, device, smooth, tag=tag, **common, **extras, **calib,
+                           **(dict(score_raw=True) if score is not None else {}))
+    elif calib:                     # one network: its Result: block as ever, then its own softmax scored and / or tempered
+        preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
+        out = ensemble_whole(shape, whole, members[:1], device, **common, **extras, **calib, raw_block=False, tag=tag,
+                             **(dict(score_raw=True) if score is not None else {}))
+        if temperature is None:     # (its label map stays the argmax of its logits)
+            out["labels"] = np.asarray(preds[which[0]]).astype(np.int64)
     else:
         preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
         labels = np.stack([preds[k] for k in which]).astype(np.int64)
@@ -119,6 +185,8 @@ def main(args, device=None):
             np.save(path, out[key])
     if args.out:
         np.save(args.out, out["labels"])
+    if args.save_reliability:
+        score.save(args.save_reliability)
     return out["labels"]
 
 
@@ -151,6 +219,23 @@ def build_parser():
                              "view t under element (t + 1) mod 4 / 8 (t mod 4 / 8 with --tta_no_clean); with --tta_noise 0 pure "
                              "geometry; the Result: tag becomes _tta_flips / _tta_d4")
     add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
+    parser.add_argument('--reliability', action='store_true',
+                        help='behind every Result: block one line Reliability<tag>: ECE, MCE, NLL, Brier score, mean confidence '
+                             'and accuracy of the block\'s class probabilities over the labelled test pixels (not with both / '
+                             'ema_both)')
+    parser.add_argument('--rel_bins', type=int, default=None, metavar='B',
+                        help='--reliability: the number of confidence bins (default 15, 1 .. 1024)')
+    parser.add_argument('--save_reliability', default=None, metavar='FILE',
+                        help='--reliability: write the int64 counter blocks as .npz, one entry Reliability<tag> per line '
+                             '(cmlpl_amd.calibrate.Reliability names the fields)')
+    parser.add_argument('--temperature', default=None, metavar='T',
+                        help="temper the final class probabilities of the prediction, q = softmax(log p / T): one more Result: "
+                             "block, tag ..._T; 'fit': the T of the least NLL on a share of the labelled test pixels")
+    parser.add_argument('--calib_frac', type=float, default=None, metavar='F',
+                        help='--temperature fit: the share of the labelled test pixels that fits T (default 0.5); every '
+                             'Reliability line is then counted on the remainder')
+    parser.add_argument('--calib_seed', type=int, default=None, metavar='N',
+                        help='--temperature fit: the seed of that share (default 1088)')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

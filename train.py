@@ -47,6 +47,10 @@ Differences from the reference that are deliberate, MI355X-first choices:
     all of them and of the plain softmax's (what memory-bank smoothing changed); for CMLPL also the positive and negative
     edges of the pseudo-label graph and their precision.  ``--save_pl PATH``: the per-epoch counter blocks.  One GPU.  The
     run itself is untouched: ``loss_hist`` is what it is without the flag.
+  * ``--reliability``: behind every ``_ens`` / ``_tta..`` / ``.._smooth`` block of the end-of-run report one ``Reliability<tag>:``
+    line -- ECE, MCE, NLL, Brier score, mean confidence and accuracy of that block's class probabilities over the labelled
+    test pixels, from integer counters kept on the device (cmlpl_amd.calibrate).  It needs ``--ensemble``, ``--tta`` or
+    ``--smooth``; ``loss_hist``, checkpoints and every other line are what they are without the flag.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -127,10 +131,10 @@ def run_record(args, hp, shape, from_scene):
 
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
-    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl) is left out at its default, so a file written without it is byte for byte what it
+    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability) is left out at its default, so a file written without it is byte for byte what it
     was before the flag existed"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
-            'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None}
+            'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
@@ -260,12 +264,64 @@ def build_nets(shape, nets, device, dropout):
     return models
 
 
+TEMPER_TAG = '_T'                                                  # temper_stage: appended to the tag of what it tempers
+
+
+class RelScore:
+    """``--reliability``: the ``Reliability<tag>:`` line behind a ``Result:`` block -- the reliability counters of the block's
+    class probabilities over the labelled test pixels (cmlpl_amd.calibrate.reliability: one launch, one read-back).
+    ``held_out``: positions in ``test_array`` the lines are counted on (the rest fitted a temperature); the line says so.
+    ``blocks`` keeps the int64 counter block of every line, by tag."""
+
+    def __init__(self, test_array, Y_test, device, bins=15, held_out=None):
+        rows, truth = np.asarray(test_array, np.int64), np.asarray(Y_test, np.int64)
+        self.note = ''
+        if held_out is not None:
+            rows, truth = rows[held_out], truth[held_out]
+            self.note = ' (held-out n=%d)' % len(rows)
+        self.rows, self.truth = (torch.from_numpy(np.ascontiguousarray(v)).to(device) for v in (rows, truth))
+        self.bins, self.blocks = bins, {}
+
+    def __call__(self, tag, res):
+        from cmlpl_amd.calibrate import reliability
+        rel = reliability(res.probs, self.truth, self.rows, self.bins)
+        self.blocks[tag] = rel.counts
+        print(rel.line(tag, self.note))
+
+    def save(self, path):
+        np.savez(path, **{'Reliability' + tag: block for tag, block in self.blocks.items()})
+
+
+def calibration_split(n, frac, seed):
+    """(calibration, held-out) positions among n labelled test pixels: a seeded random share ``frac`` fits the temperature
+    (the first round(frac n) of numpy.random.default_rng(seed).permutation(n)), the remainder scores it"""
+    perm = np.random.default_rng(seed).permutation(n)
+    k = int(round(frac * n))
+    return perm[:k], perm[k:]
+
+
+def temper_stage(tag, T, probs=False, conf=False, entropy=False, fit=None):
+    """the stage of ``together_whole`` that tempers the probabilities in front of it (cmlpl_amd.calibrate.temper_probs): its
+    ``Result:`` lines carry ``tag`` + ``_T``.  ``T`` None: fitted first, on the pixels ``fit`` = (rows, truth) on the device"""
+    from cmlpl_amd.calibrate import fit_temperature, temper_probs
+
+    def call(res, cube):
+        t = T
+        if t is None:
+            t, before, after = fit_temperature(res.probs, fit[1], fit[0])
+            print('temperature = %.4f (NLL %.4f -> %.4f on the calibration share)' % (t, before, after))
+        return temper_probs(res.probs, t, probs_out=probs, conf=conf, entropy=entropy)
+    return ('tempering time == %%.3f s (T %s)' % ('fitted' if T is None else '%g' % T), tag + TEMPER_TAG, call)
+
+
 def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-                   then=None, raw_block=True):
+                   then=(), raw_block=True, score=None, score_raw=None):
     """the body of ``ensemble_whole``, ``tta_whole`` and ``smooth_whole``: ``predict(models, cube, spectra)`` is the library call,
     ``timing`` its printed line (a format of the seconds and the number of networks), ``tag`` that of its ``Result:`` lines
-    (``raw_block`` False: not printed), ``noun`` who asks.  ``then`` = (timing, tag, call): a second stage ``call(result, cube)``
-    on the first one's result, with a line and a block of its own; its outputs are then the ones returned."""
+    (``raw_block`` False: not printed), ``noun`` who asks.  ``then`` = [(timing, tag, call), ..]: further stages, each
+    ``call(result, cube)`` on the result in front of it, with a line and a block of its own; the outputs of the last one are
+    the ones returned.  ``score(tag, result)`` (a ``RelScore``) is called behind every block (``score_raw``: behind the first
+    stage also where its block is printed elsewhere; default: where ``raw_block``)."""
     source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
     if source is None:
         raise SystemExit("%s needs the scene cube (cube.npy + scene.json in the dataset directory, "
@@ -277,19 +333,23 @@ def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synth
     print(timing % (time.time() - t1, len(models)))
     if test_array is not None and raw_block:
         print_result(tag, out["labels"], test_array, Y_test)
-    if then is not None:
-        timing, tag, call = then
+    if score is not None and (raw_block if score_raw is None else score_raw):
+        score(tag, res)
+    for timing, tag, call in then or ():
         t1 = time.time()
         res = call(res, source.cube)
         out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
         print(timing % (time.time() - t1))
         if test_array is not None:
             print_result(tag, out["labels"], test_array, Y_test)
+        if score is not None:
+            score(tag, res)
     return out
 
 
 def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
-                   resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+                   resident_cube=None, weights=None, probs=False, conf=False, entropy=False, raw_block=True, then=(), score=None,
+                   score_raw=None, tag=None):
     """Whole-image ENSEMBLE of ``nets`` = [(key, state_dict)] (1..4 networks, ``evaluate_whole``'s list): the label of their
     averaged softmax for every scene pixel, and its probabilities / confidence / entropy when asked for
     (cmlpl_amd.ensemble.ensemble_cube: every member's eval forward from the resident cube, one launch behind each chunk).
@@ -297,26 +357,30 @@ def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout
     not asked for is absent) and prints the ``Result:`` lines with the tag ``_ens`` when the test pixels are given.  It
     needs the scene as its cube: there is no loader fall-back."""
     from cmlpl_amd.ensemble import ensemble_cube
+    probs = probs or bool(then) or score is not None            # (what follows reads the probabilities)
     return together_whole(
         lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=probs, conf=conf, entropy=entropy),
-        'ensemble inference time == %.3f s (%d networks)', NET_TAGS['ens'], "the ensemble",
-        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
+        'ensemble inference time == %.3f s (%d networks)', NET_TAGS['ens'] if tag is None else tag, "the ensemble",
+        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
+        then=then, raw_block=raw_block, score=score, score_raw=score_raw)
 
 
 def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
-              resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+              resident_cube=None, weights=None, probs=False, conf=False, entropy=False, then=(), score=None):
     """``ensemble_whole`` over the noisy views of ``tta`` (cmlpl_amd.tta.TTA): every network of ``nets`` scores every view
     of every scene pixel, one label map from the average of all their softmaxes (cmlpl_amd.tta.tta_cube).  Same returns;
     the ``Result:`` lines carry the tag ``_tta`` (``_tta_flips`` / ``_tta_d4`` when the views are spatial, ``tta_tag``)."""
     from cmlpl_amd.tta import tta_cube
+    probs = probs or bool(then) or score is not None
     return together_whole(
         lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy),
         tta_timing(tta), tta_tag(tta), "test-time augmentation",
-        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube)
+        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube, then=then, score=score)
 
 
 def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None, dataID=1,
-                 dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False, entropy=False):
+                 dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False, entropy=False,
+                 then=(), score=None, score_raw=None):
     """``ensemble_whole`` (``tta``: ``tta_whole``) followed by the edge-preserving spatial smoothing of its class probability
     maps under the guide of the scene cube (``smooth``: a cmlpl_amd.smooth.Smooth; what cmlpl_amd.smooth.smooth_cube
     does, in its two halves).  Same returns, of the SMOOTHED prediction; its ``Result:`` lines carry ``tag`` + ``_smooth``.
@@ -331,12 +395,13 @@ def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens
         raw = lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True)
         timing = tta_timing(tta)
     R, ss, sr, G, iters = smooth.params()
+    probs = probs or bool(then) or score is not None            # (what follows the smoothing reads its probabilities)
     return together_whole(
         raw, timing, tag, "spatial smoothing", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-        then=('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
-              (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
-              lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy)),
-        raw_block=raw_block)
+        then=[('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
+               (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
+               lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy)), *then],
+        raw_block=raw_block, score=score, score_raw=score_raw)
 
 
 def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
@@ -677,13 +742,24 @@ def report(run, args):
                  Y_test=run.Y_test, resident_cube=run.cube_kw.get("cube"))
     evaluate_whole(run.shape, run.whole, nets, device, val_batch_size=args.val_batch_size,
                    last_eval=base.rows[-1] if base.epochs and base.epochs[-1] == args.num_epochs else None, **scene)
+    # --reliability: one Reliability<tag>: line behind every block below (no keyword at all without the flag)
+    rel = dict(score=RelScore(run.test_array, run.Y_test, device)) if args.reliability and run.test_array is not None else {}
     if args.ensemble:
-        ensemble_whole(run.shape, run.whole, nets[:2], device, **scene)
+        ensemble_whole(run.shape, run.whole, nets[:2], device, **scene, **rel)
     if args.tta:
         from cmlpl_amd.tta import TTA
-        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise, spatial=args.tta_spatial), **scene)
+        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise, spatial=args.tta_spatial), **scene, **rel)
     if run.smooth is not None:
-        smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene)
+        smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene, **rel)
+
+
+def check_reliability_args(args, smooth):
+    """what --reliability cannot mean, said before any device or communicator work"""
+    if args.reliability and not (args.ensemble or args.tta or smooth is not None):
+        raise SystemExit("--reliability scores the class probabilities of the end-of-run report's _ens / _tta / _smooth blocks: "
+                         "it needs --ensemble, --tta or --smooth")
+    if args.reliability and args.no_eval:
+        raise SystemExit("--reliability belongs to the end-of-run report: not with --no_eval")
 
 
 def check_spatial_args(args, world=1):
@@ -714,6 +790,7 @@ def main(args, make_engine=None, device=None):
         raise SystemExit(f"--pl_stats runs on one GPU: the sharded engine has no pseudo-label monitor (this job has {world} ranks)")
     if args.save_pl and not args.pl_stats:
         raise SystemExit("--save_pl belongs to --pl_stats")
+    check_reliability_args(args, smooth)
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -807,6 +884,11 @@ def build_parser():
     parser.add_argument('--save_pl', default=None, metavar='PATH',
                         help='--pl_stats: write the per-epoch counter blocks as one int64 .npy [epochs][32 + 2 K K] '
                              '(cmlpl_amd.plstats.PLCounts names the fields)')
+    parser.add_argument('--reliability', action='store_true',
+                        help="calibration of the end-of-run report: behind every _ens / _tta / _smooth Result: block one "
+                             "Reliability<tag>: line -- ECE, MCE, NLL, Brier score, mean confidence and accuracy of the block's class "
+                             "probabilities over the labelled test pixels, counted on the device (cmlpl_amd.calibrate; needs "
+                             "--ensemble, --tta or --smooth).  The run itself is untouched")
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')

@@ -9,6 +9,7 @@ Public surface:
   Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
   Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
+  embed, KnnEvaluator, KnnResult, knn_host (cmlpl_amd.knn.knn: the vote itself) ... kNN evaluation of the spectral embedding
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
 """
@@ -38,4 +39,7 @@ def __getattr__(name):
                 "nll_temps_host"):
         from . import calibrate
         return getattr(calibrate, name)
+    if name in ("embed", "KnnEvaluator", "KnnResult", "knn_host", "vote_host"):
+        from . import knn
+        return getattr(knn, name)
     raise AttributeError(name)

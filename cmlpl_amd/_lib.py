@@ -48,6 +48,7 @@ EXPORTS = (
     "cmlpl_infer_cube_tta_sym", "cmlpl_infer_pixels_tta_sym", "cmlpl_tta_patches_sym",   # added after ABI 6, no bump: flip / rotate views
     "cmlpl_pl_stats", "cmlpl_pl_stats_hard",                                     # added after ABI 6, no bump: the pseudo-label monitor
     "cmlpl_reliability", "cmlpl_temper_probs", "cmlpl_nll_temps",                # added after ABI 6, no bump: calibration
+    "cmlpl_embed", "cmlpl_knn_workspace_bytes", "cmlpl_knn",                     # added after ABI 6, no bump: kNN evaluation
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -283,6 +284,10 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_reliability.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp]
     lib.cmlpl_temper_probs.argtypes = [vp, i32, i32, f32, vp, vp, vp, vp, vp]
     lib.cmlpl_nll_temps.argtypes = [vp, i32, vp, vp, i32, C.POINTER(f32), i32, vp, vp]
+    lib.cmlpl_embed.argtypes = [SP, i32, vp, i64, vp, vp, i32, vp, vp, vp]
+    lib.cmlpl_knn_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.cmlpl_knn_workspace_bytes.restype = sz
+    lib.cmlpl_knn.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_scene_workspace_bytes.argtypes = [i64, i32, i32]
     lib.cmlpl_scene_workspace_bytes.restype = sz
     lib.cmlpl_scene_gram.argtypes = [vp, i32, i64, i32, vp, vp, vp, sz, vp]
@@ -323,7 +328,7 @@ def load(path: str = LIB_PATH):
         if hasattr(lib, s) and s not in ("cmlpl_workspace_bytes", "cmlpl_loss_workspace_bytes", "cmlpl_ntxent_workspace_bytes",
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
                      "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes",
-                     "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes"):
+                     "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes", "cmlpl_knn_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

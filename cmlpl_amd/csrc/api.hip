@@ -1163,6 +1163,23 @@ int cmlpl_infer_pixels(const cmlpl_shape* shape, int nets, const float* d_params
                     d_spec_row, d_pix, 0, n, d_labels, d_logits, d_workspace, workspace_bytes, stream, nullptr);
 }
 
+// The embedding of listed spectra rows (include/cmlpl.h): the spectral launch of infer_impl straight into d_feat, then the
+// normalisation in place (feat_norm_kernel reads its own float4 before it stores it).
+int cmlpl_embed(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride, const float* d_spectra,
+                const int64_t* d_spec_row, int n, float* d_feat, float* d_norm, void* stream) {
+  Dims d;
+  cmlpl_layout_t L;
+  if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
+  if (!d_params || !d_spectra || !d_feat || !d_norm || n < 1 || nets < 1 || nets > 2 ||
+      (nets == 2 && param_stride < L.param_total) || (reinterpret_cast<uintptr_t>(d_feat) & 15))
+    return CMLPL_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = chk(launch_spe_fwd(nets, n, d.bands, d_spectra, d_params + L.param_off[6], d_params + L.param_off[7],
+                               (long long)param_stride, d_feat, st, (const long long*)d_spec_row, 0)))) return rc;
+  return chk(launch_feat_norm(nets, n, d_feat, d_norm, d_feat, (long long)n * 1024, st));
+}
+
 int cmlpl_infer_cube_tta_sym(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
                              int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
                              float* d_logits, void* d_workspace, size_t workspace_bytes, void* stream, float sigma,

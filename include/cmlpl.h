@@ -1075,6 +1075,60 @@ int cmlpl_nll_temps(const float* d_probs /* [rows][K] */, int K, const int64_t* 
                     const int64_t* d_truth /* [n] */, int n, const float* betas /* host, [S] */, int S,
                     int64_t* d_sums /* [2][S] */, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- kNN EVALUATION OF THE SPECTRAL EMBEDDING: the embedding of listed
+ * spectra rows, and the weighted kNN classifier of Wu et al. ("Unsupervised Feature Learning via Non-Parametric Instance
+ * Discrimination", CVPR 2018, section 3.4) over such rows.  The reference has no counterpart.
+ *
+ * cmlpl_embed: feat = the 1024-wide L2-normalised output of the spectral branch (tools/models.py:142-146) of item i < n,
+ *   whose spectrum is row d_spec_row[i] of d_spectra [.][bands], or row i when d_spec_row is NULL.  `nets` (1 or 2) flat
+ *   parameter blocks param_stride floats apart, as cmlpl_infer_pixels takes them; every network reads the same rows.
+ *   d_feat [nets][n][1024], d_norm [nets][n] = the row's length before the division -- REQUIRED: a zero there marks a
+ *   dead-ReLU row, whose feat row is 0 / 0 = NaN, as everywhere else.  Two launches of kernels that exist (feat_spe + ReLU
+ *   from the canonical weights, then the normalisation in place: a thread reads its own four values before it stores them),
+ *   no workspace: bit-equal to the feat cmlpl_basenet2_fwd returns in eval mode for the same spectra rows.  d_spec_row is
+ *   followed without a bounds check.  CMLPL_E_SHAPE: a shape cmlpl_layout refuses; CMLPL_E_ARG: a null pointer, n < 1, nets
+ *   outside 1 .. 2, a stride shorter than a network, a d_feat that is not 16-byte aligned.
+ *
+ * THE DEFINITION OF A kNN VOTE.  Query rows q_i (i < n) and gallery rows g_j (j < m), 1024 floats each.
+ *   Similarity.  s_ij is the dot product of q_i and g_j to fp32 accuracy.  The BITS of s_ij are a function of the two rows'
+ *     bytes alone: not of i, j, n, m, the tile, the grid or the run.  (Each row is split once into two fp16 pieces at the
+ *     scale 2^12, x 2^12 = hi + lo; the 64 steps of 16 elements run in ascending order, each adding the products lo.hi,
+ *     hi.lo and hi.hi of its 16 elements in that order to an fp32 accumulator; 2^-24 is folded in at the end; tails are
+ *     rows of zeros.  The rows are meant to be unit vectors: an element of magnitude 16 or more leaves fp16's range, and
+ *     its row's similarities are then not finite.)
+ *   Candidates.  Gallery row j is a candidate of query i iff s_ij is finite (a NaN row on either side is never a
+ *     neighbour), j != d_skip[i] (NULL or -1: nothing is skipped; leave-one-out passes the query's own gallery index), and,
+ *     when labels are given, 0 <= d_gallery_label[j] < K (unknown truths are never neighbours).
+ *   Neighbours.  The first k' = min(k, candidates) candidates in the order (s descending, j ascending); equal floats, +0
+ *     and -0 included, go by index.  Those are ranks 0 .. k' - 1; ranks k' .. k - 1 store idx = -1, sim = -inf.  A query
+ *     without any candidate stores a NaN d_probs row and label -1.
+ *   Vote.  A fixed fp32 chain: w_r = expf(fl32(fl32(s_r - s_0) inv_T)), so w_0 is exactly 1; den and score[label_r] are
+ *     accumulated r ASCENDING from 0 (den = den + w_r, score[label_r] = score[label_r] + w_r); p[c] = score[c] / den; label =
+ *     the FIRST maximum of p.  inv_T = fl32(1 / T) is formed in double by the caller.
+ *   Determinism.  No float atomics; the same bytes on every run; a query's outputs do not depend on where it stands in the
+ *     list or on how the list is chunked.
+ *
+ * cmlpl_knn: that definition.  n, m >= 1; 1 <= k <= 32; with labels 1 <= K <= 64 and a finite inv_T > 0; with
+ *   d_gallery_label == NULL, K is 0 and d_probs / d_labels must be NULL.  d_nbr_idx [n][k] int32, d_nbr_sim [n][k],
+ *   d_probs [n][K], d_labels [n] int64: ANY of them may be NULL.  Four launches (three when d_query == d_gallery and
+ *   n == m: one set of pieces): the split of each side into fragment planes in the workspace, the streaming pass --
+ *   similarity tiles on v_mfma_f32_32x32x16_f16, the queries on the lanes, selection against a per-lane threshold, the lists
+ *   in LDS; the [n][m] matrix never exists -- and the merge + vote, one wavefront per query.  d_skip and the labels are
+ *   DATA ON THE DEVICE; nothing synchronises or allocates.  Workspace: cmlpl_knn_workspace_bytes(n, m, k) (0 for arguments
+ *   outside the ranges): 4 KiB per row of either side, padded to 128 rows, and the partial lists.
+ *   CMLPL_E_ARG: a null d_query / d_gallery / d_workspace, a range above, K / d_probs / d_labels without labels, d_query /
+ *   d_gallery / d_workspace not 16-byte aligned, another misaligned pointer; CMLPL_E_WORKSPACE -- all before any launch. */
+int cmlpl_embed(const cmlpl_shape* shape, int nets, const float* d_params, int64_t param_stride,
+                const float* d_spectra, const int64_t* d_spec_row /* [n] or NULL */, int n,
+                float* d_feat /* [nets][n][1024] */, float* d_norm /* [nets][n] */, void* stream);
+size_t cmlpl_knn_workspace_bytes(int n, int m, int k);
+int cmlpl_knn(const float* d_query /* [n][1024] */, int n, const float* d_gallery /* [m][1024] */, int m,
+              const int64_t* d_gallery_label /* [m] or NULL */, int K, const int64_t* d_skip /* [n] or NULL */,
+              int k, float inv_T,
+              int32_t* d_nbr_idx /* [n][k] or NULL */, float* d_nbr_sim /* [n][k] or NULL */,
+              float* d_probs /* [n][K] or NULL */, int64_t* d_labels /* [n] or NULL */,
+              void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

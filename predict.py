@@ -32,7 +32,13 @@ probabilities are its own softmax.  ``--temperature T`` tempers the FINAL probab
 smoothing), ``q = softmax(log p / T)``: a further ``Result:`` block follows with ``_T`` appended to the tag, and ``--out`` /
 ``--proba`` / ``--confidence`` / ``--entropy`` describe the tempered prediction.  ``--temperature fit`` finds T itself, the least
 NLL on a seeded random share (``--calib_frac``, default 0.5; ``--calib_seed``, default 1088) of the labelled test pixels; every
-``Reliability`` line of such a run is counted on the held-out remainder only, and says so."""
+``Reliability`` line of such a run is counted on the held-out remainder only, and says so.  ``--knn K`` scores the EMBEDDING
+instead of the classifier: the weighted kNN vote (cmlpl_amd.knn: K neighbours by cosine similarity of the spectral branch's
+``feat``, weights exp(s / T), T = ``--knn_T``, default the checkpoint's training temperature) of the labelled test pixels over
+the training pixels (``--knn_gallery train``) or leave-one-out among themselves (``loo``): one ``Result:`` block per network of
+``--net 0 | 1 | both | ema0 | ema1 | ema_both`` with the tag ``_knn``, ``--reliability`` prints its line behind it (the vote's
+probabilities are a probability map over the test list), ``--embed FILE`` writes the float32 [n_test][1024] embedding of a
+single network.  No label map is written: the vote is over the test list, not the scene."""
 import argparse
 import os
 
@@ -98,8 +104,77 @@ def check_args(args):
                          "ensemble for the two together)" % args.net)
 
 
+def check_knn_args(args):
+    """what --knn / --embed cannot mean"""
+    if args.knn is None:
+        if args.knn_T is not None or args.knn_gallery is not None:
+            raise SystemExit("--knn_T / --knn_gallery belong to --knn K")
+        if args.embed is None:
+            return
+    elif not 1 <= args.knn <= 32:
+        raise SystemExit("--knn K: 1 .. 32 neighbours")
+    if args.knn_T is not None and not (0.0 < args.knn_T < float("inf")):
+        raise SystemExit("--knn_T T: a finite T > 0")
+    if args.net in ENSEMBLES:
+        raise SystemExit("--knn / --embed score the embedding of ONE network at a time: --net %s averages class probabilities "
+                         "(name a network, or both / ema_both)" % args.net)
+    if args.embed and args.net in ('both', 'ema_both'):
+        raise SystemExit("--embed writes the embedding of a single network: not with --net %s" % args.net)
+    if args.out or args.proba or args.confidence or args.entropy or args.tta is not None or smooth_of(args) is not None \
+            or temperature_of(args) is not None:
+        raise SystemExit("--knn / --embed describe the labelled test pixels, not the scene: not with --out, --proba, --confidence, "
+                         "--entropy, --tta, --smooth or --temperature")
+
+
+def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members):
+    """--knn / --embed: the embedding of the labelled test pixels under the networks of --net, and its kNN vote"""
+    from cmlpl_amd import NetShape
+    from cmlpl_amd.knn import KnnEvaluator, embed
+    from train import build_nets, print_result
+    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
+    rows = np.asarray(test_array, np.int64)
+    Xt = on(whole.X[rows] if torch.is_tensor(whole.X) else np.asarray(whole.X[rows]), torch.float32)
+    Yt = on(np.asarray(Y_test), torch.int64)
+    models = build_nets(shape, members, device, hp["dropout"])
+    for model in models:
+        model.eval()
+    if args.embed:
+        np.save(args.embed, embed(models[0], Xt)[0].cpu().numpy())
+    if args.knn is None:
+        return None
+    loo = args.knn_gallery == 'loo'
+    if loo:
+        gallery = (Xt, Yt)
+    elif args.synthetic:          # the labelled split train.py --synthetic drew (its flags are in the checkpoint)
+        from hsi_loader import SyntheticHSIDataSet
+        saved = ck["extra"].get("args", {})
+        scene = whole if (saved.get("windows") == "cube" or saved.get("synthetic_scene")) else None
+        lab = SyntheticHSIDataSet(shape, saved.get("num_unlabel", 10000), 'label', seed=1, scene=scene)
+        gallery = (on(lab.X, torch.float32), on(lab.Y, torch.int64))
+    else:
+        lab = HSIDataSet(int(args.dataID), 'label')
+        gallery = (on(lab.X, torch.float32), on(lab.Y, torch.int64))
+    T = hp.get("temperature", 0.3) if args.knn_T is None else args.knn_T
+    ev = KnnEvaluator(NetShape(*shape), *gallery, *((None, None) if loo else (Xt, Yt)), k=args.knn, T=T, loo=loo)
+    score = RelScore(np.arange(len(rows)), Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins) \
+        if args.reliability else None
+    first = None
+    for key, model in zip(which, models):
+        ev.evaluate(model)
+        tag = '_knn' + NET_TAGS[key]
+        labels = ev.last.labels[0].cpu().numpy()
+        print_result(tag, labels, np.arange(len(rows)), np.asarray(Y_test))
+        if score is not None:
+            score(tag, ev.last._replace(probs=ev.last.probs[0]))
+        first = labels if first is None else first
+    if args.save_reliability:
+        score.save(args.save_reliability)
+    return first
+
+
 def main(args, device=None):
     check_args(args)
+    check_knn_args(args)
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -134,6 +209,10 @@ def main(args, device=None):
     extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
     common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
     members = [(k, ck[keys[k]]) for k in which]
+    if args.knn is not None or args.embed:
+        if test_array is None:
+            raise SystemExit("--knn / --embed need the labelled test pixels (test_array.npy and Y.npy in the dataset directory)")
+        return knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members)
     smooth, tta = smooth_of(args), None
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
@@ -236,6 +315,16 @@ def build_parser():
                              'Reliability line is then counted on the remainder')
     parser.add_argument('--calib_seed', type=int, default=None, metavar='N',
                         help='--temperature fit: the seed of that share (default 1088)')
+    parser.add_argument('--knn', type=int, default=None, metavar='K',
+                        help='score the embedding: the weighted kNN vote (K neighbours) of the labelled test pixels, one Result: '
+                             'block per network of --net with the tag _knn (not with the ensembles)')
+    parser.add_argument('--knn_T', type=float, default=None, metavar='T',
+                        help="--knn: the temperature of the vote (default: the checkpoint's training temperature)")
+    parser.add_argument('--knn_gallery', choices=('train', 'loo'), default=None,
+                        help="--knn: the gallery -- the labelled training pixels (train, the default) or leave-one-out among the "
+                             "test pixels (loo)")
+    parser.add_argument('--embed', default=None, metavar='FILE',
+                        help='write the float32 [n_test][1024] embedding of the labelled test pixels under a single network as .npy')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

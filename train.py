@@ -51,6 +51,11 @@ Differences from the reference that are deliberate, MI355X-first choices:
     line -- ECE, MCE, NLL, Brier score, mean confidence and accuracy of that block's class probabilities over the labelled
     test pixels, from integer counters kept on the device (cmlpl_amd.calibrate).  It needs ``--ensemble``, ``--tta`` or
     ``--smooth``; ``loss_hist``, checkpoints and every other line are what they are without the flag.
+  * ``--knn K`` (``--knn_T T``, default ``--temperature``): the embedding itself is scored -- the weighted kNN vote
+    (cmlpl_amd.knn: K neighbours by cosine similarity of the spectral branch's ``feat``, each weighted by exp(s / T)) of the
+    test split's pixels over the labelled training pixels, untiled.  With ``--eval_every`` two more lines per evaluation
+    (``validation_knn`` / ``validation_knn1``) and a curve of its own (``curve_knn`` in ``--save_eval``; in the checkpoints,
+    restored by ``--resume``); the same two lines once after the last epoch.  One GPU; ``loss_hist`` is what it is without it.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -131,10 +136,11 @@ def run_record(args, hp, shape, from_scene):
 
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
-    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability) is left out at its default, so a file written without it is byte for byte what it
+    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T) is left out at its default, so a file written without it is byte for byte what it
     was before the flag existed"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
-            'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False}
+            'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
+            'knn': None, 'knn_T': None}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
 
 
@@ -450,7 +456,7 @@ def load_data(run, args):
         run.shape = shape = SYNTH[args.synthetic]
         # (--windows cube / --synthetic_scene: both splits are seeded pixels of ONE synthetic scene, the evaluation's)
         run.from_scene = args.windows == 'cube' or args.synthetic_scene
-        if run.from_scene or not args.no_eval or args.eval_every > 0:
+        if run.from_scene or not args.no_eval or args.eval_every > 0 or args.knn is not None:
             run.whole = SyntheticScene(shape, 64, 64, seed=3)       # a 64 x 64 scene cube, every pixel a test pixel
         scene = run.whole if run.from_scene else None
         run.labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=scene)
@@ -550,6 +556,34 @@ def build_evaluator(run, args):
     run.evaluator = Evaluator(NetShape(*run.shape), cube_ev, Xt, Yt, pix_t)
 
 
+def build_knn(run, args):
+    """--knn: the kNN evaluation of the spectral embedding (cmlpl_amd.knn.KnnEvaluator), registered once -- the gallery is the
+    labelled training pixels UNTILED (5 per class: fewer candidates of a class than k is the normal case), the queries are
+    the test split's; spectra and labels only, no cube"""
+    from cmlpl_amd.knn import KnnEvaluator
+    device = run.device
+    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
+    if args.synthetic:
+        gallery, queries = run.labeled, run.whole
+    else:
+        gallery, queries = HSIDataSet(int(args.dataID), 'label'), HSIDataSet(int(args.dataID), 'test')
+    run.knn = KnnEvaluator(NetShape(*run.shape), on(gallery.X, torch.float32), on(gallery.Y, torch.int64),
+                           on(queries.X, torch.float32), on(queries.Y, torch.int64), k=args.knn,
+                           T=args.temperature if args.knn_T is None else args.knn_T)
+
+
+def knn_lines(run, args, epoch):
+    """the ``validation_knn`` / ``validation_knn1`` lines of the engine's two networks after ``epoch`` epochs: (rows, matrices)"""
+    from cmlpl_amd.evaluate import metrics
+    cms, rows = run.knn.evaluate((run.eng, None)).cpu().numpy(), []
+    for net, cm in enumerate(cms):
+        OA, Kappa, _, AA = metrics(cm)
+        rows.append((OA, AA, Kappa))
+        print('Epoch %d/%d: validation_knn%s OA = %.2f AA = %.2f Kappa = %.2f' %
+              (epoch, args.num_epochs, NET_TAGS[net], OA * 100, AA * 100, Kappa * 100))
+    return rows, cms
+
+
 def restore_progress(run, args):
     ex = run.resumed["extra"]
     run.start_epoch = int(ex["epoch"])
@@ -560,6 +594,8 @@ def restore_progress(run, args):
     if run.evaluator is not None:      # (a leg without --eval_every leaves a gap in the curves, not an error)
         for curve in run.curves.values():
             curve.restore(ex)
+    elif run.knn is not None:          # (--knn without --eval_every adds nothing to its curve, and keeps what it was)
+        run.curves['_knn'].restore(ex)
     if args.pl_stats and "pl_curve" in ex:      # (a leg without --pl_stats leaves a gap in the curve, not an error)
         run.pl_curve = list(ex["pl_curve"].numpy())
     if run.curves[''].epochs:          # --save_best: network 0's best validation so far
@@ -598,6 +634,8 @@ def validate(run, args, epoch):
             print('Epoch %d/%d: validation%s%s OA = %.2f AA = %.2f Kappa = %.2f' %
                   (epoch, args.num_epochs, suffix, NET_TAGS[net], OA * 100, AA * 100, Kappa * 100))
         curve.add(epoch, rows[0] if curve.nets is None else rows, cms)
+    if run.knn is not None:               # --knn: the embedding's kNN vote, two more lines and a curve of its own
+        run.curves['_knn'].add(epoch, *knn_lines(run, args, epoch))
     oa = run.curves[''].rows[-1][0][0]
     if args.save_best and (run.best_oa is None or oa > run.best_oa):
         # network 0's best validation so far (the first of equals): the state is copied on the device, behind
@@ -733,6 +771,8 @@ def report(run, args):
             print(curves['_ens'].best_line())
         if args.save_eval:
             np.savez(args.save_eval, **{k: v for curve in curves.values() if curve.epochs for k, v in curve.npz_entries().items()})
+    if run.knn is not None and not (curves['_knn'].epochs and curves['_knn'].epochs[-1] == args.num_epochs and run.evaluator is not None):
+        knn_lines(run, args, args.num_epochs)        # (once after the last epoch: --eval_every has not just printed them)
     if args.no_eval:
         return
     nets = [(net, eng.state_dict(net)) for net in range(2)]
@@ -791,18 +831,25 @@ def main(args, make_engine=None, device=None):
     if args.save_pl and not args.pl_stats:
         raise SystemExit("--save_pl belongs to --pl_stats")
     check_reliability_args(args, smooth)
+    if args.knn is not None and world > 1:
+        raise SystemExit(f"--knn runs on one GPU (this job has {world} ranks)")
+    if args.knn is not None and not 1 <= args.knn <= 32:
+        raise SystemExit("--knn K: 1 .. 32 neighbours")
+    if args.knn_T is not None and (args.knn is None or not (0.0 < args.knn_T < float("inf"))):
+        raise SystemExit("--knn_T T: a finite T > 0, with --knn K")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
     torch.manual_seed(1088)                                         # seed_torch(), train.py:50-58
     # ``run`` is what the phases hand to one another; beside each is what it adds.  The curves: the two networks'; --ema: the same
     # of the teachers, a curve of their own; --ensemble: the pair's together.  ``gen``: the same permutations on every rank
-    curves = [EvalCurve(sfx, nets) for sfx, nets, on in (('', 2, True), ('_ema', 2, args.ema), ('_ens', None, args.ensemble)) if on]
+    curves = [EvalCurve(sfx, nets) for sfx, nets, on in (('', 2, True), ('_ema', 2, args.ema), ('_ens', None, args.ensemble),
+                                                                 ('_knn', 2, args.knn is not None)) if on]
     run = argparse.Namespace(world=world, rank=rank, device=device, bt=args.labeled_batch_size, btu=args.unlabeled_batch_size,
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
                              evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth,
-                             pl_curve=[])
+                             pl_curve=[], knn=None)
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -816,6 +863,8 @@ def main(args, make_engine=None, device=None):
         raise SystemExit("--pl_stats needs the labels of the unlabelled split")
     if args.eval_every > 0 and rank == 0:
         build_evaluator(run, args)    # evaluator
+    if args.knn is not None and rank == 0:
+        build_knn(run, args)          # knn: --knn's gallery and queries
     if args.resume:
         restore_progress(run, args)   # start_epoch, its rows of loss_hist, the curves so far and best_oa
     train_epochs(run, args)
@@ -906,6 +955,13 @@ def build_parser():
     parser.add_argument('--eval_every', type=int, default=0,
                         help='score both networks on the test split after every N-th epoch, on the device (0: never); '
                              'real data needs cube.npy + scene.json')
+    parser.add_argument('--knn', type=int, default=None, metavar='K',
+                        help="score the spectral embedding itself: the weighted kNN vote (K neighbours, cmlpl_amd.knn) of the test "
+                             "split's pixels over the labelled training pixels -- two more lines validation_knn / validation_knn1 per "
+                             "--eval_every evaluation (curve_knn in --save_eval and the checkpoints) and once after the last epoch; "
+                             "one GPU")
+    parser.add_argument('--knn_T', type=float, default=None, metavar='T',
+                        help='--knn: the temperature of the vote (default: --temperature, the one the similarity softmax trains under)')
     parser.add_argument('--save_eval', default=None,
                         help='--eval_every: write the curve [evaluations][nets][OA, AA, Kappa], its epochs and the '
                              'confusion matrices as .npz')

@@ -49,6 +49,7 @@ EXPORTS = (
     "cmlpl_pl_stats", "cmlpl_pl_stats_hard",                                     # added after ABI 6, no bump: the pseudo-label monitor
     "cmlpl_reliability", "cmlpl_temper_probs", "cmlpl_nll_temps",                # added after ABI 6, no bump: calibration
     "cmlpl_embed", "cmlpl_knn_workspace_bytes", "cmlpl_knn",                     # added after ABI 6, no bump: kNN evaluation
+    "cmlpl_debug_unsup_plan", "cmlpl_debug_memobank_plan",                       # added after ABI 6, no bump: test aids (memobank.hip)
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -319,6 +320,8 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_debug_route.argtypes = [SP, i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_wgrad3_plan.argtypes = [SP, i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_loss_plan.argtypes = [SP, C.POINTER(Shard), i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_unsup_plan.argtypes = [i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_memobank_plan.argtypes = [i32, i32, i32, i32, C.POINTER(i32)]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]

@@ -1323,6 +1323,8 @@ int cmlpl_memobank_loss(const cmlpl_memobank_call* c, void* stream) {
     return CMLPL_E_ARG;
   if ((c->d_anchor_draw == nullptr) != (c->d_neg_draw == nullptr)) return CMLPL_E_ARG;
   if (c->d_momentum && (!c->d_momentum_on || !c->d_prototype)) return CMLPL_E_ARG;
+  MbPlan plan;                          // every refusal before the first launch: a refused call has touched nothing
+  if (!plan_mb_onepass(c->D, c->K, c->queries, c->negatives, &plan)) return CMLPL_E_ARG;
   MbPrep p;
   p.prob_l = c->d_prob_l; p.prob_u = c->d_prob_u; p.label_l = c->d_label_l; p.label_u = c->d_label_u;
   p.low_mask = c->d_low_mask; p.high_mask = c->d_high_mask; p.rep_t = c->d_rep_teacher;
@@ -1494,6 +1496,20 @@ int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, in
   int* o = out;
   *o++ = p.kernel; *o++ = p.MB; *o++ = p.NBW; *o++ = p.gx; *o++ = p.gy; *o++ = p.ctiles;
   *o++ = loss_dfeat_lds_shape(a) ? 1 : 0; *o++ = plan_loss_dfeat_lds(a) ? 1 : 0; *o++ = device_cus();
+  return 0;
+}
+
+int cmlpl_debug_unsup_plan(int B, int K, int* out) {
+  UnsupPlan p;
+  if (!out || !plan_unsup(B, K, &p)) return CMLPL_E_ARG;
+  out[0] = p.route; out[1] = p.regrows;
+  return 0;
+}
+
+int cmlpl_debug_memobank_plan(int D, int K, int queries, int negatives, int* out) {
+  MbPlan p;
+  if (!out || !plan_mb_onepass(D, K, queries, negatives, &p)) return CMLPL_E_ARG;
+  out[0] = p.kernel; out[1] = (int)p.lds_infonce; out[2] = (int)p.lds_scatter;
   return 0;
 }
 

@@ -423,8 +423,16 @@ struct MbLoss {
   float* lossq; float* ganchor; int* arow; float* drep; float* total;
 };
 
+// the launch plan of the one-pass call (plan_mb_onepass; launch_mb_onepass runs what it says and decides nothing itself)
+enum { MB_GENERAL = 0 };                            // MbPlan.kernel: mb_infonce_all_kernel, else NCH of mb_infonce_fast_kernel<NCH>
+constexpr size_t MB_SCATTER_LDS_MAX = 64 * 1024;    // mb_scatter_all_kernel's slot list: K * queries <= 16384
+struct MbPlan { int kernel; size_t lds_infonce, lds_scatter; };
+bool plan_mb_onepass(int D, int K, int Q, int NN, MbPlan* p);
 hipError_t launch_mb_onepass(const MbPrep& pa, const MbLoss& la, hipStream_t st);
 size_t unsup_ws_bytes(int B);
+enum { US_ONEWG = 0, US_THREE = 1, US_FIVE = 2 };   // UnsupPlan.route: us_onewg_kernel; us_entropy2 / us_select1 / us_apply; the five rank-counting launches
+struct UnsupPlan { int route, regrows; };
+bool plan_unsup(int B, int K, UnsupPlan* p);
 hipError_t launch_unsup(const float* predict, long long* target, const float* teacher, int B, int K, double percent,
                         float* loss, float* dpredict, void* ws, hipStream_t st);
 

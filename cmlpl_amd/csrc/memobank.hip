@@ -180,8 +180,11 @@ __global__ __launch_bounds__(256) void mb_infonce_kernel(const float* __restrict
   const float selfc = s_misc[0] * s_misc[1];
   float* go = ganchor + (size_t)q * D;
   for (int d = tid; d < D; d += 256) {
+    // the negatives first, the positive key last: its weight (softmax - 1) is up to NK times theirs, and a sum that
+    // starts with it rounds every later term at ITS magnitude (NK = 128, an anchor below the clamp: 2.8e-6 of the row)
     float s = 0.f;
-    for (int j = 0; j < NK; ++j) s += s_w[j] * s_key[j][d];
+    for (int j = 1; j < NK; ++j) s += s_w[j] * s_key[j][d];
+    s += s_w[0] * s_key[0][d];
     go[d] = s - selfc * a[d];
   }
 }
@@ -561,8 +564,9 @@ __global__ __launch_bounds__(256) void mb_infonce_all_kernel(MbLoss a) {
   const float selfc = s_misc[0] * s_misc[1];
   float* go = a.ganchor + (size_t)slot * D;
   for (int d = tid; d < D; d += 256) {
-    float s = 0.f;
-    for (int j = 0; j < NK; ++j) s += s_w[j] * s_key[j][d];
+    float s = 0.f;                                 // (the positive key last: see mb_infonce_kernel)
+    for (int j = 1; j < NK; ++j) s += s_w[j] * s_key[j][d];
+    s += s_w[0] * s_key[0][d];
     go[d] = s - selfc * av[d];
   }
 }
@@ -792,30 +796,38 @@ __global__ __launch_bounds__(256) void mb_scatter_all_kernel(MbLoss a, int slots
   }
 }
 
+// What one cmlpl_memobank_loss call runs, decided once on the host (cmlpl_debug_memobank_plan shows it): the InfoNCE
+// kernel -- keys in registers where they fit (mb_infonce_fast_kernel<NCH>, NCH = ceil(D / 256)), else the general kernel
+// (keys re-read from L2) -- and the dynamic LDS of it and of the scatter.  false = the call is refused, and it is
+// refused HERE, before anything is launched: a call that cannot finish must not have enqueued into the bank.
+bool plan_mb_onepass(int D, int K, int Q, int NN, MbPlan* p) {
+  if (D < 1 || K < 1 || K > 1024 || Q < 1 || NN < 1 || NN + 1 > MB_MAXKEYS) return false;
+  const size_t scatter = (size_t)K * Q * sizeof(int);            // mb_scatter_all_kernel: the slots that drew a row
+  if (scatter > MB_SCATTER_LDS_MAX) return false;
+  const int NK = NN + 1, nch = (D / 4 + 63) / 64;
+  const bool fast = D % 4 == 0 && D >= 4 && D <= 1024 && K <= 64 && ((NK + 3) / 4) * nch <= 16 && switches().mb_fast != 0;
+  p->kernel = fast ? nch : MB_GENERAL;
+  p->lds_infonce = fast ? (size_t)4 * D * 4 : (size_t)D * 4;    // fast: [4][D] partial gradients; general: the positive key
+  p->lds_scatter = scatter;
+  // (the general kernel's static tables are 7 KiB; the fast kernel's D <= 1024 is 16 KiB at most)
+  return p->lds_infonce + 8 * 1024 <= LDS_MAX;
+}
+
 hipError_t launch_mb_onepass(const MbPrep& pa, const MbLoss& la, hipStream_t st) {
-  if (la.NN + 1 > MB_MAXKEYS || la.K > 1024) return hipErrorInvalidValue;
+  MbPlan pl;
+  if (!plan_mb_onepass(la.D, la.K, la.Q, la.NN, &pl)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mb_prepare_kernel, dim3(pa.K), dim3(256), 0, st, pa);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  {
-    // keys in registers where they fit (mb_infonce_fast_kernel), else the general kernel (keys re-read from L2)
-    const int NK = la.NN + 1, nch = (la.D / 4 + 63) / 64;
-    const bool fast = la.D % 4 == 0 && la.D >= 4 && la.D <= 1024 && la.K <= 64 && ((NK + 3) / 4) * nch <= 16 &&
-                      switches().mb_fast != 0;
-    const size_t lds = (size_t)4 * la.D * 4;
-    if (fast && nch == 1) hipLaunchKernelGGL(mb_infonce_fast_kernel<1>, dim3(la.Q, la.K), dim3(256), lds, st, la);
-    else if (fast && nch == 2) hipLaunchKernelGGL(mb_infonce_fast_kernel<2>, dim3(la.Q, la.K), dim3(256), lds, st, la);
-    else if (fast && nch == 3) hipLaunchKernelGGL(mb_infonce_fast_kernel<3>, dim3(la.Q, la.K), dim3(256), lds, st, la);
-    else if (fast && nch == 4) hipLaunchKernelGGL(mb_infonce_fast_kernel<4>, dim3(la.Q, la.K), dim3(256), lds, st, la);
-    else {
-      hipLaunchKernelGGL(mb_infonce_all_kernel, dim3(la.Q, la.K), dim3(256), (size_t)la.D * 4, st, la);
-    }
+  switch (pl.kernel) {
+    case 1: hipLaunchKernelGGL(mb_infonce_fast_kernel<1>, dim3(la.Q, la.K), dim3(256), pl.lds_infonce, st, la); break;
+    case 2: hipLaunchKernelGGL(mb_infonce_fast_kernel<2>, dim3(la.Q, la.K), dim3(256), pl.lds_infonce, st, la); break;
+    case 3: hipLaunchKernelGGL(mb_infonce_fast_kernel<3>, dim3(la.Q, la.K), dim3(256), pl.lds_infonce, st, la); break;
+    case 4: hipLaunchKernelGGL(mb_infonce_fast_kernel<4>, dim3(la.Q, la.K), dim3(256), pl.lds_infonce, st, la); break;
+    default: hipLaunchKernelGGL(mb_infonce_all_kernel, dim3(la.Q, la.K), dim3(256), pl.lds_infonce, st, la);
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const int slots = la.K * la.Q;
-  const size_t lds = (size_t)slots * sizeof(int);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mb_scatter_all_kernel, dim3(la.N + 1), dim3(256), lds, st, la, slots);
+  hipLaunchKernelGGL(mb_scatter_all_kernel, dim3(la.N + 1), dim3(256), pl.lds_scatter, st, la, la.K * la.Q);
   return hipGetLastError();
 }
 
@@ -1254,11 +1266,27 @@ __global__ __launch_bounds__(256) void us_apply_kernel(const float* __restrict__
 
 size_t unsup_ws_bytes(int B) { return ((size_t)3 * B + 16) * 4; }
 
-hipError_t launch_unsup(const float* predict, long long* target, const float* teacher, int B, int K, double percent,
-                        float* loss, float* dpredict, void* ws, hipStream_t st) {
+// Which of the three forms of compute_unsupervised_loss a batch takes, decided once on the host (cmlpl_debug_unsup_plan
+// shows it): one workgroup up to 1024 rows, three launches up to 8192, the five rank-counting launches beyond --
+// CMLPL_UNSUP_3L=0 gives the three-launch batches to the one workgroup (up to eight rows per thread), CMLPL_UNSUP_ONEWG=0
+// gives everything to the five launches.  `regrows`: the K <= 16 bodies that keep a row of logits in registers (the
+// five launches have none).
+bool plan_unsup(int B, int K, UnsupPlan* p) {
+  if (B < 1 || K < 1) return false;
   const bool onewg_off = switches().unsup_onewg == 0;
   const bool three_off = switches().unsup_3l == 0;
-  if (B > US1_T && B <= US1_T * US1_R && !onewg_off && !three_off) {
+  if (B > US1_T && B <= US1_T * US1_R && !onewg_off && !three_off) p->route = US_THREE;
+  else if (B <= US1_T * US1_R && !onewg_off) p->route = US_ONEWG;
+  else p->route = US_FIVE;
+  p->regrows = (p->route != US_FIVE && K <= US1_K) ? 1 : 0;
+  return true;
+}
+
+hipError_t launch_unsup(const float* predict, long long* target, const float* teacher, int B, int K, double percent,
+                        float* loss, float* dpredict, void* ws, hipStream_t st) {
+  UnsupPlan pl;
+  if (!plan_unsup(B, K, &pl)) return hipErrorInvalidValue;
+  if (pl.route == US_THREE) {
     float* ent3 = (float*)ws;                          // [B]
     float* bpart = ent3 + B;                            // [blocks]
     UsMid* mid = (UsMid*)(bpart + B);                   // (16-byte aligned: the workspace is, B floats twice)
@@ -1268,8 +1296,8 @@ hipError_t launch_unsup(const float* predict, long long* target, const float* te
     hipLaunchKernelGGL(us_apply_kernel, dim3(nb3), dim3(256), 0, st, predict, target, ent3, B, K, mid, bpart, loss, dpredict);
     return hipGetLastError();
   }
-  if (B <= US1_T * US1_R && !onewg_off) {
-    if (K <= US1_K) hipLaunchKernelGGL(us_onewg_kernel<true>, dim3(1), dim3(US1_T), 0, st, predict, target, teacher, B, K, percent, loss, dpredict);
+  if (pl.route == US_ONEWG) {
+    if (pl.regrows) hipLaunchKernelGGL(us_onewg_kernel<true>, dim3(1), dim3(US1_T), 0, st, predict, target, teacher, B, K, percent, loss, dpredict);
     else            hipLaunchKernelGGL(us_onewg_kernel<false>, dim3(1), dim3(US1_T), 0, st, predict, target, teacher, B, K, percent, loss, dpredict);
     return hipGetLastError();
   }

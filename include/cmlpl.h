@@ -735,7 +735,10 @@ int cmlpl_ntxent_fwd_bwd(const float* d_emb_i, const float* d_emb_j, int B, int 
 
 /* compute_unsupervised_loss (loss_helper.py:242-261): rows whose teacher entropy reaches the `percent`-th percentile
  * (numpy 'linear') of the valid rows are set to 255 IN d_target; d_loss[0] = (B / kept) * mean-over-kept CE;
- * d_dpredict [B][K] = d loss / d predict. */
+ * d_dpredict [B][K] = d loss / d predict.
+ * Nothing kept -- percent = 0 (every valid row reaches the threshold) or a batch whose rows are all 255 on entry: every
+ * row of d_target is 255 afterwards, d_dpredict is zero everywhere and d_loss[0] is not finite (B / 0 times 0 / 0, like
+ * the reference); the call returns 0.  All three forms of the computation (cmlpl_debug_unsup_plan) give this answer. */
 size_t cmlpl_unsup_workspace_bytes(int B);
 int cmlpl_unsup_loss(const float* d_predict, int64_t* d_target, const float* d_pred_teacher, int B, int K,
                      double percent, float* d_loss, float* d_dpredict, void* d_workspace, size_t workspace_bytes,
@@ -777,7 +780,10 @@ int cmlpl_memobank_infonce(const float* d_rep, int N, int D, const int32_t* d_po
  * Draws: d_anchor_draw [K][queries] / d_neg_draw [K][queries*negatives] int64 indexed by LOOP POSITION replace the two
  * torch.randint calls (:164,:179) -- entries must be in range for the positions that exist; NULL = drawn in-kernel
  * (Philox keyed by seed / call).  d_momentum [K][queries][D] + d_momentum_on (device int: "not all zero", :196) +
- * ema select the prototype blend of :194-203; then d_prototype [K][queries][D] receives `prototype`. */
+ * ema select the prototype blend of :194-203; then d_prototype [K][queries][D] receives `prototype`.
+ * Limits: K <= 1024, negatives <= 127, K * queries <= 16384 (the scatter keeps one int per (position, query) slot in
+ * 64 KiB of LDS; K = 64 at queries = 256 is exactly the limit and runs).  A call outside them returns CMLPL_E_ARG
+ * BEFORE anything is launched: d_bank, d_state and every output are untouched (cmlpl_debug_memobank_plan tells). */
 typedef struct cmlpl_memobank_call {
   const float* d_rep; const float* d_rep_teacher;
   const float* d_prob_l; const float* d_prob_u; const float* d_label_l; const float* d_label_u;
@@ -894,6 +900,24 @@ int cmlpl_debug_wgrad3_plan(const cmlpl_shape* shape, int nets, int n, int* out)
  * Host arithmetic only, nothing is launched.  CMLPL_E_ARG (what cmlpl_loss_fwd_bwd refuses) / CMLPL_E_SHAPE. */
 #define CMLPL_LOSS_PLAN_INTS 9
 int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, int bank_rows, int smooth, int* out);
+
+/* Added after ABI 6, no bump (nothing existing moves).  Test aids: what the launchers of cmlpl_unsup_loss and
+ * cmlpl_memobank_loss (plan_unsup / plan_mb_onepass, the functions they obey) decide under the current switches.
+ * cmlpl_debug_unsup_plan, out[CMLPL_UNSUP_PLAN_INTS]:
+ *   [0] 0 = one workgroup (us_onewg_kernel: B <= 1024, or B <= 8192 under CMLPL_UNSUP_3L=0 with up to eight rows per
+ *       thread), 1 = three launches (us_entropy2 / us_select1 / us_apply: 1024 < B <= 8192), 2 = the five rank-counting
+ *       launches (B > 8192, or every B under CMLPL_UNSUP_ONEWG=0)
+ *   [1] 1 = the bodies that hold a row of K <= 16 logits in registers (routes 0 and 1 only), 0 = the per-k loops
+ * cmlpl_debug_memobank_plan, out[CMLPL_MEMOBANK_PLAN_INTS]:
+ *   [0] the InfoNCE kernel: 0 = mb_infonce_all_kernel (general), NCH = 1 .. 4 = mb_infonce_fast_kernel<NCH> (keys in
+ *       registers: D a multiple of 4 and <= 1024, K <= 64, ceil((negatives + 1) / 4) * ceil(D / 256) <= 16, CMLPL_MB_FAST
+ *       not 0)
+ *   [1] its dynamic LDS bytes   [2] the dynamic LDS bytes of mb_scatter_all_kernel (4 * K * queries)
+ * Host arithmetic only, nothing is launched.  CMLPL_E_ARG for what the launcher would refuse. */
+#define CMLPL_UNSUP_PLAN_INTS 2
+#define CMLPL_MEMOBANK_PLAN_INTS 3
+int cmlpl_debug_unsup_plan(int B, int K, int* out);
+int cmlpl_debug_memobank_plan(int D, int K, int queries, int negatives, int* out);
 
 /* Added after ABI 6, no bump (nothing existing moves) -- EDGE-PRESERVING SPATIAL SMOOTHING of class probability maps: the
  * probabilities of every class are averaged over a small neighbourhood in which a neighbour counts less the farther away

@@ -516,7 +516,8 @@ def unsupervised_loss(predict: torch.Tensor, target: torch.Tensor, percent: floa
     """compute_unsupervised_loss (loss_helper.py:242-261).  Rows whose teacher entropy is at or above the
     `percent`-th percentile of the valid rows' entropies are set to IGNORE; the loss is
     (B / #kept) * mean-over-kept CE(predict, target).  Returns (loss, target_after) -- the reference edits
-    `target` in place."""
+    `target` in place.  The working precision is the inputs': float64 `predict` / `pred_teacher` give entropy,
+    percentile, cross entropy and (by autograd) the gradient in float64."""
     B = predict.shape[0]
     with torch.no_grad():
         p = torch.softmax(pred_teacher, dim=1)
@@ -529,32 +530,45 @@ def unsupervised_loss(predict: torch.Tensor, target: torch.Tensor, percent: floa
         weight = B / kept.sum()                                                   # :256
     logp = F.log_softmax(predict, dim=1)
     picked = logp.gather(1, torch.where(kept, tgt, torch.zeros_like(tgt)).unsqueeze(1)).squeeze(1)
-    ce = -(picked * kept.float()).sum() / kept.sum()                              # :258 (ignore_index mean)
+    ce = -(picked * kept.to(picked.dtype)).sum() / kept.sum()                     # :258 (ignore_index mean)
     return weight * ce, tgt
 
 
 def contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask, high_mask, memobank, ptrs, sizes,
-                         rep_teacher, anchor_idx=None, neg_idx=None, momentum_prototype=None, i_iter=0):
+                         rep_teacher, anchor_idx=None, neg_idx=None, momentum_prototype=None, i_iter=0,
+                         queries=MB_QUERIES, negatives=MB_NEGATIVES):
     """compute_contra_memobank_loss (loss_helper.py:39-219) with the random draws injected.
 
     rep, rep_teacher [N, D]; label_* one-hot [*, K]; prob_* [*, K]; low_mask / high_mask [N, 1];
     memobank: list (per class) of [m_c, D] tensors; ptrs / sizes: lists of ints.
-    anchor_idx[c] int64 [256]: positions into class c's low-entropy list (the reference's first randint, :164);
-    neg_idx[c] int64 [256*50]: rows of the class's bank AFTER this call's enqueue (second randint, :179).
-    Returns dict(loss, new_keys, memobank, ptrs, valid_classes, prototype).
+    anchor_idx[c] int64 [queries]: positions into class c's low-entropy list (the reference's first randint, :164);
+    neg_idx[c] int64 [queries*negatives]: rows of the class's bank AFTER this call's enqueue (second randint, :179);
+    `queries` / `negatives` default to the reference's 256 / 50.
+    Returns dict(loss, new_keys, memobank, ptrs, valid_classes, prototype, lists, proto).
+
+    Working precision: the dtype of `rep`.  Everything that SELECTS -- prob > 0.3, prob < 1, the ranks, the masks --
+    is evaluated on the float32 values of label / prob / mask whatever that dtype is (those comparisons are functions
+    of the float32 inputs alone; float32(0.3) is not the double 0.3); only the arithmetic on rep, rep_teacher, the
+    bank, the momentum prototype and the cosine / cross entropy runs in the dtype of `rep`.
 
     Kept quirk (:158-190): the loop over the `valid_seg` valid classes indexes the per-class anchor lists and
     prototypes by POSITION i (0..valid_seg-1), but the bank by valid_classes[i]."""
     K = label_l.shape[1]
     Nl = label_l.shape[0]
     D = rep.shape[1]
+    dt = rep.dtype
+    label_l, label_u, prob_l, prob_u, low_mask, high_mask = (t.float() for t in (label_l, label_u, prob_l, prob_u,
+                                                                                 low_mask, high_mask))
+    rep_teacher = rep_teacher.to(dt)
+    if momentum_prototype is not None:
+        momentum_prototype = momentum_prototype.to(dt)
     label = torch.cat((label_l, label_u), dim=0)
     low_valid = label * low_mask                                                   # :67
     high_valid = label * high_mask                                                 # :68
     prob = torch.cat((prob_l, prob_u), dim=0)                                      # :86
     rank_l, rank_u = class_ranks(prob_l), class_ranks(prob_u)
-    anchors_pool, protos, new_keys, valid_classes, counts = [], [], [], [], []
-    bank = [b.clone() for b in memobank]
+    anchors_pool, protos, new_keys, valid_classes, counts, lists = [], [], [], [], [], []
+    bank = [b.to(dt).clone() for b in memobank]
     ptr_out = list(ptrs)
     for c in range(K):
         lv = low_valid[:, c].bool()
@@ -566,19 +580,23 @@ def contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask, high_m
         in_u = (rank_u[:, c] >= MB_LOW_RANK) & (rank_u[:, c] < MB_HIGH_RANK)       # :110-112
         in_l = (rank_l[:, c] < MB_LOW_RANK) & (label_l[:, c] == 0)                 # :117-121
         negative = high_entropy & torch.cat((in_l, in_u), dim=0)                   # :123
+        lists.append(tuple(m.nonzero().flatten() for m in (lv, low_entropy, negative)))
         bank[c], ptr_out[c], m = memobank_enqueue(rep_teacher[negative].detach(), bank[c], ptr_out[c], sizes[c])
         new_keys.append(m)                                                         # :126-133
         if int(lv.sum()) > 0:                                                      # :135-137
             counts.append(int(lv.sum()))
             valid_classes.append(c)
-    out = dict(new_keys=new_keys, memobank=bank, ptrs=ptr_out, valid_classes=valid_classes, prototype=None)
+    # (lists: per class the row indices of low_valid, the anchor pool and the negative keys, in row order;
+    #  proto: the class prototypes [K, D], a NaN row for a class without low_valid rows)
+    out = dict(new_keys=new_keys, memobank=bank, ptrs=ptr_out, valid_classes=valid_classes, prototype=None,
+               lists=lists, proto=torch.cat(protos, dim=0))
     if len(counts) <= 1:                                                           # :139-145
         out["loss"] = 0.0 * rep.sum()
         return out
     proto = torch.cat(protos, dim=0)                                               # :149  [K, D]
     valid_seg = len(counts)
-    prototype = torch.zeros(K, MB_QUERIES, 1, D)
-    total = torch.zeros(())
+    prototype = torch.zeros(K, queries, 1, D, dtype=dt)
+    total = torch.zeros((), dtype=dt)
     for i in range(valid_seg):
         vc = valid_classes[i]
         if anchors_pool[i].shape[0] == 0 or bank[vc].shape[0] == 0:                # :158-172
@@ -586,8 +604,8 @@ def contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask, high_m
             continue
         anchor = anchors_pool[i][anchor_idx[i]]                                    # :164-168  [Q, D]
         with torch.no_grad():
-            negs = bank[vc][neg_idx[i]].reshape(MB_QUERIES, MB_NEGATIVES, D)       # :176-185
-            pos = proto[i].view(1, 1, D).repeat(MB_QUERIES, 1, 1)                  # :186-192
+            negs = bank[vc][neg_idx[i]].reshape(queries, negatives, D)             # :176-185
+            pos = proto[i].view(1, 1, D).repeat(queries, 1, 1)                     # :186-192
             if momentum_prototype is not None:                                     # :194-203
                 if not bool((momentum_prototype == 0).all()):
                     ema = min(1 - 1 / i_iter, 0.999)
@@ -595,7 +613,7 @@ def contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask, high_m
                 prototype[vc] = pos.clone()
             keys = torch.cat((pos, negs), dim=1)                                   # :205-207  [Q, 51, D]
         logits = torch.cosine_similarity(anchor.unsqueeze(1), keys, dim=2)         # :209-211
-        total = total + F.cross_entropy(logits / MB_TEMP, torch.zeros(MB_QUERIES, dtype=torch.long))  # :213-215
+        total = total + F.cross_entropy(logits / MB_TEMP, torch.zeros(queries, dtype=torch.long))  # :213-215
     out["loss"] = total / valid_seg                                                # :217-219
     if momentum_prototype is not None:
         out["prototype"] = prototype

@@ -8,7 +8,7 @@ CASES_UNSUP = {
     "b": dict(B=300, K=16, percent=50.0, seed=302, ignored=17),
     "c": dict(B=1024, K=9, percent=100.0, seed=303, ignored=5),       # percentile 100: only the maximum is dropped
     "d": dict(B=37, K=4, percent=12.5, seed=304, ignored=3),
-    "e": dict(B=4096, K=9, percent=20.0, seed=305, ignored=100),      # eight rows per thread of the one-workgroup kernel
+    "e": dict(B=4096, K=9, percent=20.0, seed=305, ignored=100),      # the three launches (1024 < B <= 8192); CMLPL_UNSUP_3L=0: four rows per thread of the one-workgroup kernel
     "f": dict(B=9000, K=9, percent=70.0, seed=306, ignored=11),       # beyond it: the rank-counting kernels
     "g": dict(B=512, K=20, percent=35.0, seed=307, ignored=9),        # more classes than the register-row variant holds
 }

@@ -136,7 +136,8 @@ J_UNSUP_ML = _job("next", "unsup-multi", {"CMLPL_UNSUP_ONEWG": "0"}, ["tests/tes
 
 
 def test_multi_launch_unsupervised_loss_passes_losshelper_parity():
-    """the rank-counting kernels (what more than 8192 rows take) instead of the one-workgroup radix-select kernel"""
+    """CMLPL_UNSUP_ONEWG=0: every batch on the five rank-counting launches (the default only beyond 8192 rows: case f)
+    instead of the one-workgroup radix-select kernel (B <= 1024) and the three launches (1024 < B <= 8192: case e)"""
     _run(J_UNSUP_ML)
 
 
@@ -144,7 +145,8 @@ J_UNSUP_1 = _job("next", "unsup-onewg", {"CMLPL_UNSUP_3L": "0"}, ["tests/test_lo
 
 
 def test_one_workgroup_unsupervised_loss_up_to_8192_rows():
-    """the single-workgroup kernel also where the three-launch path (1024 < B <= 8192) is the default"""
+    """CMLPL_UNSUP_3L=0: the one-workgroup kernel also where three launches are the default (1024 < B <= 8192; case e,
+    B = 4096, then runs four rows per thread); B <= 1024 and B > 8192 go as they go without the switch"""
     _run(J_UNSUP_1)
 
 

@@ -50,6 +50,8 @@ EXPORTS = (
     "cmlpl_reliability", "cmlpl_temper_probs", "cmlpl_nll_temps",                # added after ABI 6, no bump: calibration
     "cmlpl_embed", "cmlpl_knn_workspace_bytes", "cmlpl_knn",                     # added after ABI 6, no bump: kNN evaluation
     "cmlpl_debug_unsup_plan", "cmlpl_debug_memobank_plan",                       # added after ABI 6, no bump: test aids (memobank.hip)
+    "cmlpl_grad_norm_partials_bytes", "cmlpl_grad_norm", "cmlpl_adam_step_opt", "cmlpl_train_step_opt",   # added after ABI 6, no bump:
+    "cmlpl_step_graph_create_opt", "cmlpl_dyn_adam_opt",                         # schedules, weight decay, gradient clipping
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -119,6 +121,11 @@ class Dyn(C.Structure):
 DYN_DTYPE = [("step", "<u8"), ("adam_t", "<i8"), ("lab_off", "<i8"), ("unl_off", "<i8"), ("ptr", "<i4", (2,)),
              ("smooth", "<i4"), ("adap_mask", "<f4"), ("hist_row", "<i4"), ("adam_step_size", "<f4"),
              ("adam_bc2_sqrt", "<f4"), ("reserved", "<i4")]
+
+
+class Optim(C.Structure):
+    """cmlpl_optim: the options of a clipped, decayed Adam step"""
+    _fields_ = [("max_norm", C.c_float), ("weight_decay", C.c_float), ("d_norms", C.c_void_p), ("d_partials", C.c_void_p)]
 
 
 class MemobankCall(C.Structure):
@@ -322,6 +329,14 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_debug_loss_plan.argtypes = [SP, C.POINTER(Shard), i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_unsup_plan.argtypes = [i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_memobank_plan.argtypes = [i32, i32, i32, i32, C.POINTER(i32)]
+    OP = C.POINTER(Optim)
+    lib.cmlpl_grad_norm_partials_bytes.argtypes = []
+    lib.cmlpl_grad_norm_partials_bytes.restype = sz
+    lib.cmlpl_grad_norm.argtypes = [SP, i32, vp, i64, f32, vp, vp, vp]
+    lib.cmlpl_adam_step_opt.argtypes = [SP, i32, vp, i64, vp, i64, vp, vp, i64, HP, vp, OP, vp]
+    lib.cmlpl_train_step_opt.argtypes = [SP, HP, C.POINTER(StepIO), OP, vp]
+    lib.cmlpl_step_graph_create_opt.argtypes = [SP, HP, C.POINTER(StepIO), OP, vp, C.POINTER(vp)]
+    lib.cmlpl_dyn_adam_opt.argtypes = [HP, i64, f32, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]
@@ -331,7 +346,8 @@ def load(path: str = LIB_PATH):
         if hasattr(lib, s) and s not in ("cmlpl_workspace_bytes", "cmlpl_loss_workspace_bytes", "cmlpl_ntxent_workspace_bytes",
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
                      "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes",
-                     "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes", "cmlpl_knn_workspace_bytes"):
+                     "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes", "cmlpl_knn_workspace_bytes",
+                     "cmlpl_grad_norm_partials_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

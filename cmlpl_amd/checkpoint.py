@@ -32,12 +32,15 @@ class CheckpointError(RuntimeError):
 
 
 def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_hash: str, abi: int,
-                  method: str = "cmlpl", teacher_alpha: Optional[float] = None, aug_spatial: str = "none") -> Dict[str, Any]:
+                  method: str = "cmlpl", teacher_alpha: Optional[float] = None, aug_spatial: str = "none",
+                  optim=None) -> Dict[str, Any]:
     """the record ``check_identity`` compares: plain dicts and numbers (``NetShape`` / ``HyperParams`` by field).  The
     training ``method`` is part of it; a CMLPL record carries no ``method`` key (what it held before there was a second
     method: such files still load, and a record without the key reads as ``cmlpl``).  ``teacher_alpha``: the coefficient of
     an engine that keeps an EMA teacher -- a key only such an engine's record has (without one the record is what it was).
-    ``aug_spatial``: the flip / rotate augmentation of the cube-fed step, a key only when it is not "none"."""
+    ``aug_spatial``: the flip / rotate augmentation of the cube-fed step, a key only when it is not "none".
+    ``optim`` (``cmlpl_amd.optim.OptimConfig``): ``weight_decay``, ``clip_grad`` and ``lr_schedule`` (the schedule's fields,
+    ``total_steps`` among them), each a key only when it is not the default."""
     from dataclasses import asdict
     rec = dict(shape={k: int(v) for k, v in asdict(shape).items()},
                hp={k: (int(v) if isinstance(v, int) and not isinstance(v, bool) else float(v)) for k, v in asdict(hp).items()},
@@ -48,6 +51,8 @@ def make_identity(shape, hp, bt_global: int, btu_global: int, Q: int, source_has
         rec["teacher_alpha"] = float(teacher_alpha)
     if aug_spatial != "none":
         rec["aug_spatial"] = str(aug_spatial)
+    if optim is not None:
+        rec.update(optim.identity())
     return rec
 
 
@@ -76,6 +81,8 @@ def identity_differences(saved: Dict[str, Any], mine: Dict[str, Any]) -> List[st
     #  without one leaves the file's aside -- two different coefficients are two different averages)
     if "teacher_alpha" in saved and "teacher_alpha" in mine and saved["teacher_alpha"] != mine["teacher_alpha"]:
         out.append(f"teacher_alpha: file {saved['teacher_alpha']!r}, here {mine['teacher_alpha']!r}")
+    from .optim import optim_identity_differences
+    out.extend(optim_identity_differences(saved, mine))
     return out
 
 

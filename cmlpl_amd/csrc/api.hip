@@ -870,9 +870,24 @@ int cmlpl_dyn_adam(const cmlpl_hparams* hp, int64_t adam_t, float* step_size, fl
 
 }  // extern "C"
 namespace {
+// the options of a step: 0, or CMLPL_E_ARG (include/cmlpl.h, cmlpl_optim)
+bool optim_norm_wanted(const cmlpl_optim* opt) { return opt->max_norm > 0.f || opt->d_norms != nullptr; }
+int check_optim(const cmlpl_optim* opt) {
+  if (!(opt->max_norm >= 0.f && opt->max_norm <= 3.0e38f) || !(opt->weight_decay >= 0.f && opt->weight_decay <= 3.0e38f))
+    return CMLPL_E_ARG;                                                   // (a NaN fails both comparisons)
+  if (((uintptr_t)opt->d_norms & 3) || ((uintptr_t)opt->d_partials & 7)) return CMLPL_E_ARG;
+  if (optim_norm_wanted(opt) && opt->d_partials == nullptr) return CMLPL_E_ARG;
+  return 0;
+}
+int grad_norm_launch(const cmlpl_layout_t& L, int nets, const float* d_grads, int64_t grad_stride, void* d_partials,
+                     hipStream_t st) {
+  long long off[CMLPL_NUM_LIVE], numel[CMLPL_NUM_LIVE];
+  for (int t = 0; t < CMLPL_NUM_LIVE; ++t) { off[t] = L.param_off[t]; numel[t] = L.param_numel[t]; }
+  return chk(launch_grad_norm(nets, d_grads, grad_stride, off, numel, (double*)d_partials, st));
+}
 int adam_impl(const cmlpl_shape* shape, int nets, float* d_params, int64_t param_stride,
               const float* d_grads, int64_t grad_stride, float* d_m, float* d_v, int64_t t,
-              const cmlpl_hparams* hp, float* d_packed, void* stream, DynRef dyn) {
+              const cmlpl_hparams* hp, float* d_packed, void* stream, DynRef dyn, const cmlpl_optim* opt = nullptr) {
   cmlpl_layout_t L;
   Dims d;
   int rc = cmlpl_layout(shape, &L);
@@ -880,19 +895,65 @@ int adam_impl(const cmlpl_shape* shape, int nets, float* d_params, int64_t param
   make_dims(shape, &d);
   if (nets < 1 || nets > 2 || !d_params || !d_grads || !d_m || !d_v || !hp || t < 1) return CMLPL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  return TIMED(CMLPL_K_ADAM, chk(launch_adam(nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v,
-                            L.param_live, t, hp->lr, hp->beta1, hp->beta2, hp->eps, d_packed,
-                            make_pack_info(d, L), st, dyn)));
+  if (opt == nullptr)
+    return TIMED(CMLPL_K_ADAM, chk(launch_adam(nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v,
+                              L.param_live, t, hp->lr, hp->beta1, hp->beta2, hp->eps, d_packed,
+                              make_pack_info(d, L), st, dyn)));
+  if ((rc = check_optim(opt))) return rc;
+  AdamOpt o;
+  o.partials = nullptr; o.norms = opt->d_norms; o.max_norm = opt->max_norm; o.keep = adam_keep(hp->lr, opt->weight_decay);
+  if (o.keep == 0.f) return CMLPL_E_ARG;                      // (its bits would read "no decay" in a table row)
+  const bool wanted = optim_norm_wanted(opt);
+  if (wanted) o.partials = (const double*)opt->d_partials;
+  if (grad_stride < L.param_total) return CMLPL_E_ARG;
+  auto both = [&]() -> int {                                  // the partials, then the update that folds them
+    if (wanted)
+      if (int r = grad_norm_launch(L, nets, d_grads, grad_stride, opt->d_partials, st)) return r;
+    return chk(launch_adam(nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v, L.param_live, t, hp->lr,
+                           hp->beta1, hp->beta2, hp->eps, d_packed, make_pack_info(d, L), st, dyn, &o));
+  };
+  return TIMED(CMLPL_K_ADAM, both());
+}
+// the norms row without an update: the partials, then their fold
+int grad_norm_impl(const cmlpl_shape* shape, int nets, const float* d_grads, int64_t grad_stride, float max_norm,
+                   void* d_partials, float* d_norms, void* stream, DynRef dyn) {
+  cmlpl_layout_t L;
+  int rc = cmlpl_layout(shape, &L);
+  if (rc) return rc;
+  if (nets < 1 || nets > 2 || !d_grads || !d_partials || !d_norms || grad_stride < L.param_total ||
+      !(max_norm >= 0.f && max_norm <= 3.0e38f) || ((uintptr_t)d_partials & 7) || ((uintptr_t)d_norms & 3))
+    return CMLPL_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = grad_norm_launch(L, nets, d_grads, grad_stride, d_partials, st))) return rc;
+  return chk(launch_grad_norm_fin(nets, (const double*)d_partials, max_norm, d_norms, st, dyn));
 }
 }  // namespace
 extern "C" {
+int cmlpl_adam_step_opt(const cmlpl_shape* shape, int nets, float* d_params, int64_t param_stride,
+                        const float* d_grads, int64_t grad_stride, float* d_m, float* d_v, int64_t t,
+                        const cmlpl_hparams* hp, float* d_packed, const cmlpl_optim* opt, void* stream) {
+  return adam_impl(shape, nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v, t, hp, d_packed, stream, DynRef(), opt);
+}
 int cmlpl_adam_step(const cmlpl_shape* shape, int nets, float* d_params, int64_t param_stride,
                     const float* d_grads, int64_t grad_stride, float* d_m, float* d_v, int64_t t,
                     const cmlpl_hparams* hp, float* d_packed, void* stream) {
-  return adam_impl(shape, nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v, t, hp, d_packed, stream, DynRef());
+  return cmlpl_adam_step_opt(shape, nets, d_params, param_stride, d_grads, grad_stride, d_m, d_v, t, hp, d_packed, nullptr, stream);
+}
+size_t cmlpl_grad_norm_partials_bytes(void) { return grad_norm_partials_bytes(); }
+int cmlpl_grad_norm(const cmlpl_shape* shape, int nets, const float* d_grads, int64_t grad_stride, float max_norm,
+                    void* d_partials, float* d_norms, void* stream) {
+  return grad_norm_impl(shape, nets, d_grads, grad_stride, max_norm, d_partials, d_norms, stream, DynRef());
+}
+int cmlpl_dyn_adam_opt(const cmlpl_hparams* hp, int64_t adam_t, float weight_decay, float* step_size, float* bc2_sqrt,
+                       float* keep) {
+  if (!keep || !(weight_decay >= 0.f && weight_decay <= 3.0e38f)) return CMLPL_E_ARG;
+  if (int rc = cmlpl_dyn_adam(hp, adam_t, step_size, bc2_sqrt)) return rc;
+  *keep = adam_keep(hp->lr, weight_decay);
+  return *keep == 0.f ? CMLPL_E_ARG : 0;
 }
 
-int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io, void* stream) {
+int cmlpl_train_step_opt(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io,
+                         const cmlpl_optim* opt, void* stream) {
   Dims d;
   cmlpl_layout_t L;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
@@ -900,6 +961,10 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
       !io->d_packed || !io->d_logits || !io->d_feat || !io->d_scalars || !io->d_labels)
     return CMLPL_E_ARG;
   if (io->apply_update && (!io->d_m || !io->d_v)) return CMLPL_E_ARG;
+  if (opt != nullptr) {
+    if (int orc = check_optim(opt)) return orc;
+    if (io->apply_update && adam_keep(hp->lr, opt->weight_decay) == 0.f) return CMLPL_E_ARG;
+  }
   // reserved: bits 0..7 the method, bits 8..9 the spatial augmentation of the cube-fed rows (CMLPL_SYM_*), no other bit
   const int method = io->reserved & 0xff, sym_mode = (io->reserved >> 8) & 3;
   if ((io->reserved & ~0x3ff) != 0 || sym_mode > CMLPL_SYM_D4 ||
@@ -944,15 +1009,20 @@ int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cm
                           io->workspace_bytes, stream, dyn, io->d_dyn_cursor))) return rc;
   if (io->apply_update)   // (device-side scalars: the by-value step count is not used, any valid one will do)
     return adam_impl(shape, 2, io->d_params, L.param_total, io->d_grads, L.param_total, io->d_m, io->d_v,
-                     (dyn.table != nullptr && io->adam_t < 1) ? 1 : io->adam_t, hp, io->d_packed, stream, dyn);
+                     (dyn.table != nullptr && io->adam_t < 1) ? 1 : io->adam_t, hp, io->d_packed, stream, dyn, opt);
+  if (opt != nullptr && opt->d_norms != nullptr)     // no update: the norms of these gradients all the same
+    return grad_norm_impl(shape, 2, io->d_grads, L.param_total, opt->max_norm, opt->d_partials, opt->d_norms, stream, dyn);
   return 0;
+}
+int cmlpl_train_step(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io, void* stream) {
+  return cmlpl_train_step_opt(shape, hp, io, nullptr, stream);
 }
 
 // ---- the step as a replayable hipGraph
 struct StepGraph { hipGraph_t graph; hipGraphExec_t exec; };
 
-int cmlpl_step_graph_create(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io, void* stream,
-                            void** graph_out) {
+int cmlpl_step_graph_create_opt(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io,
+                                const cmlpl_optim* opt, void* stream, void** graph_out) {
   if (!io || !graph_out || !io->d_dyn_table || !io->d_dyn_cursor) return CMLPL_E_ARG;
   if (g_timing.on) return CMLPL_E_ARG;                     // (event pairs are not part of the product's graph)
   hipStream_t st = (hipStream_t)stream;
@@ -960,7 +1030,7 @@ int cmlpl_step_graph_create(const cmlpl_shape* shape, const cmlpl_hparams* hp, c
   if (e != hipSuccess) return (int)e;
   e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return (int)e;
-  const int rc = cmlpl_train_step(shape, hp, io, stream);
+  const int rc = cmlpl_train_step_opt(shape, hp, io, opt, stream);
   hipGraph_t g = nullptr;
   e = hipStreamEndCapture(st, &g);                          // always end the capture, also after a failed launch
   if (rc != 0) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -971,6 +1041,10 @@ int cmlpl_step_graph_create(const cmlpl_shape* shape, const cmlpl_hparams* hp, c
   StepGraph* sg = new StepGraph{g, ex};
   *graph_out = sg;
   return 0;
+}
+int cmlpl_step_graph_create(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io, void* stream,
+                            void** graph_out) {
+  return cmlpl_step_graph_create_opt(shape, hp, io, nullptr, stream, graph_out);
 }
 
 // one stage of the sharded step, every per-step scalar from the device table (see cmlpl_dist_io)

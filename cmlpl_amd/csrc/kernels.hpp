@@ -380,9 +380,18 @@ hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T
                          float* ws, hipStream_t st);
 
 // ---- optim.hip
+// the clipped, decayed step: opt == nullptr is the plain launch (adam_kernel<false>, the code it has always been)
+struct AdamOpt { const double* partials; float* norms; float max_norm, keep; };
 hipError_t launch_adam(int nets, float* params, long long pstride, const float* grads, long long gstride,
                        float* m, float* v, long long live, long long t, float lr, float b1, float b2, float eps,
-                       float* packed, const PackInfo& pi, hipStream_t st, DynRef dyn = DynRef());
+                       float* packed, const PackInfo& pi, hipStream_t st, DynRef dyn = DynRef(),
+                       const AdamOpt* opt = nullptr);
+float adam_keep(float lr, float weight_decay);      // (float)(1 - (double)lr * (double)weight_decay)
+hipError_t launch_grad_norm(int nets, const float* grads, long long gstride, const long long* off, const long long* numel,
+                            double* partials, hipStream_t st);
+hipError_t launch_grad_norm_fin(int nets, const double* partials, float max_norm, float* norms, hipStream_t st,
+                                DynRef dyn = DynRef());
+size_t grad_norm_partials_bytes();
 void adam_bias_scalars(float lr, float b1, float b2, long long t, float* step_size, float* bc2_sqrt);
 
 // ---- ema.hip  (the weight average of reference tools/models.py:155-164: ema = fl(fl(src * oma) + fl(ema * alpha)))

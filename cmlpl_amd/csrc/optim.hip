@@ -16,9 +16,97 @@ struct AdamArgs {
   float* packed; PackInfo pi;
   int nb_elem;                     // blocks of the elementwise part; the 3x3 weight chunks follow
   DynRef dyn;                      // the two bias-correction scalars from device memory (graph replay), or null
+  // the clipped, decayed step (adam_kernel<true> only; include/cmlpl.h, "THE DEFINITION OF A CLIPPED, DECAYED ADAM STEP")
+  const double* partials;          // [nets][NORM_PARTS] of grad_norm_kernel, or null: no coefficient is formed (coef = 1)
+  float* norms;                    // {norm0, norm1, coef0, coef1} (ring base under replay), or null
+  float max_norm, keep;
 };
 
-__device__ __forceinline__ float adam_update(float& mm, float& vv, float p, float g, const AdamArgs& a) {
+// ---- the gradient norm: S_n = sum of (double)g * (double)g over the ten live tensors of network n, in NORM_PARTS fp64
+// partials per network.  The order of every addition is fixed by the launch geometry: a thread walks its elements of
+// tensor 0, 1, .. 9 ascending, a wavefront folds by the xor butterfly, the four wavefronts of a workgroup add up
+// ascending, and whoever needs S_n folds the 64 partials by the same butterfly (norm_fold).  No atomics, no ticket.
+constexpr int NORM_PARTS = 64;
+struct NormArgs {
+  const float* grads; long long gstride;
+  long long off[CMLPL_NUM_LIVE]; int numel[CMLPL_NUM_LIVE];
+  double* partials;
+};
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void grad_norm_kernel(NormArgs a) {
+  __shared__ double red[4];
+  const int net = blockIdx.y, tid = threadIdx.x, gt = (int)blockIdx.x * 256 + tid;
+  const float* g = a.grads + (long long)net * a.gstride;
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < CMLPL_NUM_LIVE; ++t) {
+    const float* gp = g + a.off[t];
+    const int n = a.numel[t];
+#pragma unroll 4
+    for (int i = gt; i < n; i += NORM_PARTS * 256) {
+      const double x = (double)gp[i];
+      acc += x * x;                                  // (the product of two floats is exact in fp64)
+    }
+  }
+  acc = wave_sum_f64(acc);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) a.partials[net * NORM_PARTS + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+// S_n from the partials: every lane of a (whole) wavefront gets the same bits
+__device__ __forceinline__ double norm_fold(const double* partials, int net) {
+  return wave_sum_f64(partials[net * NORM_PARTS + (threadIdx.x & 63)]);
+}
+// torch's clip_grad_norm_: max_norm / (norm + 1e-6) clamped to at most 1; a NaN norm stays a NaN coefficient
+__device__ __forceinline__ float clip_coef(float norm, float max_norm) {
+  if (max_norm == 0.f) return 1.f;
+  const float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+  return c > 1.0f ? 1.0f : c;
+}
+// the norms row of the step whose gradients these are (both launches that write it run behind the cursor's advance)
+__device__ __forceinline__ float* norms_row(float* norms, DynRef dyn) {
+  const cmlpl_dyn* d = dyn_row(dyn, -1);
+  return d != nullptr ? norms + 4 * uni32(d->hist_row) : norms;
+}
+// the norms row without an update behind it (cmlpl_grad_norm; a step with apply_update == 0): one wavefront per network
+__global__ __launch_bounds__(64) void grad_norm_fin_kernel(const double* partials, float max_norm, float* norms, DynRef dyn) {
+  const int net = blockIdx.x;
+  const float norm = (float)sqrt(norm_fold(partials, net));
+  if (threadIdx.x == 0) {
+    float* o = norms_row(norms, dyn);
+    o[net] = norm; o[2 + net] = clip_coef(norm, max_norm);
+  }
+}
+
+// ONE rounded fp32 multiply whose result the compiler may not fuse into what follows (a * b - c would otherwise become
+// one fma, and x * 1.0f would no longer leave the update the bits of the plain one): the product goes through an empty
+// asm, after which the update sees it as it sees a loaded value
+__device__ __forceinline__ float mul_alone(float a, float b) {
+  float r = a * b;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+
+// CHUNK: called from adam_conv_chunk (the elementwise part otherwise) -- it matters to the variant only
+template <bool OPT, bool CHUNK>
+__device__ __forceinline__ float adam_update(float& mm, float& vv, float p, float g, const AdamArgs& a, float coef, float keep) {
+  if (OPT) {
+    g = mul_alone(g, coef);                              // clip_grad_norm_: grad.mul_(coef)
+    p = mul_alone(p, keep);                              // AdamW: param.mul_(1 - lr * weight_decay)
+    // The plain instantiation below leaves the fusing of its products into fmas to the compiler, which has two ways to
+    // fuse v's sum of two products and takes one in the chunk workgroups (the square is fused) and the other in the
+    // elementwise part (the decay of v is fused).  The variant spells out the same fmas, so that coef == keep == 1.0f
+    // leaves the plain step's bits (tests/test_gpu_optim.py holds the two instantiations to each other).
+    mm = fmaf(a.w1, g - mm, mm);
+    vv = CHUNK ? fmaf(g, a.w2 * g, vv * a.b2) : fmaf(vv, a.b2, (a.w2 * g) * g);
+    const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
+    return fmaf(-a.step_size, mm / denom, p);
+  }
+
   mm = mm + a.w1 * (g - mm);                             // exp_avg.lerp_(grad, 1-beta1)
   vv = vv * a.b2 + (a.w2 * g) * g;                       // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
   const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
@@ -32,6 +120,25 @@ __device__ __forceinline__ void adam_dyn(AdamArgs& a) {
     a.bc2_sqrt = __int_as_float(uni32(__float_as_int(d->adam_bc2_sqrt)));
   }
 }
+// the variant's two factors: the decay factor of a replayed step is the bit pattern in its row's `reserved` (all-zero
+// bits: no decay), the clip coefficient comes from the partials; block 0 of each network writes the norms row
+__device__ __forceinline__ void adam_opt_factors(const AdamArgs& a, int net, float* coef, float* keep) {
+  float k = a.keep, c = 1.f;
+  const cmlpl_dyn* d = dyn_row(a.dyn, -1);
+  if (d != nullptr) {
+    const int bits = uni32(d->reserved);
+    k = bits == 0 ? 1.f : __int_as_float(bits);
+  }
+  if (a.partials != nullptr) {
+    const float norm = (float)sqrt(norm_fold(a.partials, net));
+    c = __int_as_float(uni32(__float_as_int(clip_coef(norm, a.max_norm))));
+    if (a.norms != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+      float* o = norms_row(a.norms, a.dyn);
+      o[net] = norm; o[2 + net] = c;
+    }
+  }
+  *coef = c; *keep = k;
+}
 
 // A 3x3 weight tensor in chunks of (four output channels) x (sixteen input channels) = 4 segments of 144 consecutive
 // elements per workgroup, 128 chunks per tensor pair and network: Adam on <= 3 elements per thread, the updated values
@@ -40,7 +147,8 @@ __device__ __forceinline__ void adam_dyn(AdamArgs& a) {
 // pack_weights_kernel.  (Round 3: chunks of 4 x 64 input channels, 32 workgroups per network, each with nine elements
 // per thread and three passes over the packing items, were the long pole of the launch: 10 us.)
 constexpr int ADAM_CHUNKS = 2 * 16 * 4;          // (conv1 | conv2) x output-channel quads x input-channel blocks
-__device__ __forceinline__ void adam_conv_chunk(const AdamArgs& a, int chunk, int net, float* lds) {
+template <bool OPT>
+__device__ __forceinline__ void adam_conv_chunk(const AdamArgs& a, int chunk, int net, float* lds, float coef, float keep) {
   const int which = (chunk >= 64) ? 2 : 0, co0 = ((chunk >> 2) & 15) * 4, ci0 = (chunk & 3) * 16, tid = threadIdx.x;
   const long long off = (which == 0 ? a.pi.off_w1 : a.pi.off_w2) + (long long)co0 * 576 + ci0 * 9;
   float* p = a.params + (long long)net * a.pstride + off;
@@ -61,7 +169,7 @@ __device__ __forceinline__ void adam_conv_chunk(const AdamArgs& a, int chunk, in
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     if (gi[q] < 0) continue;
-    const float pn = adam_update(mq[q], vq[q], pq[q], gq[q], a);
+    const float pn = adam_update<OPT, true>(mq[q], vq[q], pq[q], gq[q], a, coef, keep);
     mm[gi[q]] = mq[q]; vv[gi[q]] = vq[q]; p[gi[q]] = pn;
     lds[tid + 256 * q] = pn;                                          // [4 co][16 ci][9 taps]
   }
@@ -119,11 +227,14 @@ __device__ __forceinline__ void adam_conv_chunk(const AdamArgs& a, int chunk, in
   if (bad) atomicOr((unsigned int*)(pkn + pack_off_h2flag(a.pi.C, a.pi.bands)), 1u);
 }
 
+template <bool OPT>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[768];
   const int net = blockIdx.y;
   adam_dyn(a);
-  if ((int)blockIdx.x >= a.nb_elem) { adam_conv_chunk(a, (int)blockIdx.x - a.nb_elem, net, lds); return; }
+  float coef = 1.f, keep = 1.f;
+  if (OPT) adam_opt_factors(a, net, &coef, &keep);       // (every lane of every wavefront: before any early return)
+  if ((int)blockIdx.x >= a.nb_elem) { adam_conv_chunk<OPT>(a, (int)blockIdx.x - a.nb_elem, net, lds, coef, keep); return; }
   const PackInfo& pi = a.pi;
   float* packed = a.packed;
   const long long i4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -139,7 +250,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
   float ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {sv.x, sv.y, sv.z, sv.w}, pa[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
-  for (int q = 0; q < 4; ++q) pa[q] = adam_update(ma[q], va[q], pa[q], ga[q], a);
+  for (int q = 0; q < 4; ++q) pa[q] = adam_update<OPT, false>(ma[q], va[q], pa[q], ga[q], a, coef, keep);
   *(float4*)mm = make_float4(ma[0], ma[1], ma[2], ma[3]);
   *(float4*)vv = make_float4(va[0], va[1], va[2], va[3]);
   *(float4*)p = make_float4(pa[0], pa[1], pa[2], pa[3]);
@@ -172,7 +283,7 @@ void adam_bias_scalars(float lr, float b1, float b2, long long t, float* step_si
 
 hipError_t launch_adam(int nets, float* params, long long pstride, const float* grads, long long gstride,
                        float* m, float* v, long long live, long long t, float lr, float b1, float b2, float eps,
-                       float* packed, const PackInfo& pi, hipStream_t st, DynRef dyn) {
+                       float* packed, const PackInfo& pi, hipStream_t st, DynRef dyn, const AdamOpt* opt) {
   float step_size, bc2_sqrt;
   adam_bias_scalars(lr, b1, b2, t, &step_size, &bc2_sqrt);
   const long long n4 = (live + 3) / 4;
@@ -183,8 +294,30 @@ hipError_t launch_adam(int nets, float* params, long long pstride, const float* 
   a.bc2_sqrt = bc2_sqrt; a.eps = eps; a.packed = (CMLPL_ABL == 40) ? nullptr : packed; a.pi = pi;   // (40: timing of the update alone)
   a.nb_elem = (int)((n4 + 255) / 256);
   dim3 grid((unsigned)(a.nb_elem + ADAM_CHUNKS), nets);  // + the (4 co x 16 ci) chunks of conv1.weight and conv2.weight
-  hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, a);
+  a.partials = nullptr; a.norms = nullptr; a.max_norm = 0.f; a.keep = 1.f;
+  if (opt != nullptr) {
+    a.partials = opt->partials; a.norms = opt->norms; a.max_norm = opt->max_norm; a.keep = opt->keep;
+    hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, st, a);
+  }
   return hipGetLastError();
 }
+
+float adam_keep(float lr, float weight_decay) { return (float)(1.0 - (double)lr * (double)weight_decay); }
+
+hipError_t launch_grad_norm(int nets, const float* grads, long long gstride, const long long* off, const long long* numel,
+                            double* partials, hipStream_t st) {
+  NormArgs a;
+  a.grads = grads; a.gstride = gstride; a.partials = partials;
+  for (int t = 0; t < CMLPL_NUM_LIVE; ++t) { a.off[t] = off[t]; a.numel[t] = (int)numel[t]; }
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(NORM_PARTS, nets), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_grad_norm_fin(int nets, const double* partials, float max_norm, float* norms, hipStream_t st, DynRef dyn) {
+  hipLaunchKernelGGL(grad_norm_fin_kernel, dim3(nets), dim3(64), 0, st, partials, max_norm, norms, dyn);
+  return hipGetLastError();
+}
+size_t grad_norm_partials_bytes() { return (size_t)2 * NORM_PARTS * sizeof(double); }
 
 }  // namespace cmlpl

@@ -362,7 +362,8 @@ class DistTrainEngine(TrainEngine):
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, comm=None, hist_rows: int = 1,
-                 alias_single: bool = True, method: str = "cmlpl", aug_spatial: str = "none", pl_monitor: bool = False):
+                 alias_single: bool = True, method: str = "cmlpl", aug_spatial: str = "none", pl_monitor: bool = False,
+                 optim=None):
         """``alias_single=False`` keeps the REAL collectives at world size 1 (separate send / receive buffers, four
         torch.distributed calls per step): what scripts/dist_overhead.py measures the host cost of the calls with."""
         if method != "cmlpl":      # before any device or communicator work
@@ -373,6 +374,10 @@ class DistTrainEngine(TrainEngine):
         if pl_monitor:
             raise ValueError("pl_monitor: the sharded step has no pseudo-label monitor (its counters would need an "
                              "all-reduce over the ranks) -- run --pl_stats on one GPU")
+        if optim is not None and optim.active():
+            raise ValueError("optim: the sharded step has no learning-rate schedule, weight decay or gradient clipping (the "
+                             "norm would need an all-reduce of two doubles per network before the update) -- run "
+                             "--lr_schedule / --weight_decay / --clip_grad on one GPU")
         if comm is None:
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized()):

@@ -131,8 +131,10 @@ class TrainEngine:
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
                  hist_rows: int = 1, method: str = "cmlpl", teacher_alpha: Optional[float] = None,
-                 aug_spatial: str = "none", pl_monitor: bool = False):
+                 aug_spatial: str = "none", pl_monitor: bool = False, optim=None):
         self.method = check_method(method)
+        # the options of the update (cmlpl_amd.optim.OptimConfig); a record with everything off is no record
+        self.optim = optim if optim is not None and optim.active() else None
         self.aug_spatial = check_spatial(aug_spatial)
         if teacher_alpha is not None and not 0.0 <= float(teacher_alpha) <= 1.0:       # (a NaN fails both comparisons)
             raise ValueError(f"teacher_alpha {teacher_alpha!r}: a coefficient in [0, 1]")
@@ -194,6 +196,13 @@ class TrainEngine:
         # the pseudo-label monitor: int64 counts[PL_HEAD + 2 K K], added to by one launch behind every step
         self.pl_block = torch.zeros(_lib.PL_HEAD + 2 * shape.K * shape.K, dtype=torch.int64, device=dev) if pl_monitor else None
         self._pl_off = {}           # n -> byte offset of the step's targets inside the workspace (asked of the library)
+        # the clipped, decayed step: a [hist_rows][4] ring of {norm0, norm1, coef0, coef1} beside the scalars' ring and the
+        # fp64 partials of the gradient-norm launch; without options neither exists and the step is the call it was
+        self.norm_hist = self.norm_partials = self._copt = None
+        if self.optim is not None:
+            self.norm_hist = z(self.hist_rows, 4)
+            self.norm_partials = torch.empty(int(self.lib.cmlpl_grad_norm_partials_bytes()) // 8, dtype=torch.float64, device=dev)
+            self._copt = self._make_opt(self.norm_hist.data_ptr())
 
     @property
     def scalars(self) -> torch.Tensor:
@@ -205,6 +214,42 @@ class TrainEngine:
         h = self.hp
         return _lib.HParams(h.lr, h.beta1, h.beta2, h.eps, h.temperature, h.alpha, h.noise, h.dropout,
                             h.w_contrast, h.w_mutual, h.pos_thr, h.neg_thr)
+
+    # ------------------------------------------------------------------ schedule, weight decay, clipping
+    def _make_opt(self, d_norms: int) -> "_lib.Optim":
+        o = self.optim
+        return _lib.Optim(float(o.clip_grad), float(o.weight_decay), d_norms, self.norm_partials.data_ptr())
+
+    def lr_of(self, t: int) -> float:
+        """the learning rate of the 1-based Adam step ``t`` as the kernels take it: the float32 of the schedule's
+        ``lr_at(t)`` (of ``hp.lr`` without a schedule)"""
+        o = self.optim
+        lr = self.hp.lr if o is None or o.schedule is None else o.schedule.lr_at(t)
+        return float(C.c_float(lr).value)
+
+    def _hp_at(self, t: int) -> "_lib.HParams":
+        """the step's hyper-parameter record: ``self._chp``, or a copy carrying the scheduled rate of Adam step ``t``"""
+        if self.optim is None or self.optim.schedule is None:
+            return self._chp
+        hp = _lib.HParams.from_buffer_copy(self._chp)
+        hp.lr = self.lr_of(t)
+        return hp
+
+    def grad_norms(self):
+        """[norm0, norm1, coef0, coef1] of the last step (a synchronising read): each network's gradient norm and the
+        clip coefficient its update used (1 without clipping)"""
+        if self.norm_hist is None:
+            raise RuntimeError("grad_norms(): an engine built with optim=OptimConfig(...) with an option on")
+        return self.norm_hist[self._cur_row].tolist()
+
+    def norm_window(self, k: int):
+        """the norms rows of the last k steps, oldest first, float32 numpy [k][4] (as ``loss_window``; one read-back)"""
+        if self.norm_hist is None:
+            raise RuntimeError("norm_window(): an engine built with optim=OptimConfig(...) with an option on")
+        if k < 1 or k > self.hist_rows or k > self.step_count:
+            raise ValueError(f"window of {k} steps not held (hist_rows={self.hist_rows}, steps={self.step_count})")
+        idx = [(self.step_count - k + j) % self.hist_rows for j in range(k)]
+        return self.norm_hist[torch.tensor(idx, device=self.device)].cpu().numpy()
 
     def tensor_shapes(self) -> "OrderedDict[str, tuple]":
         s = self.shape
@@ -345,7 +390,7 @@ class TrainEngine:
         return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
                              self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method,
                              teacher_alpha=getattr(self, "teacher_alpha", None),
-                             aug_spatial=getattr(self, "aug_spatial", "none"))
+                             aug_spatial=getattr(self, "aug_spatial", "none"), optim=getattr(self, "optim", None))
 
     def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
         """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
@@ -624,8 +669,13 @@ class TrainEngine:
         io.adam_t = self.adam_t + 1
         io.step = self.step_count
         io.apply_update = 1 if apply_update else 0
-        _lib.check("cmlpl_train_step",
-                   self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
+        if self.optim is None:
+            _lib.check("cmlpl_train_step",
+                       self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
+        else:
+            self._copt.d_norms = self.norm_hist.data_ptr() + 16 * self._cur_row
+            _lib.check("cmlpl_train_step_opt", self.lib.cmlpl_train_step_opt(
+                C.byref(self.cshape), C.byref(self._hp_at(self.adam_t + 1)), C.byref(io), C.byref(self._copt), stream))
         if self.teacher is not None and apply_update:
             self._teacher_update(stream)
         self._advance(n, apply_update)
@@ -755,8 +805,14 @@ class StepGraph:
         cap.wait_stream(torch.cuda.current_stream(dev))
         handle = C.c_void_p()
         with torch.cuda.stream(cap):
-            _lib.check("cmlpl_step_graph_create", eng.lib.cmlpl_step_graph_create(
-                C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.c_void_p(cap.cuda_stream), C.byref(handle)))
+            if getattr(eng, "optim", None) is None:
+                _lib.check("cmlpl_step_graph_create", eng.lib.cmlpl_step_graph_create(
+                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.c_void_p(cap.cuda_stream), C.byref(handle)))
+            else:        # the norms ring by its base, as the scalars' ring: the row comes from the table
+                opt = eng._make_opt(eng.norm_hist.data_ptr())
+                _lib.check("cmlpl_step_graph_create_opt", eng.lib.cmlpl_step_graph_create_opt(
+                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.byref(opt), C.c_void_p(cap.cuda_stream),
+                    C.byref(handle)))
         torch.cuda.current_stream(dev).wait_stream(cap)
         self.handle = handle
 
@@ -799,9 +855,20 @@ class StepGraph:
         rows["hist_row"] = (eng.step_count + j) % eng.hist_rows
         a, b = C.c_float(), C.c_float()       # Adam's two scalars: formed by the library, exactly as the eager step does
         ss, bc = np.empty(k, np.float32), np.empty(k, np.float32)
-        for i in range(k):
-            eng.lib.cmlpl_dyn_adam(C.byref(eng._chp), eng.adam_t + 1 + i, C.byref(a), C.byref(b))
-            ss[i], bc[i] = a.value, b.value
+        if getattr(eng, "optim", None) is None:
+            for i in range(k):
+                eng.lib.cmlpl_dyn_adam(C.byref(eng._chp), eng.adam_t + 1 + i, C.byref(a), C.byref(b))
+                ss[i], bc[i] = a.value, b.value
+        else:
+            # the scheduled rate of each row goes through the same float32 as an eager step's hp copy; the decay factor
+            # travels as its bit pattern in the row's `reserved`
+            c, keep = C.c_float(), np.empty(k, np.float32)
+            for i in range(k):
+                t = eng.adam_t + 1 + i
+                _lib.check("cmlpl_dyn_adam_opt", eng.lib.cmlpl_dyn_adam_opt(
+                    C.byref(eng._hp_at(t)), t, float(eng.optim.weight_decay), C.byref(a), C.byref(b), C.byref(c)))
+                ss[i], bc[i], keep[i] = a.value, b.value, c.value
+            rows["reserved"] = keep.view(np.int32)
         rows["adam_step_size"], rows["adam_bc2_sqrt"] = ss, bc
         self.host[:64].copy_(self.host[64:128])            # row 0: the working copy starts as the first step's row
         k = (k + 1) * 64

@@ -197,7 +197,7 @@ typedef struct cmlpl_dyn {
   int32_t hist_row;         /* the step's scalars go to d_scalars + 16 * hist_row                      */
   float adam_step_size;     /* lr / (1 - beta1^adam_t)   } torch.optim.Adam's bias corrections, formed in double  */
   float adam_bc2_sqrt;      /* sqrt(1 - beta2^adam_t)    } on the host: cmlpl_dyn_adam() fills both               */
-  int32_t reserved;
+  int32_t reserved;         /* 0, or the bit pattern of the step's decay factor ("A CLIPPED, DECAYED ADAM STEP")       */
 } cmlpl_dyn;
 /* the two Adam scalars of a table row, exactly as cmlpl_adam_step forms them from (hp, t) */
 int cmlpl_dyn_adam(const cmlpl_hparams* hp, int64_t adam_t, float* step_size, float* bc2_sqrt);
@@ -1152,6 +1152,78 @@ int cmlpl_knn(const float* d_query /* [n][1024] */, int n, const float* d_galler
               int32_t* d_nbr_idx /* [n][k] or NULL */, float* d_nbr_sim /* [n][k] or NULL */,
               float* d_probs /* [n][K] or NULL */, int64_t* d_labels /* [n] or NULL */,
               void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Added after ABI 6, no bump (nothing existing moves; cmlpl_dyn.reserved keeps its name, type and offset and gains a
+ * meaning that every earlier caller's zero spells "off") -- LEARNING-RATE SCHEDULES, DECOUPLED WEIGHT DECAY AND
+ * GRADIENT-NORM CLIPPING.  The reference trains with torch.optim.Adam at one fixed --lr (train.py:131-132); these are
+ * torch.optim.AdamW's decay (Loshchilov & Hutter, "Decoupled Weight Decay Regularization", ICLR 2019) and
+ * torch.nn.utils.clip_grad_norm_, per network, since the reference keeps one optimiser per network.
+ *
+ * THE DEFINITION OF A CLIPPED, DECAYED ADAM STEP.  Network n (0 or 1) has the gradients g of its flat block, d_grads +
+ * n * grad_stride, laid out as the parameters are (cmlpl_layout_t).
+ *   Gradient norm.  S_n = the sum, over the elements of the ten live tensors (tensor by tensor: param_off[t] ..
+ *     param_off[t] + param_numel[t], t < CMLPL_NUM_LIVE), of (double)g * (double)g.  The up4(K) - K pad floats behind
+ *     classifier.bias lie inside param_live and do NOT count; nothing of the dead tensors counts.  The sum is taken in
+ *     fp64 in an order fixed by the launch geometry alone: the same bytes on every run, no floating-point atomics.
+ *     norm_n = (float)sqrt(S_n).
+ *   Clip coefficient.  coef_n = max_norm / (norm_n + 1e-6f) in fp32 (one addition, one correctly rounded division),
+ *     then coef_n = 1.0f where coef_n > 1.0f.  A NaN norm gives a NaN coefficient (the comparison is false), as
+ *     torch's clamp does.  max_norm == 0 means NO clipping: coef_n = 1.0f whatever the norm is.
+ *   Update, per element of the ten live tensors (the pad floats behind classifier.bias go through the same chain, as
+ *     they go through cmlpl_adam_step; their gradients are whatever the caller left there):
+ *       1. g' = g * coef_n                 one fp32 multiply, never fused into what follows
+ *       2. p' = p * keep                   one fp32 multiply, never fused; keep = (float)(1.0 - (double)lr_t *
+ *                                          (double)weight_decay), formed on the HOST in double -- AdamW's
+ *                                          param.mul_(1 - lr * weight_decay).  All ten live tensors, biases included,
+ *                                          as torch.optim.AdamW(Base.parameters()) would; dead tensors never move.
+ *       3. cmlpl_adam_step's update of (p', g'), unchanged: m, v and the new parameter.
+ *     coef_n == 1.0f and keep == 1.0f are exact identities: the step is then cmlpl_adam_step's, bit for bit.
+ *   Side effects.  The packed weight copies and the two-piece range flag follow the new parameters exactly as they
+ *     follow cmlpl_adam_step's.
+ *   Learning rate.  lr_t is hp->lr of the call for a by-value step; for a table-fed (replayed) step it is what formed
+ *     the row's adam_step_size, and keep is the float whose BIT PATTERN the row's `reserved` holds -- all-zero bits
+ *     mean no decay (keep = 1.0f), which is what every caller before this section writes.  A keep of exactly 0.0f
+ *     (lr_t * weight_decay == 1) is refused on the host: its bits would say "off".
+ *   The norms row.  Four floats {norm_0, norm_1, coef_0, coef_1}; a call over one network writes slots 0 and 2 only.
+ *     d_norms follows d_scalars' addressing: the four floats AT the pointer for a by-value step, at d_norms + 4 *
+ *     hist_row of the step's row for a table-fed one.
+ *
+ * cmlpl_optim: the options of a step.  max_norm >= 0 and weight_decay >= 0, both finite.  d_norms is optional (NULL:
+ *   no row is written).  d_partials: cmlpl_grad_norm_partials_bytes() bytes of device memory, 8-byte aligned, required
+ *   when max_norm > 0 or d_norms != NULL; it needs no initialisation and carries nothing from step to step.
+ * cmlpl_grad_norm: the reduction alone, two launches -- grad_norm_kernel (64 workgroups per network, each leaves ONE
+ *   fp64 partial: thread -> wavefront butterfly -> four wavefronts added ascending; no ticket word, no memset) and a
+ *   one-wavefront-per-network launch that folds the 64 partials by the same butterfly and writes the norms row AT
+ *   d_norms.  grad_stride >= param_total is the distance between the networks' blocks.
+ * cmlpl_adam_step_opt: cmlpl_adam_step with options.  opt == NULL IS cmlpl_adam_step (the same launch of the same
+ *   kernel).  Otherwise: grad_norm_kernel when max_norm > 0 or d_norms is given, then ONE launch of the Adam kernel's
+ *   second instantiation (a template parameter, no run-time branch per element), in which every wavefront folds its
+ *   network's 64 L2-resident partials itself and workgroup 0 of each network writes the norms row: one launch more than
+ *   cmlpl_adam_step, none when neither clipping nor the row is asked for.
+ * cmlpl_train_step_opt / cmlpl_step_graph_create_opt: cmlpl_train_step / cmlpl_step_graph_create with options; opt ==
+ *   NULL is the old call.  With io->apply_update == 0 the norms row is still written (cmlpl_grad_norm's two launches
+ *   behind the backward), so gradients and norms of the same step can be read together.
+ * cmlpl_dyn_adam_opt: cmlpl_dyn_adam, and the decay factor of the row (store its bit pattern in cmlpl_dyn.reserved).
+ * CMLPL_E_ARG: a null opt where one is required, a negative / NaN / infinite max_norm or weight_decay, a keep of 0.0f,
+ *   missing or misaligned d_partials, a misaligned d_norms, nets outside 1 .. 2, grad_stride < param_total. */
+typedef struct cmlpl_optim {
+  float max_norm;       /* clip_grad_norm_'s max_norm; 0 = no clipping     */
+  float weight_decay;   /* AdamW's weight_decay; 0 = none                  */
+  float* d_norms;       /* optional: {norm0, norm1, coef0, coef1}          */
+  void* d_partials;     /* cmlpl_grad_norm_partials_bytes() bytes          */
+} cmlpl_optim;
+size_t cmlpl_grad_norm_partials_bytes(void);
+int cmlpl_grad_norm(const cmlpl_shape* shape, int nets, const float* d_grads, int64_t grad_stride, float max_norm,
+                    void* d_partials, float* d_norms, void* stream);
+int cmlpl_adam_step_opt(const cmlpl_shape* shape, int nets, float* d_params, int64_t param_stride,
+                        const float* d_grads, int64_t grad_stride, float* d_m, float* d_v,
+                        int64_t t, const cmlpl_hparams* hp, float* d_packed, const cmlpl_optim* opt, void* stream);
+int cmlpl_train_step_opt(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io,
+                         const cmlpl_optim* opt, void* stream);
+int cmlpl_step_graph_create_opt(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_step_io* io,
+                                const cmlpl_optim* opt, void* stream, void** graph_out);
+int cmlpl_dyn_adam_opt(const cmlpl_hparams* hp, int64_t adam_t, float weight_decay, float* step_size, float* bc2_sqrt,
+                       float* keep);
 
 #ifdef __cplusplus
 }

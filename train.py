@@ -56,6 +56,12 @@ Differences from the reference that are deliberate, MI355X-first choices:
     test split's pixels over the labelled training pixels, untiled.  With ``--eval_every`` two more lines per evaluation
     (``validation_knn`` / ``validation_knn1``) and a curve of its own (``curve_knn`` in ``--save_eval``; in the checkpoints,
     restored by ``--resume``); the same two lines once after the last epoch.  One GPU; ``loss_hist`` is what it is without it.
+  * ``--lr_schedule constant | linear | cosine`` (``--warmup_steps N``, ``--lr_min F``), ``--weight_decay F``, ``--clip_grad F``:
+    a learning-rate schedule over the run's steps (linear warm-up, then the decay; cmlpl_amd.optim.LRSchedule), AdamW's
+    decoupled weight decay, and gradient-norm clipping per network (torch's ``clip_grad_norm_``; one launch more per step,
+    eager or replayed).  With any of them on, one ``optim`` line per epoch -- the last rate, mean and max of each network's
+    gradient norm, how many steps clipped -- and ``--save_optim PATH`` writes [num_steps][5] = lr, norm, norm1, coef, coef1.
+    One GPU.  The defaults are the reference's fixed-rate Adam: no line, no launch, and a checkpoint is what it was.
 ``--synthetic SHAPE`` (B2 | P | B4 | B5) runs without the datasets, which are not shipped.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ...`` shards every batch by
 sample over the ranks (cmlpl_amd.distributed); batch sizes must be multiples of N, and a short last batch
@@ -136,12 +142,41 @@ def run_record(args, hp, shape, from_scene):
 
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
-    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T) is left out at its default, so a file written without it is byte for byte what it
+    its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T, the optimiser flags) is left out at its default, so a file written without it is byte for byte what it
     was before the flag existed"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
             'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
-            'knn': None, 'knn_T': None}
+            'knn': None, 'knn_T': None, **OPTIM_FLAGS}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
+
+
+OPTIM_FLAGS = {'lr_schedule': 'constant', 'warmup_steps': 0, 'lr_min': 0.0, 'weight_decay': 0.0, 'clip_grad': 0.0,
+               'save_optim': None}     # the flags of cmlpl_amd.optim, at their defaults: the reference's fixed-rate Adam
+
+
+def optim_of(args, total_steps):
+    """the run's ``cmlpl_amd.optim.OptimConfig``, or None with every optimiser flag at its default; ``total_steps``: the
+    steps of the WHOLE run (--num_epochs epochs), which a resumed leg shares with the leg that wrote its file"""
+    from cmlpl_amd.optim import LRSchedule, OptimConfig
+    try:
+        schedule = None
+        if args.lr_schedule != 'constant' or args.warmup_steps != 0:
+            schedule = LRSchedule(args.lr_schedule, args.lr, total_steps, warmup_steps=args.warmup_steps, lr_min=args.lr_min)
+        elif args.lr_min != 0.0:
+            raise ValueError("--lr_min belongs to --lr_schedule linear | cosine")
+        cfg = OptimConfig(schedule=schedule, weight_decay=args.weight_decay, clip_grad=args.clip_grad)
+    except ValueError as e:
+        raise SystemExit("optimiser flags: %s" % e)
+    return cfg if cfg.active() else None
+
+
+def optim_line(epoch, num_epochs, rows):
+    """the ``optim`` line of one epoch's rows [steps][5] = lr, norm, norm1, coef, coef1"""
+    parts = ['lr = %.4e' % rows[-1, 0]]
+    for d, tag in enumerate(('', '1')):
+        parts.append('norm%s = %.4f max%s = %.4f clipped%s = %d/%d' %
+                     (tag, rows[:, 1 + d].mean(), tag, rows[:, 1 + d].max(), tag, int((rows[:, 3 + d] < 1.0).sum()), len(rows)))
+    return 'Epoch %d/%d: optim %s' % (epoch, num_epochs, ' '.join(parts))
 
 
 def run_differences(saved, mine):
@@ -481,6 +516,9 @@ def build_engine(run, args, make_engine):
     if world > 1 and (bt % world or btu % world):
         raise SystemExit(f"--labeled_batch_size {bt} / --unlabeled_batch_size {btu} must be multiples of the "
                          f"number of GPUs ({world}): the batch is sharded equally by sample")
+    # the optimiser options: the schedule runs over the steps of the whole run, known from the splits' sizes (train.py:134)
+    run.total_steps = args.num_epochs * min(-(-len(run.labeled) // bt), -(-len(run.unlabeled) // btu))
+    run.optim = optim_of(args, run.total_steps)
     if make_engine is not None:
         run.eng = make_engine(NetShape(*run.shape), bt // world, btu // world, hp, ppb)
     elif world > 1:
@@ -491,8 +529,9 @@ def build_engine(run, args, make_engine):
         from cmlpl_amd import TrainEngine
         spatial = {} if args.aug_spatial == "none" else dict(aug_spatial=args.aug_spatial)
         monitor = dict(pl_monitor=True) if args.pl_stats else {}
+        optim = dict(optim=run.optim) if run.optim is not None else {}
         run.eng = TrainEngine(NetShape(*run.shape), bt, btu, hp, device=device, seed=1088, hist_rows=ppb, method=args.method,
-                              teacher_alpha=args.teacher_alpha if args.ema else None, **spatial, **monitor)
+                              teacher_alpha=args.teacher_alpha if args.ema else None, **spatial, **monitor, **optim)
     run.eng.init_params_default(1088)
 
 
@@ -535,6 +574,9 @@ def build_loaders(run, args):
     run.lab_loader, run.unl_loader = DeviceLoader(lab_arrays, run.bt, run.gen), DeviceLoader(unl_arrays, run.btu, run.gen)
     run.num_batches = min(len(run.lab_loader), len(run.unl_loader))  # train.py:134
     run.loss_hist = np.zeros((args.num_epochs * run.num_batches, 5))  # train.py:135-136
+    if run.optim is not None:         # one row per step: lr, norm, norm1, coef, coef1 (--save_optim, the optim line)
+        assert run.total_steps == args.num_epochs * run.num_batches
+        run.optim_hist = np.zeros((run.total_steps, 5), np.float32)
 
 
 def build_evaluator(run, args):
@@ -598,6 +640,8 @@ def restore_progress(run, args):
         run.curves['_knn'].restore(ex)
     if args.pl_stats and "pl_curve" in ex:      # (a leg without --pl_stats leaves a gap in the curve, not an error)
         run.pl_curve = list(ex["pl_curve"].numpy())
+    if run.optim is not None and "optim_hist" in ex:     # (a leg without --save_optim leaves its rows zero, not an error)
+        run.optim_hist[:run.start_epoch * run.num_batches] = ex["optim_hist"].numpy()
     if run.curves[''].epochs:          # --save_best: network 0's best validation so far
         run.best_oa = max(row[0][0] for row in run.curves[''].rows)
 
@@ -614,6 +658,8 @@ def run_extra(run, args, epochs_done):
     if args.pl_stats:                 # the monitor's counter block of every epoch so far, int64 [epochs][32 + 2 K K]
         size = 32 + 2 * run.shape[4] ** 2
         extra["pl_curve"] = torch.from_numpy(np.stack(run.pl_curve)) if run.pl_curve else torch.zeros(0, size, dtype=torch.int64)
+    if args.save_optim and run.optim is not None:        # the per-step block so far: only a run that asks for it keeps it
+        extra["optim_hist"] = torch.from_numpy(run.optim_hist[:epochs_done * run.num_batches].copy())
     return extra
 
 
@@ -677,6 +723,8 @@ def train_epochs(run, args):
     def read_back():
         if pending:
             loss_hist[pending] = eng.loss_window(len(pending))
+            if run.optim is not None:
+                run.optim_hist[pending, 1:] = eng.norm_window(len(pending))
             pending.clear()
     by_index = getattr(eng, "takes_indices", False)
     truth_kw = dict(unl_truth=unl_loader.Y) if args.pl_stats else {}      # --pl_stats: the unlabelled split's labels
@@ -693,6 +741,8 @@ def train_epochs(run, args):
             graph.program(replays(run, epoch, batches))
         for batch_index, ((lo, ls), (uo, us)) in enumerate(batches):
             index_i += 1                                             # train.py:150
+            if run.optim is not None: # the rate this step's update takes, as the kernels take it (float32)
+                run.optim_hist[index_i, 0] = eng.lr_of(eng.adam_t + 1)
             bl, bul, r = ls, us, 0
             if world > 1:                                            # shard by sample; decided on GLOBAL sizes
                 plan = shard_plan(ls, us, world)
@@ -730,6 +780,8 @@ def train_epochs(run, args):
                                             np.mean(w[:, 0]), np.mean(w[:, 1]), np.mean(w[:, 2]), np.mean(w[:, 3]),
                                             np.mean(w[:, 4]) * 100))
         read_back()                   # rows of the epoch's tail (num_batches % print_per_batches steps)
+        if run.optim is not None:
+            print(optim_line(epoch + 1, args.num_epochs, run.optim_hist[epoch * num_batches:(epoch + 1) * num_batches]))
         if args.pl_stats:             # the epoch's counters: read, zeroed for the next epoch, one line
             counts = eng.pl_counts()
             eng.pl_reset()
@@ -758,6 +810,8 @@ def report(run, args):
     eng, device, curves, base = run.eng, run.device, run.curves, run.curves['']
     if args.save_loss_hist:
         np.save(args.save_loss_hist, run.loss_hist)
+    if args.save_optim:
+        np.save(args.save_optim, run.optim_hist)
     if args.save_pl:
         np.save(args.save_pl, np.stack(run.pl_curve) if run.pl_curve else np.zeros((0, 32 + 2 * run.shape[4] ** 2), np.int64))
     if run.best_state is not None:
@@ -830,6 +884,12 @@ def main(args, make_engine=None, device=None):
         raise SystemExit(f"--pl_stats runs on one GPU: the sharded engine has no pseudo-label monitor (this job has {world} ranks)")
     if args.save_pl and not args.pl_stats:
         raise SystemExit("--save_pl belongs to --pl_stats")
+    optim_on = [k for k, v in OPTIM_FLAGS.items() if k != 'save_optim' and getattr(args, k) != v]
+    if optim_on and world > 1:
+        raise SystemExit("--%s runs on one GPU: the sharded step has no schedule, weight decay or clipping (this job has %d "
+                         "ranks)" % (optim_on[0], world))
+    if args.save_optim and not optim_on:
+        raise SystemExit("--save_optim belongs to --lr_schedule / --warmup_steps / --weight_decay / --clip_grad")
     check_reliability_args(args, smooth)
     if args.knn is not None and world > 1:
         raise SystemExit(f"--knn runs on one GPU (this job has {world} ranks)")
@@ -849,7 +909,7 @@ def main(args, make_engine=None, device=None):
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
                              evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth,
-                             pl_curve=[], knn=None)
+                             pl_curve=[], knn=None, optim=None, optim_hist=None, total_steps=0)
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -938,6 +998,17 @@ def build_parser():
                              "Reliability<tag>: line -- ECE, MCE, NLL, Brier score, mean confidence and accuracy of the block's class "
                              "probabilities over the labelled test pixels, counted on the device (cmlpl_amd.calibrate; needs "
                              "--ensemble, --tta or --smooth).  The run itself is untouched")
+    parser.add_argument('--lr_schedule', choices=('constant', 'linear', 'cosine'), default='constant',
+                        help="the learning rate over the run's steps: --lr throughout ('constant', the reference), or a linear / "
+                             "cosine decay from --lr towards --lr_min behind --warmup_steps steps of linear warm-up (one GPU)")
+    parser.add_argument('--warmup_steps', type=int, default=0, metavar='N', help='steps of linear warm-up from --lr / N to --lr')
+    parser.add_argument('--lr_min', type=float, default=0.0, metavar='F', help='--lr_schedule linear | cosine: where the decay ends')
+    parser.add_argument('--weight_decay', type=float, default=0.0, metavar='F',
+                        help="AdamW's decoupled weight decay of every live tensor, biases included (0: none, the reference)")
+    parser.add_argument('--clip_grad', type=float, default=0.0, metavar='F',
+                        help="clip each network's gradient norm to F before the update (torch's clip_grad_norm_; 0: no clipping)")
+    parser.add_argument('--save_optim', default=None, metavar='PATH',
+                        help='with an optimiser flag on: write [num_steps][5] = lr, norm, norm1, coef, coef1 of every step as .npy')
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')

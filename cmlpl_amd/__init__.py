@@ -10,6 +10,7 @@ Public surface:
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
   Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
   embed, KnnEvaluator, KnnResult, knn_host (cmlpl_amd.knn.knn: the vote itself) ... kNN evaluation of the spectral embedding
+  LabelProp, label_propagation, knn_graph, build_graph, propagate, labelprop_host ... label propagation over its kNN graph
   LRSchedule, OptimConfig, grad_norm_host, clip_coef_host, adamw_host ... TrainEngine(optim=): schedule, weight decay, clipping
 The compute runs in libcmlpl_hip.so (hand-written gfx950 kernels, C ABI in include/cmlpl.h);
 importing the package does not load it, using any op does -- and fails loudly if it is missing.
@@ -43,6 +44,10 @@ def __getattr__(name):
     if name in ("embed", "KnnEvaluator", "KnnResult", "knn_host", "vote_host"):
         from . import knn
         return getattr(knn, name)
+    if name in ("LabelProp", "LPGraph", "LPResult", "label_propagation", "knn_graph", "build_graph", "one_hot_seeds", "propagate",
+                "labelprop_host"):
+        from . import labelprop
+        return getattr(labelprop, name)
     if name in ("LRSchedule", "OptimConfig", "grad_norm_host", "clip_coef_host", "adamw_host"):
         from . import optim
         return getattr(optim, name)

@@ -1225,6 +1225,75 @@ int cmlpl_step_graph_create_opt(const cmlpl_shape* shape, const cmlpl_hparams* h
 int cmlpl_dyn_adam_opt(const cmlpl_hparams* hp, int64_t adam_t, float weight_decay, float* step_size, float* bc2_sqrt,
                        float* keep);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- LABEL PROPAGATION OVER THE EMBEDDING'S kNN GRAPH: the transductive
+ * "label spreading" of Zhou et al. ("Learning with Local and Global Consistency", NIPS 2003), as Iscen et al. use it on
+ * deep embeddings ("Label Propagation for Deep Semi-supervised Learning", CVPR 2019), over the neighbour lists cmlpl_knn
+ * writes.  The reference has no counterpart.
+ *
+ * THE DEFINITION OF A PROPAGATED LABELLING.
+ *   Inputs.  n nodes; neighbour lists nbr_idx [n][k] int32 and nbr_sim [n][k] float exactly as cmlpl_knn writes them
+ *     (pads are idx = -1), 1 <= k <= 32; an integer exponent gamma in 1 .. 8; a dense non-negative Y [n][K] float,
+ *     1 <= K <= 64 (one-hot rows for seeds and zero rows elsewhere is the usual case; any non-negative matrix is allowed,
+ *     e.g. a classifier's probabilities); 0 <= alpha < 1; iters in 1 .. 10,000; an optional start F0 [n][K], NULL = Y.
+ *   Edges.  Entry (i, r) with j = idx[i][r], 0 <= j < n, j != i is a FORWARD edge i -> j of weight a = s^gamma, formed by
+ *     repeated fp32 multiplication (a = s; gamma - 1 times a = a * s), when 0 < s <= FLT_MAX, else a = 0: NaN, -inf and
+ *     negative similarities give weight 0, and an edge of weight 0 STAYS an edge.  Pads and self entries are no edges.
+ *     Indices >= n are followed without a check.
+ *   Symmetrisation.  W = A + A^T.  Node i's EDGE LIST is its forward edges, r ascending, followed by its REVERSE edges
+ *     -- every (j, r) with idx[j][r] == i -- ordered by j ascending (and r ascending within one j).  A mutual pair simply
+ *     appears in both parts: its weight counts twice, nothing is de-duplicated.
+ *   Degree and coefficients.  d_i = the fp32 sum of the list's weights in that order (one chain from 0).  c_i = 1 /
+ *     sqrtf(d_i) when d_i > 0, else 0.  The coefficient of an edge of node i to j is (c_i * a) * c_j, two fp32
+ *     multiplications in that order: Zhou's S = D^-1/2 W D^-1/2.
+ *   Iteration.  F_{t+1}[i][c] = alpha * SUM_e coef_e * F_t[j_e][c] + beta * Y[i][c]; the sum runs over the node's list
+ *     in list order in fp32, acc = fma(coef_e, F_t[j_e][c], acc) from 0, and the result is fma(alpha, acc, fl32(beta *
+ *     Y[i][c])).  beta = (float)(1 - (double)alpha) is formed on the host.  With alpha = 0 the result is Y's bytes after
+ *     any number of iterations (finite F).
+ *   Finish.  z = SUM_c F[i][c], c ascending.  When z > 0: p = F / z, label = the FIRST maximum of p, confidence =
+ *     p[label], entropy = -SUM_c p log p, c ascending, the terms at p = 0 left out.  When z is not > 0 (an unreached node,
+ *     or NaN): label -1 and NaN p / confidence / entropy -- cmlpl_knn's rule for a query without candidates.
+ *   Residual.  max |F_T - F_{T-1}| over all entries of the last iteration: a float obtained with an INTEGER max on the bit
+ *     patterns of non-negative floats (a NaN difference gives a NaN).  No float atomics.
+ *   Determinism.  The same bytes on every run, every byte of the graph workspace included.  Splitting iters into legs
+ *     changes no byte: 10 iterations, then 10 more from the result passed as F0, are the bytes of 20.
+ *
+ * THE GRAPH WORKSPACE: cmlpl_lp_graph_bytes(n, k) = 4 (3 n + 1 + 5 n k) bytes, arrays of 4-byte words one behind the
+ *   other with no padding, N = n k:
+ *       cinv      float [n]        c_i                                              word 0
+ *       fwd_coef  float [n][k]     the coefficient of entry (i, r); 0 for a pad / self entry    n
+ *       rev_ptr   int32 [n + 1]    node i's reverse edges are slots rev_ptr[i] .. rev_ptr[i + 1] - 1;  n + N
+ *                                  rev_ptr[n] = E, the number of edges
+ *       rev_src   int32 [N]        the source node of each reverse edge; -1 in slots >= E       2 n + 1 + N
+ *       rev_coef  float [N]        its coefficient (c_i * a) * c_src; 0 in slots >= E           2 n + 1 + 2 N
+ *       fwd_dst   int32 [n][k]     idx[i][r] of a forward edge, -1 for a pad / self entry       2 n + 1 + 3 N
+ *       rev_edge  int32 [N]        the entry j k + r a reverse edge came from; -1 past E        2 n + 1 + 4 N
+ *       in_deg    int32 [n]        rev_ptr[i + 1] - rev_ptr[i]                                  2 n + 1 + 5 N
+ *   The propagation reads the workspace alone (the lists may be freed).
+ *
+ * cmlpl_lp_graph: builds it.  Six stream operations: a memset of in_deg, the in-degree count (one integer atomic per
+ *   edge), an exclusive scan by one workgroup, the fill (the same atomic hands out slots: the order inside a segment is
+ *   the run's), the per-node pass that REMOVES that order -- a segment of up to 2,048 edges is sorted in LDS by counting
+ *   (edge ids are unique), a longer one (a hub: in-degree has no bound) is re-found in ascending order by a compaction
+ *   scan over all N entries -- and adds the node's degree as one chain, and the coefficients.  rev_ptr / rev_src are
+ *   identical on every run.  CMLPL_E_ARG: a null or misaligned (4 bytes) pointer, n < 1, k outside 1 .. 32, n k >= 2^31,
+ *   gamma outside 1 .. 8; CMLPL_E_WORKSPACE: bytes < cmlpl_lp_graph_bytes(n, k) (which is 0 for n, k outside the ranges).
+ * cmlpl_lp_propagate: `iters` launches, ping-pong between d_F and d_tmp ([n][K] each; the final F always ends in d_F;
+ *   d_tmp holds F_{T-1} or garbage), then one finishing launch unless all of d_probs [n][K], d_labels [n] int64, d_conf
+ *   [n], d_entropy [n] are NULL; d_residual (one float) is cleared by a memset node first when given.  A group of G =
+ *   2^ceil(log2 K) lanes per node, one class per lane; the group reads indices and coefficients once, G at a time, and a
+ *   neighbour's F row as one contiguous segment.  One group walks one list whatever its length.  d_Y is only read.
+ *   CMLPL_E_ARG: a null d_graph / d_Y / d_F / d_tmp, a range above, n K >= 2^31, alpha outside [0, 1) (NaN too), two of
+ *   d_F / d_tmp / d_Y / d_F0 the same pointer, a misaligned pointer.
+ * All before any launch; nothing synchronises or allocates. */
+size_t cmlpl_lp_graph_bytes(int n, int k);
+int cmlpl_lp_graph(const int32_t* d_nbr_idx /* [n][k] */, const float* d_nbr_sim /* [n][k] */, int n, int k, int gamma,
+                   void* d_graph, size_t bytes, void* stream);
+int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float* d_Y /* [n][K] */, int K, float alpha, int iters,
+                       const float* d_F0 /* [n][K] or NULL */, float* d_F /* [n][K] */, float* d_tmp /* [n][K] */,
+                       float* d_probs /* [n][K] or NULL */, int64_t* d_labels /* [n] or NULL */,
+                       float* d_conf /* [n] or NULL */, float* d_entropy /* [n] or NULL */,
+                       float* d_residual /* [1] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

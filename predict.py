@@ -38,7 +38,12 @@ instead of the classifier: the weighted kNN vote (cmlpl_amd.knn: K neighbours by
 the training pixels (``--knn_gallery train``) or leave-one-out among themselves (``loo``): one ``Result:`` block per network of
 ``--net 0 | 1 | both | ema0 | ema1 | ema_both`` with the tag ``_knn``, ``--reliability`` prints its line behind it (the vote's
 probabilities are a probability map over the test list), ``--embed FILE`` writes the float32 [n_test][1024] embedding of a
-single network.  No label map is written: the vote is over the test list, not the scene."""
+single network.  No label map is written: the vote is over the test list, not the scene.  ``--propagate`` (``--lp_k`` / ``--lp_alpha`` /
+``--lp_gamma`` / ``--lp_iters``; defaults 10, 0.99, 3, 50, not tuned) is the transductive second opinion on the same embedding: label
+propagation over its kNN graph (cmlpl_amd.labelprop) -- the nodes are the labelled training pixels, which are the seeds (the
+gallery of ``--knn_gallery train``), followed by the labelled test pixels.  Per network of ``--net`` one line ``propagate<tag>: nodes=..
+edges=.. max_in_degree=.. unreached=.. residual=..`` and a ``Result:`` block with the tag ``_lp`` scored on the test pixels (one the seeds
+do not reach counts as wrong); ``--reliability`` prints its line behind it.  With ``--knn`` both appear: ``_knn`` first, then ``_lp``."""
 import argparse
 import os
 
@@ -47,8 +52,9 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SPATIAL_MODES, SYNTH, RelScore, add_smooth_flags, calibration_split,
-                   ensemble_whole, evaluate_whole, smooth_of, smooth_whole, temper_stage, tta_tag, tta_whole)
+from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SPATIAL_MODES, SYNTH, RelScore, add_propagate_flags, add_smooth_flags,
+                   calibration_split, ensemble_whole, evaluate_whole, propagate_nodes, propagate_of, smooth_of, smooth_whole,
+                   temper_stage, tta_tag, tta_whole)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
@@ -126,7 +132,63 @@ def check_knn_args(args):
                          "--entropy, --tta, --smooth or --temperature")
 
 
-def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members):
+def check_propagate_args(args):
+    """what --propagate cannot mean (the refusals of --knn)"""
+    if propagate_of(args) is None:
+        return
+    if args.net in ENSEMBLES:
+        raise SystemExit("--propagate scores the embedding of ONE network at a time: --net %s averages class probabilities "
+                         "(name a network, or both / ema_both)" % args.net)
+    if args.out or args.proba or args.confidence or args.entropy or args.tta is not None or smooth_of(args) is not None \
+            or temperature_of(args) is not None:
+        raise SystemExit("--propagate describes the labelled test pixels, not the scene: not with --out, --proba, --confidence, "
+                         "--entropy, --tta, --smooth or --temperature")
+
+
+def training_pixels(args, ck, shape, whole, on):
+    """(spectra, labels) of the labelled training pixels on the device: the gallery of --knn_gallery train, the seeds of
+    --propagate"""
+    if args.synthetic:          # the labelled split train.py --synthetic drew (its flags are in the checkpoint)
+        from hsi_loader import SyntheticHSIDataSet
+        saved = ck["extra"].get("args", {})
+        scene = whole if (saved.get("windows") == "cube" or saved.get("synthetic_scene")) else None
+        lab = SyntheticHSIDataSet(shape, saved.get("num_unlabel", 10000), 'label', seed=1, scene=scene)
+    else:
+        lab = HSIDataSet(int(args.dataID), 'label')
+    return on(lab.X, torch.float32), on(lab.Y, torch.int64)
+
+
+def propagate_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=None):
+    """--propagate: label propagation over the kNN graph of the embedding of the training and test pixels, per network of --net"""
+    from cmlpl_amd.labelprop import propagate_embedding, score_labels
+    from train import build_nets
+    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
+    rows = np.asarray(test_array, np.int64)
+    Xt = whole.X[rows] if torch.is_tensor(whole.X) else np.asarray(whole.X[rows])
+    spectra, seeds = propagate_nodes(*training_pixels(args, ck, shape, whole, on), Xt, device)
+    first, truth = len(seeds) - len(rows), np.asarray(Y_test, np.int64)
+    cfg = propagate_of(args)
+    models = build_nets(shape, members, device, hp["dropout"])
+    out = None
+    for key, model in zip(which, models):
+        model.eval()
+        with torch.no_grad():
+            graph, res = propagate_embedding(model, spectra, seeds, shape[4], cfg, residual=True)[0]
+        labels = res.labels[first:].cpu().numpy()
+        tag = '_lp' + NET_TAGS[key]
+        print('propagate%s: nodes=%d edges=%d max_in_degree=%d unreached=%d residual=%.3e' %
+              (NET_TAGS[key], len(seeds), graph.edges(), graph.max_in_degree(), int((labels < 0).sum()), float(res.residual.cpu()[0])))
+        OA, Kappa, producerA, AA, _ = score_labels(labels, truth, shape[4])
+        print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
+        print('producerA%s:' % tag, producerA * 100)
+        print('AA%s=%.2f' % (tag, AA * 100))
+        if score is not None:
+            score(tag, res._replace(probs=res.probs[first:].clone()))      # (a buffer of its own: the test rows' block)
+        out = labels if out is None else out
+    return out
+
+
+def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=None):
     """--knn / --embed: the embedding of the labelled test pixels under the networks of --net, and its kNN vote"""
     from cmlpl_amd import NetShape
     from cmlpl_amd.knn import KnnEvaluator, embed
@@ -145,19 +207,10 @@ def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, memb
     loo = args.knn_gallery == 'loo'
     if loo:
         gallery = (Xt, Yt)
-    elif args.synthetic:          # the labelled split train.py --synthetic drew (its flags are in the checkpoint)
-        from hsi_loader import SyntheticHSIDataSet
-        saved = ck["extra"].get("args", {})
-        scene = whole if (saved.get("windows") == "cube" or saved.get("synthetic_scene")) else None
-        lab = SyntheticHSIDataSet(shape, saved.get("num_unlabel", 10000), 'label', seed=1, scene=scene)
-        gallery = (on(lab.X, torch.float32), on(lab.Y, torch.int64))
     else:
-        lab = HSIDataSet(int(args.dataID), 'label')
-        gallery = (on(lab.X, torch.float32), on(lab.Y, torch.int64))
+        gallery = training_pixels(args, ck, shape, whole, on)
     T = hp.get("temperature", 0.3) if args.knn_T is None else args.knn_T
     ev = KnnEvaluator(NetShape(*shape), *gallery, *((None, None) if loo else (Xt, Yt)), k=args.knn, T=T, loo=loo)
-    score = RelScore(np.arange(len(rows)), Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins) \
-        if args.reliability else None
     first = None
     for key, model in zip(which, models):
         ev.evaluate(model)
@@ -167,14 +220,13 @@ def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, memb
         if score is not None:
             score(tag, ev.last._replace(probs=ev.last.probs[0]))
         first = labels if first is None else first
-    if args.save_reliability:
-        score.save(args.save_reliability)
     return first
 
 
 def main(args, device=None):
     check_args(args)
     check_knn_args(args)
+    check_propagate_args(args)
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -209,10 +261,21 @@ def main(args, device=None):
     extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
     common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
     members = [(k, ck[keys[k]]) for k in which]
-    if args.knn is not None or args.embed:
+    propagate = getattr(args, 'propagate', False)
+    if args.knn is not None or args.embed or propagate:
         if test_array is None:
-            raise SystemExit("--knn / --embed need the labelled test pixels (test_array.npy and Y.npy in the dataset directory)")
-        return knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members)
+            raise SystemExit("--knn / --embed / --propagate need the labelled test pixels (test_array.npy and Y.npy in the dataset "
+                             "directory)")
+        # (the blocks are over the test LIST: position i of a probability map is test pixel i)
+        score = RelScore(np.arange(len(test_array)), Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins) \
+            if args.reliability else None
+        out, todo = None, [knn_main] * (args.knn is not None or bool(args.embed)) + [propagate_main] * bool(propagate)
+        for stage in todo:                  # _knn first, then _lp
+            labels = stage(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=score)
+            out = labels if out is None else out
+        if args.save_reliability and (args.knn is not None or propagate):
+            score.save(args.save_reliability)
+        return out
     smooth, tta = smooth_of(args), None
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
@@ -325,6 +388,8 @@ def build_parser():
                              "test pixels (loo)")
     parser.add_argument('--embed', default=None, metavar='FILE',
                         help='write the float32 [n_test][1024] embedding of the labelled test pixels under a single network as .npy')
+    add_propagate_flags(parser, 'one propagate line and one Result: block per network of --net with the tag _lp (not with the '
+                                'ensembles)')
     parser.add_argument('--val_batch_size', type=int, default=512,
                         help='batch of the loader fall-back (a dataset directory without cube.npy)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,

@@ -56,6 +56,11 @@ Differences from the reference that are deliberate, MI355X-first choices:
     test split's pixels over the labelled training pixels, untiled.  With ``--eval_every`` two more lines per evaluation
     (``validation_knn`` / ``validation_knn1``) and a curve of its own (``curve_knn`` in ``--save_eval``; in the checkpoints,
     restored by ``--resume``); the same two lines once after the last epoch.  One GPU; ``loss_hist`` is what it is without it.
+  * ``--propagate`` (``--lp_k K``, ``--lp_alpha A``, ``--lp_gamma G``, ``--lp_iters N``; defaults 10, 0.99, 3, 50, not tuned): a
+    second opinion on the classifier that costs no training -- label propagation over the embedding's kNN graph
+    (cmlpl_amd.labelprop: the labelled training pixels are the seeds, the test split's pixels the other nodes), once after
+    the last epoch: two lines ``validation_lp`` / ``validation_lp1`` in the format of ``validation_knn``.  One GPU; ``loss_hist``,
+    the curves, the checkpoints (the flag is not recorded in them) and every other line are what they are without it.
   * ``--lr_schedule constant | linear | cosine`` (``--warmup_steps N``, ``--lr_min F``), ``--weight_decay F``, ``--clip_grad F``:
     a learning-rate schedule over the run's steps (linear warm-up, then the decay; cmlpl_amd.optim.LRSchedule), AdamW's
     decoupled weight decay, and gradient-norm clipping per network (torch's ``clip_grad_norm_``; one launch more per step,
@@ -143,11 +148,52 @@ def run_record(args, hp, shape, from_scene):
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
     its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T, the optimiser flags) is left out at its default, so a file written without it is byte for byte what it
-    was before the flag existed"""
+    was before the flag existed; --propagate and its sub-flags only add lines behind the run and are never recorded"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
             'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
             'knn': None, 'knn_T': None, **OPTIM_FLAGS}
-    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k])}
+    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS}
+
+
+LP_FLAGS = ('propagate', 'lp_k', 'lp_alpha', 'lp_gamma', 'lp_iters')     # --propagate: cmlpl_amd.labelprop.LabelProp's fields
+
+
+def add_propagate_flags(parser, what):
+    """``--propagate`` and its sub-flags (train.py and predict.py); every sub-flag's default is None: the flag was not given"""
+    parser.add_argument('--propagate', action='store_true',
+                        help='label propagation over the kNN graph of the spectral embedding (cmlpl_amd.labelprop): the labelled '
+                             'training pixels are the seeds, the labelled test pixels the other nodes; %s (one GPU)' % what)
+    parser.add_argument('--lp_k', type=int, default=None, metavar='K', help='--propagate: neighbours per node (default 10, 1 .. 32)')
+    parser.add_argument('--lp_alpha', type=float, default=None, metavar='A',
+                        help='--propagate: the share a node takes from its neighbours per iteration (default 0.99, 0 <= A < 1)')
+    parser.add_argument('--lp_gamma', type=int, default=None, metavar='G',
+                        help='--propagate: an edge weighs similarity^G (default 3, 1 .. 8)')
+    parser.add_argument('--lp_iters', type=int, default=None, metavar='N', help='--propagate: iterations (default 50, 1 .. 10000)')
+
+
+def propagate_of(args):
+    """the ``cmlpl_amd.labelprop.LabelProp`` of the command line, or None without ``--propagate``; what it cannot mean is a
+    SystemExit before anything is loaded"""
+    given = [k for k in LP_FLAGS[1:] if getattr(args, k, None) is not None]
+    if not getattr(args, 'propagate', False):
+        if given:
+            raise SystemExit("%s belong%s to --propagate" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
+        return None
+    from cmlpl_amd.labelprop import LabelProp
+    cfg = LabelProp(**{k[3:]: getattr(args, k) for k in given})
+    try:
+        return cfg.check()
+    except ValueError as e:
+        raise SystemExit("--propagate: --lp_%s" % e)
+
+
+def propagate_nodes(seeds_X, seeds_Y, test_X, device):
+    """the nodes of --propagate: (spectra float32 [n, bands], seed labels int64 [n], -1 for a test pixel) -- the labelled
+    training pixels followed by the labelled test pixels"""
+    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
+    seeds_X, seeds_Y, test_X = on(seeds_X, torch.float32), on(seeds_Y, torch.int64), on(test_X, torch.float32)
+    return (torch.cat([seeds_X, test_X]).contiguous(),
+            torch.cat([seeds_Y, torch.full((test_X.shape[0],), -1, dtype=torch.int64, device=device)]))
 
 
 OPTIM_FLAGS = {'lr_schedule': 'constant', 'warmup_steps': 0, 'lr_min': 0.0, 'weight_decay': 0.0, 'clip_grad': 0.0,
@@ -491,7 +537,7 @@ def load_data(run, args):
         run.shape = shape = SYNTH[args.synthetic]
         # (--windows cube / --synthetic_scene: both splits are seeded pixels of ONE synthetic scene, the evaluation's)
         run.from_scene = args.windows == 'cube' or args.synthetic_scene
-        if run.from_scene or not args.no_eval or args.eval_every > 0 or args.knn is not None:
+        if run.from_scene or not args.no_eval or args.eval_every > 0 or args.knn is not None or getattr(args, 'propagate', False):
             run.whole = SyntheticScene(shape, 64, 64, seed=3)       # a 64 x 64 scene cube, every pixel a test pixel
         scene = run.whole if run.from_scene else None
         run.labeled = SyntheticHSIDataSet(shape, args.num_unlabel, 'label', seed=1, scene=scene)
@@ -612,6 +658,30 @@ def build_knn(run, args):
     run.knn = KnnEvaluator(NetShape(*run.shape), on(gallery.X, torch.float32), on(gallery.Y, torch.int64),
                            on(queries.X, torch.float32), on(queries.Y, torch.int64), k=args.knn,
                            T=args.temperature if args.knn_T is None else args.knn_T)
+
+
+def build_lp(run, args):
+    """--propagate: the nodes, registered once -- the labelled training pixels (the seeds: what --knn's gallery is) followed
+    by the test split's pixels; spectra and labels only, no cube"""
+    if args.synthetic:
+        seeds, queries = run.labeled, run.whole
+    else:
+        seeds, queries = HSIDataSet(int(args.dataID), 'label'), HSIDataSet(int(args.dataID), 'test')
+    run.lp_nodes = propagate_nodes(seeds.X, seeds.Y, queries.X, run.device)
+    run.lp_truth = np.asarray(queries.Y.cpu() if torch.is_tensor(queries.Y) else queries.Y, np.int64)
+
+
+def lp_lines(run, args, epoch):
+    """the ``validation_lp`` / ``validation_lp1`` lines of the engine's two networks after ``epoch`` epochs; a test pixel the
+    seeds do not reach counts as wrong"""
+    from cmlpl_amd.labelprop import propagate_embedding, score_labels
+    first = len(run.lp_nodes[1]) - len(run.lp_truth)
+    with torch.no_grad():
+        pairs = propagate_embedding((run.eng, None), *run.lp_nodes, run.shape[4], run.lp, probs=False)
+    for net, (_, res) in enumerate(pairs):
+        OA, Kappa, _, AA, _ = score_labels(res.labels[first:].cpu().numpy(), run.lp_truth, run.shape[4])
+        print('Epoch %d/%d: validation_lp%s OA = %.2f AA = %.2f Kappa = %.2f' %
+              (epoch, args.num_epochs, NET_TAGS[net], OA * 100, AA * 100, Kappa * 100))
 
 
 def knn_lines(run, args, epoch):
@@ -827,6 +897,8 @@ def report(run, args):
             np.savez(args.save_eval, **{k: v for curve in curves.values() if curve.epochs for k, v in curve.npz_entries().items()})
     if run.knn is not None and not (curves['_knn'].epochs and curves['_knn'].epochs[-1] == args.num_epochs and run.evaluator is not None):
         knn_lines(run, args, args.num_epochs)        # (once after the last epoch: --eval_every has not just printed them)
+    if run.lp is not None:
+        lp_lines(run, args, args.num_epochs)         # --propagate: once after the last epoch
     if args.no_eval:
         return
     nets = [(net, eng.state_dict(net)) for net in range(2)]
@@ -897,6 +969,9 @@ def main(args, make_engine=None, device=None):
         raise SystemExit("--knn K: 1 .. 32 neighbours")
     if args.knn_T is not None and (args.knn is None or not (0.0 < args.knn_T < float("inf"))):
         raise SystemExit("--knn_T T: a finite T > 0, with --knn K")
+    lp = propagate_of(args)
+    if lp is not None and world > 1:
+        raise SystemExit(f"--propagate runs on one GPU (this job has {world} ranks)")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(device)
@@ -909,7 +984,7 @@ def main(args, make_engine=None, device=None):
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
                              evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth,
-                             pl_curve=[], knn=None, optim=None, optim_hist=None, total_steps=0)
+                             pl_curve=[], knn=None, optim=None, optim_hist=None, total_steps=0, lp=lp)
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -925,6 +1000,8 @@ def main(args, make_engine=None, device=None):
         build_evaluator(run, args)    # evaluator
     if args.knn is not None and rank == 0:
         build_knn(run, args)          # knn: --knn's gallery and queries
+    if lp is not None and rank == 0:
+        build_lp(run, args)           # lp_nodes, lp_truth: --propagate's seeds and test pixels
     if args.resume:
         restore_progress(run, args)   # start_epoch, its rows of loss_hist, the curves so far and best_oa
     train_epochs(run, args)
@@ -1033,6 +1110,7 @@ def build_parser():
                              "one GPU")
     parser.add_argument('--knn_T', type=float, default=None, metavar='T',
                         help='--knn: the temperature of the vote (default: --temperature, the one the similarity softmax trains under)')
+    add_propagate_flags(parser, 'two lines validation_lp / validation_lp1 after the last epoch')
     parser.add_argument('--save_eval', default=None,
                         help='--eval_every: write the curve [evaluations][nets][OA, AA, Kappa], its epochs and the '
                              'confusion matrices as .npz')

@@ -39,7 +39,7 @@ import torch
 
 from . import _lib
 from .config import FEAT_DIM, HyperParams, NetShape
-from .engine import SCALAR_NAMES, TrainEngine, _chk_f32
+from .engine import SCALAR_NAMES, TrainEngine, _ReplayTable, _chk_f32, _fill_rows
 
 
 class DistStartupError(RuntimeError):
@@ -50,7 +50,6 @@ def _fail_after(seconds: float, what: str):
     """Watchdog for a start-up phase that may hang (rendezvous, RCCL communicator creation, first collective): if the
     returned timer is not cancelled in time, say what was being waited for and end THIS process with code 3 -- a hung
     rank would otherwise hang the whole job (the launcher stops the others when one exits non-zero)."""
-    import os
     import sys
     import threading
 
@@ -81,7 +80,6 @@ def init_distributed(backend: str = "nccl", device: Optional[torch.device] = Non
     `one_gpu`: rehearsal of the multi-process path on a one-GPU box (gloo over device buffers): check 1 / the
     distinct-device part of 3 are skipped.  Returns torch.distributed."""
     import datetime
-    import os
     import torch.distributed as dist
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -209,7 +207,6 @@ class TorchDistComm:
     before / after a reduce-scatter and an all-reduce agree across ranks) -- slow, for bring-up on a new node."""
 
     def __init__(self, group=None, debug: Optional[bool] = None):
-        import os
         import torch.distributed as dist
         self.dist, self.group = dist, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
@@ -339,18 +336,6 @@ def drive_step(engine, comm, *fwd_args, **fwd_kw) -> None:
     assert not pending, f"exchanges never waited for: {sorted(pending)}"
 
 
-def _fill_batch(b, XPl, Xl, Y, XPu, Xu, cube=None, lab_pix=None, unl_pix=None) -> None:
-    """the row sources of a cmlpl_batch record: the window tensors, or (cube-fed) the scene and its two pixel lists"""
-    b.d_xl, b.d_xu, b.d_labels = Xl.data_ptr(), Xu.data_ptr(), Y.data_ptr()
-    if cube is None:
-        b.d_xpl, b.d_xpu = XPl.data_ptr(), XPu.data_ptr()
-        b.d_cube, b.d_lab_pix, b.d_unl_pix, b.cube_rows, b.cube_cols = None, None, None, 0, 0
-    else:
-        b.d_xpl, b.d_xpu = None, None
-        b.d_cube, b.d_lab_pix, b.d_unl_pix = cube.data_ptr(), lab_pix.data_ptr(), unl_pix.data_ptr()
-        b.cube_rows, b.cube_cols = cube.shape[0], cube.shape[1]
-
-
 class DistTrainEngine(TrainEngine):
     """TrainEngine whose step is sharded by sample over ``comm.world`` ranks.  Batch sizes given to
     the constructor are PER RANK (the largest shard a step may bring); banks are sized from the global
@@ -419,6 +404,11 @@ class DistTrainEngine(TrainEngine):
         if lw == 0:
             raise _lib.CmlplError("cmlpl_loss_workspace_bytes", -2)
         self.loss_ws = torch.empty(lw, dtype=torch.uint8, device=dev)
+        # (one cmlpl_banks record, kept: only the two pointers change from step to step -- rebuilding the structs of a
+        #  stage call on every step was a third of the sharded step's host time)
+        self._c_banks = _lib.Banks()
+        self._fill_banks(self._c_banks)
+        self._unpacked = False      # outputs(): the gathered blocks of the last step are in global row order
         self._bound = None
         self._bind(bt_l, btu_l)
         self._ctx = None
@@ -449,6 +439,7 @@ class DistTrainEngine(TrainEngine):
         # world 1: the column-side gradient partial IS this rank's slice of dfeat
         self.dfw_part = self.dfeat_l[1, bt_l:] if alias else self._dfw_part[:self.btu_g * FEAT_DIM].view(self.btu_g, FEAT_DIM)
         self.cshard = _lib.Shard(self.bt_g, self.btu_g, self.rank * bt_l, bt_l, self.rank * btu_l, btu_l)
+        self._c_gathered = _lib.Gathered(self.recv.data_ptr(), self.logits_l.data_ptr(), W, bt_l, btu_l)
         self._bound = (bt_l, btu_l)
         self._args = None           # the stage calls' ready-made argument tuples (see _stage_args)
         self._io = None             # cmlpl_dist_step's records (see _step_io)
@@ -462,17 +453,13 @@ class DistTrainEngine(TrainEngine):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _banks(self) -> _lib.Banks:
-        # (one record, kept: only the two pointers change from step to step -- rebuilding the structs of a stage call
-        #  on every step was a third of the sharded step's host time)
-        b = self.__dict__.get("_c_banks")
-        if b is None:
-            b = self._c_banks = _lib.Banks()
-            for i in range(2):
-                b.d_feats[i] = self.bank_feats[i].data_ptr()
-                b.d_probs[i] = self.bank_probs[i].data_ptr()
-            b.Q = self.Q
+        """the kept cmlpl_banks record, its pointers those of the step about to run"""
+        b = self._c_banks
         b.ptr[0], b.ptr[1] = self.ptr
         return b
+
+    def _gathered(self) -> _lib.Gathered:
+        return self._c_gathered         # (of the bound shard: _bind)
 
     def _stage_args(self):
         """The seven stage calls' argument tuples for the bound shard, built ONCE: every pointer into the engine's own
@@ -515,21 +502,14 @@ class DistTrainEngine(TrainEngine):
     # ------------------------------------------------------------------ stages (no communication inside)
     def _begin_step(self, XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise=None, dropmask=None, apply_update=True,
                     lab_idx=None, unl_idx=None, cube=None, lab_pix=None, unl_pix=None):
-        """checks, the shard's views, and what changes from step to step written into the kept ctypes cells"""
+        """checks, the shard's views, and what changes from step to step written into the kept ctypes cells; returns the
+        step's row of the logging ring"""
         s = self.shape
-        g = self._graph() if self._graph is not None else None
-        if g is not None and g.pending > 0:
-            raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them (or program() anew) "
-                               "before an eager step")
+        if self._graph is not None:
+            self._refuse_pending("an eager step", " (or program() anew)")
         # (lab_idx / unl_idx: THIS rank's rows as indices into the resident splits, see TrainEngine.step)
         # (cube / lab_pix / unl_pix: the cube-fed step, XPl = XPu = None -- see TrainEngine.step)
-        cube_fed = cube is not None or lab_pix is not None or unl_pix is not None
-        if cube_fed:
-            if XPl is not None or XPu is not None:
-                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
-            bt_l, btu_l = self._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx)
-        else:
-            bt_l, btu_l = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        bt_l, btu_l = self._check_batch(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
         if btu_l > self.btu_max:
             raise ValueError(f"shard {bt_l}+{btu_l} outside the engine's capacity {self.bt_max}+{self.btu_max} per rank")
         if self.Q < (bt_l + btu_l) * self.world:
@@ -537,31 +517,29 @@ class DistTrainEngine(TrainEngine):
         self._bind(bt_l, btu_l)
         n_l = bt_l + btu_l
         self._ensure_packed(self._stream())
-        keep = None
-        noise8 = None
+        keep = noise8 = None
         if noise is not None:
             keep = (C.c_void_p * 8)(*[t.data_ptr() for t in noise])
             noise8 = C.cast(keep, C.POINTER(C.c_void_p))
         if dropmask is not None:
             _chk_f32(dropmask, (2, n_l, s.cls_in), "dropmask")
-        self._cur_row = self.step_count % self.hist_rows
+        row = self.step_count % self.hist_rows
         if self._args is None:
             self._stage_args()
         c = self._cells
         b = c["batch"]          # (updated in place: the stage calls hold a reference to this record)
-        _fill_batch(b, XPl, Xl, Y, XPu, Xu, cube, lab_pix, unl_pix)
-        b.noise8, b.bt, b.btu = noise8, bt_l, btu_l
-        b.d_lab_idx = None if lab_idx is None else lab_idx.data_ptr()
-        b.d_unl_idx = None if unl_idx is None else unl_idx.data_ptr()
+        _fill_rows(b, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt_l, btu_l, cube, lab_pix, unl_pix)
+        b.noise8 = noise8
         c["step"].value = self.step_count
         c["smooth"].value = 1 if self.hp.smooth_gate(epoch, batch_index) else 0
         c["adap"].value = float(self.hp.thr * self.hp.adap_thr(epoch))
         c["dm"].value = None if dropmask is None else dropmask.data_ptr()
         c["adam_t"].value = self.adam_t + 1
-        c["scal"].value = self.scalar_hist.data_ptr() + 64 * self._cur_row       # this step's row of the logging ring
+        c["scal"].value = self.scalar_hist.data_ptr() + 64 * row         # this step's row of the logging ring
         self._banks()           # (the record's pointers: ptr[] of this step)
-        self._ctx = dict(apply_update=apply_update, keep=(keep, XPl, Xl, Y, XPu, Xu, noise, lab_idx, unl_idx, dropmask,
+        self._ctx = dict(apply_update=apply_update, row=row, keep=(keep, XPl, Xl, Y, XPu, Xu, noise, lab_idx, unl_idx, dropmask,
                                                           cube, lab_pix, unl_pix))
+        return row
 
     def stage_spectral(self, *args, **kw):
         self._begin_step(*args, **kw)
@@ -574,13 +552,6 @@ class DistTrainEngine(TrainEngine):
         # are handed over as they are (the fused forward leaves the augmented rows in the workspace for the backward
         # stages: no other forward may use this workspace in between)
         self._call("spatial")
-
-    def _gathered(self) -> _lib.Gathered:
-        g = self.__dict__.get("_c_gathered")
-        if g is None or self._c_gathered_for != self._bound:
-            g = self._c_gathered = _lib.Gathered(self.recv.data_ptr(), self.logits_l.data_ptr(), self.world, self.bt_l, self.btu_l)
-            self._c_gathered_for = self._bound
-        return g
 
     def stage_phase1(self):
         # the loss kernels read the global rows where the all-gather left them (rank-major blocks): no re-ordering copy
@@ -606,12 +577,7 @@ class DistTrainEngine(TrainEngine):
         self._end_step()
 
     def _end_step(self):
-        if self._ctx["apply_update"]:
-            self.adam_t += 1
-        p0 = (self.ptr[0] + self.hp.bank_step) % self.Q                 # train.py:234,237
-        self.ptr = [p0, (p0 + self.hp.bank_step) % self.Q]
-        self.step_count += 1
-        self._last_n = self.bt_l + self.btu_l
+        self._advance(self.bt_l + self.btu_l, self._ctx["apply_update"], self._ctx["row"])
         self._ctx = None
 
     # the collectives that follow a stage: (kind, output, input, key).  key None: synchronous (on the critical path);
@@ -647,12 +613,12 @@ class DistTrainEngine(TrainEngine):
                        lab_idx=lab_idx, unl_idx=unl_idx, cube=cube, lab_pix=lab_pix, unl_pix=unl_pix)
             return
         # the whole step as ONE C call: stages and collectives enqueued back to back (cmlpl_dist_step, csrc/dist.hip)
-        self._begin_step(XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise, dropmask, apply_update, lab_idx=lab_idx, unl_idx=unl_idx,
-                         cube=cube, lab_pix=lab_pix, unl_pix=unl_pix)
+        row = self._begin_step(XPl, Xl, Y, XPu, Xu, epoch, batch_index, noise, dropmask, apply_update, lab_idx=lab_idx,
+                               unl_idx=unl_idx, cube=cube, lab_pix=lab_pix, unl_pix=unl_pix)
         io, a, c = self._step_io()
         io.batch, io.banks = c["batch"], self._c_banks
         a.step, a.adam_t, a.d_dropmask = c["step"].value, c["adam_t"].value, c["dm"].value
-        a.smooth, a.adap_mask, a.apply_update, a.scalars_row = c["smooth"].value, c["adap"].value, 1 if apply_update else 0, self._cur_row
+        a.smooth, a.adap_mask, a.apply_update, a.scalars_row = c["smooth"].value, c["adap"].value, 1 if apply_update else 0, row
         self._unpacked = False
         _lib.check("cmlpl_dist_step", self.lib.cmlpl_dist_step(
             C.byref(self.cshape), C.byref(self._chp), C.byref(io), C.byref(a), coll, self._stream()))
@@ -668,23 +634,27 @@ class DistTrainEngine(TrainEngine):
         nat = getattr(self.comm, "native", None)
         return C.byref(nat(self.async_exchanges)) if nat is not None else False
 
+    def _dist_io(self) -> _lib.DistIO:
+        """a cmlpl_dist_io of the bound shard: everything but the batch, the bank pointers and a replay table"""
+        io = _lib.DistIO()
+        io.shard, io.gathered = self.cshard, self._gathered()
+        io.d_params, io.d_m, io.d_v, io.d_packed = self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.packed.data_ptr()
+        io.d_grads, io.grad_stride = self.grads.data_ptr(), self.live
+        io.d_logits_l, io.d_feat_l, io.d_labels_f = self.logits_l.data_ptr(), self.feat_l.data_ptr(), self.labels_f.data_ptr()
+        io.d_dlogits, io.d_dfeat = self.dlogits_l.data_ptr(), self.dfeat_l.data_ptr()
+        io.d_probs_l, io.d_probs_g, io.probs_shard_rows = self.probs_l.data_ptr(), self.probs_g.data_ptr(), self.btu_l
+        io.d_scalars, io.d_dfeat_w_partial = self.scalar_hist.data_ptr(), self.dfw_part.data_ptr()
+        io.d_workspace, io.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
+        io.d_loss_workspace, io.loss_workspace_bytes = self.loss_ws.data_ptr(), self.loss_ws.numel()
+        io.seed = self.seed
+        return io
+
     def _step_io(self):
         """cmlpl_dist_io of the bound shard in by-value mode + the per-step record, built once per shard"""
         if self._args is None:
             self._stage_args()
         if self._io is None:
-            io = _lib.DistIO()
-            io.shard, io.gathered = self.cshard, self._gathered()
-            io.d_params, io.d_m, io.d_v, io.d_packed = self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.packed.data_ptr()
-            io.d_grads, io.grad_stride = self.grads.data_ptr(), self.live
-            io.d_logits_l, io.d_feat_l, io.d_labels_f = self.logits_l.data_ptr(), self.feat_l.data_ptr(), self.labels_f.data_ptr()
-            io.d_dlogits, io.d_dfeat = self.dlogits_l.data_ptr(), self.dfeat_l.data_ptr()
-            io.d_probs_l, io.d_probs_g, io.probs_shard_rows = self.probs_l.data_ptr(), self.probs_g.data_ptr(), self.btu_l
-            io.d_scalars, io.d_dfeat_w_partial = self.scalar_hist.data_ptr(), self.dfw_part.data_ptr()
-            io.d_workspace, io.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
-            io.d_loss_workspace, io.loss_workspace_bytes = self.loss_ws.data_ptr(), self.loss_ws.numel()
-            io.seed = self.seed
-            self._io = (io, _lib.DistStepArgs())
+            self._io = (self._dist_io(), _lib.DistStepArgs())
         return self._io[0], self._io[1], self._cells
 
     def capture(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
@@ -700,7 +670,7 @@ class DistTrainEngine(TrainEngine):
         ranks ; unlabelled of all ranks] (re-ordered on demand from the gathered blocks; the step itself never
         makes this copy and never gathers the logits: they are gathered HERE, a collective every rank must join --
         or handed in as ``gathered_logits``, the ranks' logits_l back to back)."""
-        if not getattr(self, "_unpacked", False):
+        if not self._unpacked:
             nk = self.logits_l.numel()
             if gathered_logits is not None:          # (a harness that moved the blocks itself: tests' lockstep ranks)
                 recv_z = gathered_logits.reshape(-1)
@@ -717,22 +687,18 @@ class DistTrainEngine(TrainEngine):
         return self.logits_g, self.feat_g
 
     def read_scalars(self):
-        t = self.scalars.clone()
-        self.comm.all_reduce(t)             # shares are additive (finalize_kernel)
-        return dict(zip(SCALAR_NAMES, t.tolist()))
+        return dict(zip(SCALAR_NAMES, self._reduce_rows(self.scalars.clone()).tolist()))
 
     def loss_row(self):
-        t = self.scalars.clone()
-        self.comm.all_reduce(t)
-        return t[:5].tolist()
+        return self._reduce_rows(self.scalars.clone())[:5].tolist()
 
     def _reduce_rows(self, rows):
         rows = rows.contiguous()
-        self.comm.all_reduce(rows)          # one collective per printed window
+        self.comm.all_reduce(rows)          # shares are additive (finalize_kernel): one collective per row or window
         return rows
 
 
-class DistStepGraph:
+class DistStepGraph(_ReplayTable):
     """The sharded training step replayed from seven hipGraphs (spectral | spatial | phase 1 | phase 2 | backward data |
     backward weights | update) with the step's four collectives issued eagerly between them, exactly where and how
     ``drive_step`` issues them: the embedding all-gather asynchronously behind the spectral stage (waited for in front of
@@ -745,53 +711,14 @@ class DistStepGraph:
 
     def __init__(self, eng: "DistTrainEngine", XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
                  cube=None, lab_pix=None, unl_pix=None):
-        import numpy as np
-        self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
-        if lab_idx is None or unl_idx is None:
-            raise ValueError("a captured step reads its rows through index buffers")
-        for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
-            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name}: need a contiguous int64 cuda vector")
-        if lab_idx.shape[0] < bt or unl_idx.shape[0] < btu:
-            raise ValueError("index buffers shorter than one shard")
-        if eng.step_count == 0:
-            raise RuntimeError("run one eager DistTrainEngine.step() before capturing (kernel attributes are set lazily)")
-        if cube is not None or lab_pix is not None or unl_pix is not None:
-            if XPl is not None or XPu is not None:
-                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
-            eng._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx[:bt], unl_idx[:btu])
-        else:
-            eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
-        TrainEngine.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
-        TrainEngine.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
+        super().__init__(eng, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix,
+                         a_batch="shard")
         eng._bind(self.bt, self.btu)
-        self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
-        self.n_lab_idx, self.n_unl_idx = int(lab_idx.shape[0]), int(unl_idx.shape[0])
         dev = eng.device
-        self.table = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8, device=dev)
-        self.cursor = torch.ones(1, dtype=torch.int32, device=dev)
-        self.host = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8).pin_memory()
-        self.rows = self.host.numpy().view(np.dtype(_lib.DYN_DTYPE))[1:]
-        self.pending = 0
-        st = eng._stream()
-        eng._ensure_packed(st)
-        io = _lib.DistIO()
-        _fill_batch(io.batch, XPl, Xl, Y, XPu, Xu, cube, lab_pix, unl_pix)
-        io.batch.noise8, io.batch.bt, io.batch.btu = None, self.bt, self.btu
-        io.batch.d_lab_idx, io.batch.d_unl_idx = lab_idx.data_ptr(), unl_idx.data_ptr()
-        io.shard = eng.cshard
-        io.gathered = eng._gathered()
+        eng._ensure_packed(eng._stream())
+        io = eng._dist_io()
+        _fill_rows(io.batch, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, self.bt, self.btu, cube, lab_pix, unl_pix)
         io.banks = eng._banks()
-        io.d_params, io.d_m, io.d_v, io.d_packed = eng.params.data_ptr(), eng.m.data_ptr(), eng.v.data_ptr(), eng.packed.data_ptr()
-        io.d_grads, io.grad_stride = eng.grads.data_ptr(), eng.live
-        io.d_logits_l, io.d_feat_l, io.d_labels_f = eng.logits_l.data_ptr(), eng.feat_l.data_ptr(), eng.labels_f.data_ptr()
-        io.d_dlogits, io.d_dfeat = eng.dlogits_l.data_ptr(), eng.dfeat_l.data_ptr()
-        io.d_probs_l, io.d_probs_g, io.probs_shard_rows = eng.probs_l.data_ptr(), eng.probs_g.data_ptr(), self.btu
-        io.d_scalars = eng.scalar_hist.data_ptr()
-        io.d_dfeat_w_partial = eng.dfw_part.data_ptr()
-        io.d_workspace, io.workspace_bytes = eng.workspace.data_ptr(), eng.workspace.numel()
-        io.d_loss_workspace, io.loss_workspace_bytes = eng.loss_ws.data_ptr(), eng.loss_ws.numel()
-        io.seed = eng.seed
         io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
         self._io = io
         eng._captured = True
@@ -807,17 +734,6 @@ class DistStepGraph:
                 self.handles[name] = h
         torch.cuda.current_stream(dev).wait_stream(cap)
 
-    def validate_indices(self) -> None:
-        """range check of the two index buffers (synchronising): after the caller re-filled them in place"""
-        _, Xl, _, _, Xu, lab_idx, unl_idx = self._keep[:7]
-        TrainEngine.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
-        TrainEngine.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
-
-    def program(self, steps) -> None:
-        """as StepGraph.program: (epoch, batch_index, lab_off, unl_off) of the next replays, offsets = this rank's"""
-        from .engine import StepGraph
-        StepGraph.program(self, steps)
-
     def launch_stage(self, name: str) -> None:
         """enqueue ONE stage's graph (the lockstep test harness performs the exchanges itself; ``launch`` is the product path)"""
         eng = self.eng
@@ -826,15 +742,10 @@ class DistStepGraph:
         if name == eng.STAGES[0]:
             eng._bind(self.bt, self.btu)      # (an eager short batch in between re-bound the views; same pointers for the same shard)
             eng._ensure_packed(eng._stream())
-            eng._cur_row = eng.step_count % eng.hist_rows
             eng._unpacked = False
         _lib.check("cmlpl_step_graph_launch", eng.lib.cmlpl_step_graph_launch(self.handles[name], eng._stream()))
-        if name == "update":                  # host copy of the step bookkeeping (train.py:234,237)
-            eng.adam_t += 1
-            p0 = (eng.ptr[0] + eng.hp.bank_step) % eng.Q
-            eng.ptr = [p0, (p0 + eng.hp.bank_step) % eng.Q]
-            eng.step_count += 1
-            eng._last_n = self.bt + self.btu
+        if name == "update":
+            eng._advance(self.bt + self.btu, True)
             self.pending -= 1
 
     def launch(self) -> None:
@@ -859,9 +770,3 @@ class DistStepGraph:
             if h:
                 self.eng.lib.cmlpl_step_graph_destroy(h)
         self.handles = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -8,13 +8,14 @@ train.py:147-148,212 -- and ONE ctypes call per step into ``cmlpl_train_step``
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import os
+import weakref
 from collections import OrderedDict
 from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
-
-import os
-import weakref
 
 from . import _lib
 from .config import FEAT_DIM, HyperParams, NetShape
@@ -43,9 +44,45 @@ def _chk_f32(t: torch.Tensor, shape, name):
                          f"got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+def _chk_idx(t: torch.Tensor, name: str, rows: Optional[int] = None, what: str = "") -> None:
+    """an index vector as the kernels follow it (``rows``: its length, said in ``what``)"""
+    if t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous() \
+            or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name}: need a contiguous int64 cuda vector{what}")
+
+
 def check_spatial(mode: str) -> str:
     _lib.spatial_elements(mode)
     return mode
+
+
+def _fill_rows(rec, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube=None, lab_pix=None, unl_pix=None) -> None:
+    """the row sources of a cmlpl_step_io or a cmlpl_batch record (the same field names): the window tensors, or
+    (cube-fed) the scene and its two pixel lists; the index lists; the batch's size"""
+    rec.d_xl, rec.d_labels, rec.d_xu = Xl.data_ptr(), Y.data_ptr(), Xu.data_ptr()
+    if cube is None:
+        rec.d_xpl, rec.d_xpu = XPl.data_ptr(), XPu.data_ptr()
+        rec.d_cube, rec.d_lab_pix, rec.d_unl_pix, rec.cube_rows, rec.cube_cols = None, None, None, 0, 0
+    else:
+        rec.d_xpl, rec.d_xpu = None, None
+        rec.d_cube, rec.d_lab_pix, rec.d_unl_pix = cube.data_ptr(), lab_pix.data_ptr(), unl_pix.data_ptr()
+        rec.cube_rows, rec.cube_cols = cube.shape[0], cube.shape[1]
+    rec.d_lab_idx = None if lab_idx is None else lab_idx.data_ptr()
+    rec.d_unl_idx = None if unl_idx is None else unl_idx.data_ptr()
+    rec.bt, rec.btu = bt, btu
+
+
+def replay_counters(ptr, adam_t: int, step_count: int, Q: int, bank_step: int, hist_rows: int, method: str, k: int):
+    """``TrainEngine._advance`` for k steps ahead, as the columns of a replay table: row j is what the j-th step from
+    now reads -- ``step`` and ``ptr`` as they stand BEFORE it, its own 1-based ``adam_t`` and the ``hist_row`` it writes.
+    Row 0 carries the pointers as they are: ptr1 follows ptr0 (train.py:234,237) only from the first advance on."""
+    j = np.arange(k, dtype=np.int64)
+    p = np.empty((k, 2), np.int64)
+    p[:] = ptr                            # (CPS has no memory bank: its pointers stay where they are)
+    if method == "cmlpl":
+        p[:, 0] = (ptr[0] + j * bank_step) % Q
+        p[1:, 1] = (p[1:, 0] + bank_step) % Q
+    return dict(step=step_count + j, adam_t=adam_t + 1 + j, ptr=p, hist_row=(step_count + j) % hist_rows)
 
 
 class Teacher:
@@ -127,6 +164,7 @@ class TrainEngine:
     """
     takes_indices = True      # step(..., lab_idx=, unl_idx=): batches as row indices into the resident splits
     takes_cube = True         # step(None, Xl, Y, None, Xu, ..., cube=, lab_pix=, unl_pix=): windows gathered from the scene
+    world = 1                 # ranks the step is sharded over (DistTrainEngine: its communicator's)
 
     def __init__(self, shape: NetShape, labeled_batch_size: int, unlabeled_batch_size: int,
                  hp: Optional[HyperParams] = None, device="cuda:0", seed: int = 1088, bank_labeled: int = 0,
@@ -144,7 +182,6 @@ class TrainEngine:
             raise RuntimeError("cmlpl_amd.TrainEngine needs a GPU (no CPU fallback)")
         self.shape, self.hp = shape, hp or HyperParams()
         if self.method == "cps":
-            import dataclasses
             self.hp = dataclasses.replace(self.hp, w_mutual=CPS_W_CROSS)
         self.device = torch.device(device)
         self.bt_max, self.btu_max = int(labeled_batch_size), int(unlabeled_batch_size)
@@ -246,10 +283,7 @@ class TrainEngine:
         """the norms rows of the last k steps, oldest first, float32 numpy [k][4] (as ``loss_window``; one read-back)"""
         if self.norm_hist is None:
             raise RuntimeError("norm_window(): an engine built with optim=OptimConfig(...) with an option on")
-        if k < 1 or k > self.hist_rows or k > self.step_count:
-            raise ValueError(f"window of {k} steps not held (hist_rows={self.hist_rows}, steps={self.step_count})")
-        idx = [(self.step_count - k + j) % self.hist_rows for j in range(k)]
-        return self.norm_hist[torch.tensor(idx, device=self.device)].cpu().numpy()
+        return self._ring_rows(self.norm_hist, k).cpu().numpy()
 
     def tensor_shapes(self) -> "OrderedDict[str, tuple]":
         s = self.shape
@@ -320,10 +354,8 @@ class TrainEngine:
     def _pl_truth(self, unl_truth, rows: int) -> torch.Tensor:
         if unl_truth is None:
             raise ValueError("an engine built with pl_monitor scores every step: pass unl_truth (the unlabelled rows' labels)")
-        t = unl_truth
-        if t.dtype != torch.int64 or tuple(t.shape) != (rows,) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"unl_truth: need a contiguous int64 cuda vector, one label per unlabelled row ({rows})")
-        return t
+        _chk_idx(unl_truth, "unl_truth", rows, f", one label per unlabelled row ({rows})")
+        return unl_truth
 
     def _pl_update(self, stream, truth: torch.Tensor, idx_ptr, btu: int, adap_mask: float) -> None:
         """behind a step of ``self._last_n`` rows: its targets, still in the workspace, against ``truth`` (read at
@@ -377,20 +409,18 @@ class TrainEngine:
             self._flag_off = int(off.value)
         return self.packed[:, self._flag_off:].view(torch.int32)
 
-    def _refuse_pending(self, what: str) -> None:
+    def _refuse_pending(self, what: str, or_else: str = "") -> None:
         g = self._graph() if self._graph is not None else None
         if g is not None and g.pending > 0:
             # the programmed rows were formed from counters and bank pointers the replays have yet to catch up with
-            raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them before {what}")
+            raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them{or_else} before {what}")
 
     def identity(self) -> Dict[str, object]:
         """what a checkpoint must agree with to be loaded here (batch capacities GLOBAL: a sharded engine's are per rank)"""
         from .checkpoint import make_identity
-        W = getattr(self, "world", 1)
-        return make_identity(self.shape, self.hp, self.bt_max * W, self.btu_max * W, self.Q,
+        return make_identity(self.shape, self.hp, self.bt_max * self.world, self.btu_max * self.world, self.Q,
                              self.lib.cmlpl_source_hash().decode(), _lib.ABI_VERSION, method=self.method,
-                             teacher_alpha=getattr(self, "teacher_alpha", None),
-                             aug_spatial=getattr(self, "aug_spatial", "none"), optim=getattr(self, "optim", None))
+                             teacher_alpha=self.teacher_alpha, aug_spatial=self.aug_spatial, optim=self.optim)
 
     def checkpoint_state(self, on_device: bool = False, into: Optional[dict] = None) -> dict:
         """Everything the step carries from one step to the next (``grads``, the workspace and the logging ring are
@@ -405,7 +435,7 @@ class TrainEngine:
                    range_flags=self._flag_words())
         for net, key in enumerate(("Base", "Base1")):
             src[key] = OrderedDict((k, self.view(self.params, net, k)) for k in self.state_dict_keys())
-        if getattr(self, "teacher", None) is not None:
+        if self.teacher is not None:
             self._teacher_begin()
             src["teacher_params"] = self.teacher_params
             for net, key in enumerate(("Teacher", "Teacher1")):
@@ -454,7 +484,7 @@ class TrainEngine:
         self.adam_t, self.step_count = int(state["adam_t"]), int(state["step_count"])
         self._saved_flags = flags.to(self.device).clone()
         self._packed_dirty = True
-        if getattr(self, "teacher", None) is not None:
+        if self.teacher is not None:
             # (a state without a teacher: the average starts from the loaded parameters; an engine without one ignores
             #  the state's)
             t = state.get("teacher_params")
@@ -477,76 +507,76 @@ class TrainEngine:
         return [f"{mod}.{leaf}" for mod in order for leaf in ("weight", "bias")]
 
     # ------------------------------------------------------------------ the step
-    def _check_rows(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx):
-        """Shapes of a batch: the rows themselves, or (lab_idx / unl_idx given) the resident splits the int64 index
-        lists point into (hsi_loader.py:109-133 hands rows out by index; here the kernels follow the index)."""
+    def _check_batch(self, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix):
+        """The check of a batch, eager or captured -> (bt, btu).  Split-fed: the rows themselves, or (lab_idx / unl_idx
+        given) the resident splits the index lists point into (hsi_loader.py:109-133 hands rows out by index; here the
+        kernels follow the index).  CUBE-FED (any of cube / lab_pix / unl_pix given): the scene [rows][cols][C], the spectra /
+        labels of the splits (or of the batch), one scene pixel per split row and no window tensors."""
         s = self.shape
-        if lab_idx is not None and unl_idx is not None:
-            # the same resident splits as last time (by identity and storage): only the index lists are new
-            key = (id(XPl), id(Xl), id(Y), id(XPu), id(Xu), XPl.data_ptr(), XPu.data_ptr(), XPl.shape[0], XPu.shape[0])
-            if key == self._checked and lab_idx.dtype == torch.int64 and unl_idx.dtype == torch.int64 \
-                    and lab_idx.is_cuda and unl_idx.is_cuda and lab_idx.dim() == 1 and unl_idx.dim() == 1 \
-                    and lab_idx.is_contiguous() and unl_idx.is_contiguous():
-                bt, btu = lab_idx.shape[0], unl_idx.shape[0]
-                if 1 <= bt <= self.bt_max and btu >= 1 and bt + btu <= self.n_max:
-                    return bt, btu
-        if (lab_idx is None) != (unl_idx is None):
-            raise ValueError("lab_idx and unl_idx come together")
-        for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
-            if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError(f"{name}: need a contiguous int64 cuda vector")
-        bt = XPl.shape[0] if lab_idx is None else lab_idx.shape[0]
-        btu = XPu.shape[0] if unl_idx is None else unl_idx.shape[0]
-        n = bt + btu
-        if bt < 1 or btu < 1 or bt > self.bt_max or n > self.n_max:
-            raise ValueError(f"batch {bt}+{btu} outside the engine's capacity {self.bt_max}+{self.btu_max}")
-        nl, nu = XPl.shape[0], XPu.shape[0]
-        _chk_f32(XPl, (nl, s.C, s.H, s.W), "XPl"); _chk_f32(Xl, (nl, s.bands), "Xl")
-        _chk_f32(XPu, (nu, s.C, s.H, s.W), "XPu"); _chk_f32(Xu, (nu, s.bands), "Xu")
-        if Y.dtype != torch.int64 or tuple(Y.shape) != (nl,) or not Y.is_cuda:
-            raise ValueError("Y: need int64 cuda tensor, one label per labelled row")
-        if lab_idx is not None:
-            self._checked = (id(XPl), id(Xl), id(Y), id(XPu), id(Xu), XPl.data_ptr(), XPu.data_ptr(), XPl.shape[0], XPu.shape[0])
-        return bt, btu
-
-    def _check_cube_rows(self, cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx):
-        """Shapes of a CUBE-FED batch: the resident scene [rows][cols][C], the spectra / labels of the splits (or of the
-        batch) and one scene pixel per split row.  The pixel lists are range-checked here ONCE per array (a
-        synchronising min / max; the gather follows them without a bounds check), not per step."""
-        s = self.shape
-        if cube is None or lab_pix is None or unl_pix is None:
-            raise ValueError("a cube-fed step needs cube, lab_pix and unl_pix")
-        key = (id(cube), id(Xl), id(Y), id(Xu), id(lab_pix), id(unl_pix), cube.data_ptr(), lab_pix.data_ptr(),
-               unl_pix.data_ptr(), tuple(cube.shape), Xl.shape[0], Xu.shape[0])
-        if key != self._checked_cube:
-            if s.H != s.W:
-                raise ValueError(f"cube-fed windows are square, the shape has {s.H} x {s.W}")
-            if cube.dim() != 3 or cube.dtype != torch.float32 or not cube.is_contiguous() or not cube.is_cuda:
-                raise ValueError("cube: need a contiguous float32 cuda tensor [rows][cols][C]")
-            rows, cols, ch = cube.shape
-            if ch != s.C:
-                raise ValueError(f"cube: {ch} channels, the shape has C = {s.C}")
-            if rows < s.H or cols < s.W:
-                raise ValueError(f"cube: scene {rows} x {cols} smaller than the {s.H} x {s.W} window")
+        cube_fed = cube is not None or lab_pix is not None or unl_pix is not None
+        if cube_fed:
+            if XPl is not None or XPu is not None:
+                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
+            if cube is None or lab_pix is None or unl_pix is None:
+                raise ValueError("a cube-fed step needs cube, lab_pix and unl_pix")
+            key = (id(cube), id(Xl), id(Y), id(Xu), id(lab_pix), id(unl_pix), cube.data_ptr(), lab_pix.data_ptr(),
+                   unl_pix.data_ptr(), tuple(cube.shape), Xl.shape[0], Xu.shape[0])
+            if key != self._checked_cube:         # another scene than last time
+                self._check_scene(cube, Xl, Y, Xu, lab_pix, unl_pix)
+                self._checked_cube = key
             nl, nu = Xl.shape[0], Xu.shape[0]
-            _chk_f32(Xl, (nl, s.bands), "Xl"); _chk_f32(Xu, (nu, s.bands), "Xu")
-            if Y.dtype != torch.int64 or tuple(Y.shape) != (nl,) or not Y.is_cuda:
-                raise ValueError("Y: need int64 cuda tensor, one label per labelled row")
-            for name, t, n in (("lab_pix", lab_pix, nl), ("unl_pix", unl_pix, nu)):
-                if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_cuda or not t.is_contiguous():
-                    raise ValueError(f"{name}: need a contiguous int64 cuda vector, one scene pixel per split row ({n})")
-                self.check_index_range(t, rows * cols, name)
-            self._checked_cube = key
+        else:
+            if self.aug_spatial != "none":
+                self._refuse_split_fed()
+            if lab_idx is not None and unl_idx is not None:
+                # the same resident splits as last time (by identity and storage): only the index lists are new
+                key = (id(XPl), id(Xl), id(Y), id(XPu), id(Xu), XPl.data_ptr(), XPu.data_ptr(), XPl.shape[0], XPu.shape[0])
+                if key == self._checked and lab_idx.dtype == torch.int64 and unl_idx.dtype == torch.int64 \
+                        and lab_idx.is_cuda and unl_idx.is_cuda and lab_idx.dim() == 1 and unl_idx.dim() == 1 \
+                        and lab_idx.is_contiguous() and unl_idx.is_contiguous():
+                    bt, btu = lab_idx.shape[0], unl_idx.shape[0]
+                    if 1 <= bt <= self.bt_max and btu >= 1 and bt + btu <= self.n_max:
+                        return bt, btu
+            nl, nu = XPl.shape[0], XPu.shape[0]
         if (lab_idx is None) != (unl_idx is None):
             raise ValueError("lab_idx and unl_idx come together")
-        for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
-            if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError(f"{name}: need a contiguous int64 cuda vector")
-        bt = Xl.shape[0] if lab_idx is None else lab_idx.shape[0]
-        btu = Xu.shape[0] if unl_idx is None else unl_idx.shape[0]
+        if lab_idx is not None:
+            _chk_idx(lab_idx, "lab_idx")
+            _chk_idx(unl_idx, "unl_idx")
+        bt = nl if lab_idx is None else lab_idx.shape[0]
+        btu = nu if unl_idx is None else unl_idx.shape[0]
         if bt < 1 or btu < 1 or bt > self.bt_max or bt + btu > self.n_max:
             raise ValueError(f"batch {bt}+{btu} outside the engine's capacity {self.bt_max}+{self.btu_max}")
+        if not cube_fed:
+            _chk_f32(XPl, (nl, s.C, s.H, s.W), "XPl"); _chk_f32(XPu, (nu, s.C, s.H, s.W), "XPu")
+            self._check_spectra(Xl, Y, Xu)
+            if lab_idx is not None:
+                self._checked = key
         return bt, btu
+
+    def _check_spectra(self, Xl, Y, Xu) -> None:
+        nl, bands = Xl.shape[0], self.shape.bands
+        _chk_f32(Xl, (nl, bands), "Xl"); _chk_f32(Xu, (Xu.shape[0], bands), "Xu")
+        if Y.dtype != torch.int64 or tuple(Y.shape) != (nl,) or not Y.is_cuda:
+            raise ValueError("Y: need int64 cuda tensor, one label per labelled row")
+
+    def _check_scene(self, cube, Xl, Y, Xu, lab_pix, unl_pix) -> None:
+        """The resident arrays of a cube-fed batch.  The pixel lists are range-checked here ONCE per array (a
+        synchronising min / max; the gather follows them without a bounds check), not per step."""
+        s = self.shape
+        if s.H != s.W:
+            raise ValueError(f"cube-fed windows are square, the shape has {s.H} x {s.W}")
+        if cube.dim() != 3 or cube.dtype != torch.float32 or not cube.is_contiguous() or not cube.is_cuda:
+            raise ValueError("cube: need a contiguous float32 cuda tensor [rows][cols][C]")
+        rows, cols, ch = cube.shape
+        if ch != s.C:
+            raise ValueError(f"cube: {ch} channels, the shape has C = {s.C}")
+        if rows < s.H or cols < s.W:
+            raise ValueError(f"cube: scene {rows} x {cols} smaller than the {s.H} x {s.W} window")
+        self._check_spectra(Xl, Y, Xu)
+        for name, t, n in (("lab_pix", lab_pix, Xl.shape[0]), ("unl_pix", unl_pix, Xu.shape[0])):
+            _chk_idx(t, name, n, f", one scene pixel per split row ({n})")
+            self.check_index_range(t, rows * cols, name)
 
     @staticmethod
     def check_index_range(idx: torch.Tensor, rows: int, name: str = "index") -> None:
@@ -560,41 +590,36 @@ class TrainEngine:
         if lo < 0 or hi >= rows:
             raise ValueError(f"{name}: entries span [{lo}, {hi}], the resident split has {rows} rows")
 
-    def _fill_io(self, io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube=None, lab_pix=None, unl_pix=None):
-        io.d_xl, io.d_labels, io.d_xu = Xl.data_ptr(), Y.data_ptr(), Xu.data_ptr()
-        if cube is None:
-            io.d_xpl, io.d_xpu = XPl.data_ptr(), XPu.data_ptr()
-            io.d_cube, io.d_lab_pix, io.d_unl_pix, io.cube_rows, io.cube_cols = None, None, None, 0, 0
-        else:
-            io.d_xpl, io.d_xpu = None, None
-            io.d_cube, io.d_lab_pix, io.d_unl_pix = cube.data_ptr(), lab_pix.data_ptr(), unl_pix.data_ptr()
-            io.cube_rows, io.cube_cols = cube.shape[0], cube.shape[1]
-        io.d_lab_idx = None if lab_idx is None else lab_idx.data_ptr()
-        io.d_unl_idx = None if unl_idx is None else unl_idx.data_ptr()
-        io.bt, io.btu = bt, btu
+    _fill_io = staticmethod(_fill_rows)       # (io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube, lab_pix, unl_pix)
+
+    def _fill_banks(self, b) -> None:
+        """what never changes of a cmlpl_banks record (its two pointers follow ``self.ptr`` step by step)"""
+        for i in range(2):
+            b.d_feats[i] = self.bank_feats[i].data_ptr()
+            b.d_probs[i] = self.bank_probs[i].data_ptr()
+        b.Q = self.Q
 
     def _fill_state(self, io):
         io.d_params, io.d_m, io.d_v = self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
         io.d_grads, io.d_packed = self.grads.data_ptr(), self.packed.data_ptr()
-        for i in range(2):
-            io.banks.d_feats[i] = self.bank_feats[i].data_ptr()
-            io.banks.d_probs[i] = self.bank_probs[i].data_ptr()
-        io.banks.Q = self.Q
+        self._fill_banks(io.banks)
         # outputs are laid out [2][n][..] for THIS n (views of the max-size buffers)
         io.d_logits, io.d_feat = self.logits.data_ptr(), self.feat.data_ptr()
         io.d_workspace, io.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         io.seed = self.seed
         # cmlpl_step_io.reserved: the method (0 = CMLPL) in bits 0..7, the spatial augmentation (0 = none) in bits 8..9
-        io.reserved = _lib.METHODS[self.method] | (_lib.SPATIAL[getattr(self, "aug_spatial", "none")] << 8)
+        io.reserved = _lib.METHODS[self.method] | (_lib.SPATIAL[self.aug_spatial] << 8)
 
     def _refuse_split_fed(self) -> None:
-        if getattr(self, "aug_spatial", "none") != "none":
+        if self.aug_spatial != "none":
             raise ValueError(f"aug_spatial={self.aug_spatial!r} needs cube-fed steps (cube=, lab_pix=, unl_pix=): the "
                              "window's spatial element is applied in the gather from the scene")
 
-    def _advance(self, n, apply_update=True):
-        """host copy of the step bookkeeping: bank pointers (train.py:234,237 -- ptr1 follows ptr0, reference quirk
-        kept), Adam step, step counter"""
+    def _advance(self, n, apply_update=True, row=None):
+        """THE step bookkeeping, behind every step of n rows however it ran (eager, replayed, sharded): the ring row it
+        wrote (``row``, where the caller has formed it already), bank pointers (train.py:234,237 -- ptr1 follows ptr0,
+        reference quirk kept), Adam step, step counter.  ``replay_counters`` states the same rule for k steps ahead."""
+        self._cur_row = self.step_count % self.hist_rows if row is None else row
         if self.method == "cmlpl":        # (CPS has no memory bank: its pointers stay where they are)
             p0 = (self.ptr[0] + self.hp.bank_step) % self.Q
             self.ptr = [p0, (p0 + self.hp.bank_step) % self.Q]
@@ -625,18 +650,9 @@ class TrainEngine:
                    indexed the way Xu is -- the whole split's when unl_idx is given, the batch's otherwise
         """
         s = self.shape
-        g = self._graph() if self._graph is not None else None
-        if g is not None and g.pending > 0:
-            # the remaining replays were programmed from the state BEFORE this step (counters, bank pointers, Adam step)
-            raise RuntimeError(f"{g.pending} programmed graph replays are pending: launch them (or program() anew) "
-                               "before an eager step")
-        if cube is not None or lab_pix is not None or unl_pix is not None:
-            if XPl is not None or XPu is not None:
-                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
-            bt, btu = self._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx, unl_idx)
-        else:
-            self._refuse_split_fed()
-            bt, btu = self._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx)
+        if self._graph is not None:
+            self._refuse_pending("an eager step", " (or program() anew)")
+        bt, btu = self._check_batch(XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
         if _CHECK_INDICES and lab_idx is not None:
             self.check_index_range(lab_idx, Xl.shape[0], "lab_idx")
             self.check_index_range(unl_idx, Xu.shape[0], "unl_idx")
@@ -647,7 +663,7 @@ class TrainEngine:
         self._ensure_packed(stream)
         self._teacher_begin()
         io = self._io
-        self._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube, lab_pix, unl_pix)
+        _fill_rows(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, cube, lab_pix, unl_pix)
         io.noise8, io.d_dropmask = None, None
         keep = None
         if noise is not None:
@@ -662,8 +678,8 @@ class TrainEngine:
             io.d_dropmask = dropmask.data_ptr()
         for i in range(2):
             io.banks.ptr[i] = self.ptr[i]
-        self._cur_row = self.step_count % self.hist_rows
-        io.d_scalars = self.scalar_hist.data_ptr() + 64 * self._cur_row
+        row = self.step_count % self.hist_rows        # of the two logging rings
+        io.d_scalars = self.scalar_hist.data_ptr() + 64 * row
         io.smooth = 1 if self.hp.smooth_gate(epoch, batch_index) else 0
         io.adap_mask = float(self.hp.thr * self.hp.adap_thr(epoch))        # train.py:221
         io.adam_t = self.adam_t + 1
@@ -673,12 +689,12 @@ class TrainEngine:
             _lib.check("cmlpl_train_step",
                        self.lib.cmlpl_train_step(C.byref(self.cshape), C.byref(self._chp), C.byref(io), stream))
         else:
-            self._copt.d_norms = self.norm_hist.data_ptr() + 16 * self._cur_row
+            self._copt.d_norms = self.norm_hist.data_ptr() + 16 * row
             _lib.check("cmlpl_train_step_opt", self.lib.cmlpl_train_step_opt(
                 C.byref(self.cshape), C.byref(self._hp_at(self.adam_t + 1)), C.byref(io), C.byref(self._copt), stream))
         if self.teacher is not None and apply_update:
             self._teacher_update(stream)
-        self._advance(n, apply_update)
+        self._advance(n, apply_update, row)
         self._last_btu = btu
         if self.pl_block is not None:     # one launch behind the step, on its stream; io.adap_mask: the float32 the step read
             self._pl_update(stream, unl_truth, _ptr(unl_idx), btu, io.adap_mask)
@@ -731,90 +747,58 @@ class TrainEngine:
     def loss_window(self, k: int):
         """loss_hist[index_i-k+1 : index_i+1] (train.py:285-289) as a float64 numpy array [k,5]: the rows of the
         last k steps, oldest first.  One synchronising read-back."""
-        if k < 1 or k > self.hist_rows or k > self.step_count:
-            raise ValueError(f"window of {k} steps not held (hist_rows={self.hist_rows}, steps={self.step_count})")
-        idx = [(self.step_count - k + j) % self.hist_rows for j in range(k)]
-        rows = self.scalar_hist[torch.tensor(idx, device=self.device)]
-        out = self._reduce_rows(rows)[:, :5].double().cpu().numpy()
+        out = self._reduce_rows(self._ring_rows(self.scalar_hist, k))[:, :5].double().cpu().numpy()
         if self.method == "cps":
             out[:, 0] = out[:, 3]          # trian_CPS.py:254: column 0 repeats the cross loss
         return out
+
+    def _ring_rows(self, hist: torch.Tensor, k: int) -> torch.Tensor:
+        """the rows that the last k steps wrote into a [hist_rows][..] ring, oldest first"""
+        if k < 1 or k > self.hist_rows or k > self.step_count:
+            raise ValueError(f"window of {k} steps not held (hist_rows={self.hist_rows}, steps={self.step_count})")
+        idx = [(self.step_count - k + j) % self.hist_rows for j in range(k)]
+        return hist[torch.tensor(idx, device=self.device)]
 
     def _reduce_rows(self, rows: torch.Tensor) -> torch.Tensor:
         return rows
 
 
-class StepGraph:
-    """The training step as a replayable hipGraph (SURVEY.md section 7 stage 6; ``cmlpl_step_graph_create``).
+class _ReplayTable:
+    """What a captured step replays from, single-GPU (``StepGraph``) or sharded (``DistStepGraph``): the device table of
+    ``cmlpl_dyn`` rows with its cursor, the pinned rows ``program()`` fills them through, and the checks of a capture's
+    arguments.  What is captured, and what a replay launches, is the subclass's."""
 
-    Everything that changes from step to step -- random-stream counter, Adam step, bank pointers, the train.py:212 /
-    :221 gates, the offsets of the batch inside the index buffers, the row of the logging ring -- lives in a device
-    table of ``cmlpl_dyn`` rows that ``program()`` fills for a run of steps ahead of time (an epoch, say); a device
-    cursor walks it, advanced by the step itself.  ``launch()`` is then ONE hipGraphLaunch per step: no arguments to
-    marshal, nothing else enqueued.  The engine's host-side bookkeeping advances exactly as in ``TrainEngine.step``,
-    so eager steps and replays can be mixed (an epoch's short last batch runs eagerly: its shape is not the graph's)
-    -- but only BETWEEN programs: an eager step while programmed replays are pending raises (their rows were formed
-    from the state before it).
-    """
-
-    def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
-                 cube=None, lab_pix=None, unl_pix=None, unl_truth=None):
-        import numpy as np
+    def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int,
+                 cube, lab_pix, unl_pix, unl_truth=None, a_batch: str = "batch"):
         self.eng, self.bt, self.btu, self.capacity = eng, int(bt), int(btu), int(capacity)
-        self._programmed = 0
-        if cube is None and lab_pix is None and unl_pix is None:
-            eng._refuse_split_fed()
         if lab_idx is None or unl_idx is None:
             raise ValueError("a captured step reads its rows through index buffers")
-        self._pl_truth = eng._pl_truth(unl_truth, Xu.shape[0]) if getattr(eng, "pl_block", None) is not None else None
         if lab_idx.shape[0] < bt or unl_idx.shape[0] < btu:
-            raise ValueError("index buffers shorter than one batch")
-        for name, t in (("lab_idx", lab_idx), ("unl_idx", unl_idx)):
-            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name}: need a contiguous int64 cuda vector")
-        if cube is not None or lab_pix is not None or unl_pix is not None:
-            if XPl is not None or XPu is not None:
-                raise ValueError("a cube-fed step takes no window tensors: pass XPl = XPu = None")
-            eng._check_cube_rows(cube, Xl, Y, Xu, lab_pix, unl_pix, lab_idx[:bt], unl_idx[:btu])
-        else:
-            eng._check_rows(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu])
+            raise ValueError(f"index buffers shorter than one {a_batch}")
+        # (a batch the engine does not take is refused before its tensors are looked at)
+        eng._check_batch(XPl, Xl, Y, XPu, Xu, lab_idx[:bt], unl_idx[:btu], cube, lab_pix, unl_pix)
+        _chk_idx(lab_idx, "lab_idx")
+        _chk_idx(unl_idx, "unl_idx")
+        self._pl_truth = eng._pl_truth(unl_truth, Xu.shape[0]) if eng.pl_block is not None else None
+        # the launchers set their kernels' LDS attributes on first use, which must not happen inside a capture
+        if eng.step_count == 0:
+            raise RuntimeError(f"run one eager {type(eng).__name__}.step() before capturing (kernel attributes are set lazily)")
         self._keep = (XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, cube, lab_pix, unl_pix)
         self.validate_indices()
         self.n_lab_idx, self.n_unl_idx = int(lab_idx.shape[0]), int(unl_idx.shape[0])
-        dev = eng.device
         # row 0 = the working copy the kernels read, rows 1 .. k the programmed steps, one spare row behind them
-        self.table = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8, device=dev)
-        self.cursor = torch.ones(1, dtype=torch.int32, device=dev)
+        self.table = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8, device=eng.device)
+        self.cursor = torch.ones(1, dtype=torch.int32, device=eng.device)
         self.host = torch.zeros((self.capacity + 2) * 64, dtype=torch.uint8).pin_memory()
         self.rows = self.host.numpy().view(np.dtype(_lib.DYN_DTYPE))[1:]
-        self.pending = 0
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        eng._ensure_packed(stream)
-        io = _lib.StepIO()
-        eng._fill_state(io)
-        eng._fill_io(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, self.bt, self.btu, cube, lab_pix, unl_pix)
-        io.d_scalars = eng.scalar_hist.data_ptr()          # ring base: the row comes from the table
-        io.apply_update = 1
-        io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
-        self._io = io
-        eng._captured = True
-        # the launchers set their kernels' LDS attributes on first use, which must not happen inside a capture
-        if eng.step_count == 0:
-            raise RuntimeError("run one eager TrainEngine.step() before capturing (kernel attributes are set lazily)")
-        cap = torch.cuda.Stream(device=dev)
-        cap.wait_stream(torch.cuda.current_stream(dev))
-        handle = C.c_void_p()
-        with torch.cuda.stream(cap):
-            if getattr(eng, "optim", None) is None:
-                _lib.check("cmlpl_step_graph_create", eng.lib.cmlpl_step_graph_create(
-                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.c_void_p(cap.cuda_stream), C.byref(handle)))
-            else:        # the norms ring by its base, as the scalars' ring: the row comes from the table
-                opt = eng._make_opt(eng.norm_hist.data_ptr())
-                _lib.check("cmlpl_step_graph_create_opt", eng.lib.cmlpl_step_graph_create_opt(
-                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.byref(opt), C.c_void_p(cap.cuda_stream),
-                    C.byref(handle)))
-        torch.cuda.current_stream(dev).wait_stream(cap)
-        self.handle = handle
+        self.pending = self._programmed = 0
+        self._copied = None       # event behind the last program()'s copy out of the pinned rows
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def validate_indices(self) -> None:
         """Range check of the two index buffers (synchronising): at capture, and whenever the caller has re-filled them
@@ -832,30 +816,23 @@ class StepGraph:
             raise RuntimeError(f"{self.pending} programmed steps have not been launched")
         if not 1 <= len(steps) <= self.capacity:
             raise ValueError(f"1..{self.capacity} steps per program")
-        if getattr(self, "_copied", None) is not None:
+        if self._copied is not None:
             self._copied.synchronize()        # the previous program's staging rows have left the pinned buffer
-        import numpy as np
         k = len(steps)
         st = np.asarray(steps, dtype=np.int64).reshape(k, 4)
         if (st[:, 2:] < 0).any() or (st[:, 2] + self.bt > self.n_lab_idx).any() or (st[:, 3] + self.btu > self.n_unl_idx).any():
             raise ValueError("batch offsets outside the index buffers")
-        j = np.arange(k, dtype=np.int64)
         rows = self.rows[:k]
-        rows["step"] = eng.step_count + j
-        rows["adam_t"] = eng.adam_t + 1 + j
+        for name, col in replay_counters(eng.ptr, eng.adam_t, eng.step_count, eng.Q, hp.bank_step, eng.hist_rows,
+                                         eng.method, k).items():
+            rows[name] = col
         rows["lab_off"], rows["unl_off"] = st[:, 2], st[:, 3]
-        # bank pointers BEFORE step j (train.py:234,237: ptr0 advances by the literal step, ptr1 follows ptr0)
-        p0 = (eng.ptr[0] + j * hp.bank_step) % eng.Q
-        rows["ptr"][:, 0] = p0
-        rows["ptr"][:, 1] = (p0 + hp.bank_step) % eng.Q
-        rows["ptr"][0, 1] = eng.ptr[1]
         rows["smooth"] = [1 if hp.smooth_gate(int(e), int(bi)) else 0 for e, bi in st[:, :2]]
         adap = {int(e): float(hp.thr * hp.adap_thr(int(e))) for e in np.unique(st[:, 0])}
         rows["adap_mask"] = [adap[int(e)] for e in st[:, 0]]
-        rows["hist_row"] = (eng.step_count + j) % eng.hist_rows
         a, b = C.c_float(), C.c_float()       # Adam's two scalars: formed by the library, exactly as the eager step does
         ss, bc = np.empty(k, np.float32), np.empty(k, np.float32)
-        if getattr(eng, "optim", None) is None:
+        if eng.optim is None:
             for i in range(k):
                 eng.lib.cmlpl_dyn_adam(C.byref(eng._chp), eng.adam_t + 1 + i, C.byref(a), C.byref(b))
                 ss[i], bc[i] = a.value, b.value
@@ -880,6 +857,48 @@ class StepGraph:
         self._copied = torch.cuda.Event()
         self._copied.record(torch.cuda.current_stream(eng.device))
 
+
+class StepGraph(_ReplayTable):
+    """The training step as a replayable hipGraph (SURVEY.md section 7 stage 6; ``cmlpl_step_graph_create``).
+
+    Everything that changes from step to step -- random-stream counter, Adam step, bank pointers, the train.py:212 /
+    :221 gates, the offsets of the batch inside the index buffers, the row of the logging ring -- lives in a device
+    table of ``cmlpl_dyn`` rows that ``program()`` fills for a run of steps ahead of time (an epoch, say); a device
+    cursor walks it, advanced by the step itself.  ``launch()`` is then ONE hipGraphLaunch per step: no arguments to
+    marshal, nothing else enqueued.  The engine's host-side bookkeeping advances exactly as in ``TrainEngine.step``,
+    so eager steps and replays can be mixed (an epoch's short last batch runs eagerly: its shape is not the graph's)
+    -- but only BETWEEN programs: an eager step while programmed replays are pending raises (their rows were formed
+    from the state before it).
+    """
+
+    def __init__(self, eng: TrainEngine, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt: int, btu: int, capacity: int = 1024,
+                 cube=None, lab_pix=None, unl_pix=None, unl_truth=None):
+        super().__init__(eng, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, bt, btu, capacity, cube, lab_pix, unl_pix, unl_truth)
+        dev = eng.device
+        eng._ensure_packed(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        io = _lib.StepIO()
+        eng._fill_state(io)
+        _fill_rows(io, XPl, Xl, Y, XPu, Xu, lab_idx, unl_idx, self.bt, self.btu, cube, lab_pix, unl_pix)
+        io.d_scalars = eng.scalar_hist.data_ptr()          # ring base: the row comes from the table
+        io.apply_update = 1
+        io.d_dyn_table, io.d_dyn_cursor = self.table.data_ptr(), self.cursor.data_ptr()
+        self._io = io
+        eng._captured = True
+        cap = torch.cuda.Stream(device=dev)
+        cap.wait_stream(torch.cuda.current_stream(dev))
+        handle = C.c_void_p()
+        with torch.cuda.stream(cap):
+            if eng.optim is None:
+                _lib.check("cmlpl_step_graph_create", eng.lib.cmlpl_step_graph_create(
+                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.c_void_p(cap.cuda_stream), C.byref(handle)))
+            else:        # the norms ring by its base, as the scalars' ring: the row comes from the table
+                opt = eng._make_opt(eng.norm_hist.data_ptr())
+                _lib.check("cmlpl_step_graph_create_opt", eng.lib.cmlpl_step_graph_create_opt(
+                    C.byref(eng.cshape), C.byref(eng._chp), C.byref(io), C.byref(opt), C.c_void_p(cap.cuda_stream),
+                    C.byref(handle)))
+        torch.cuda.current_stream(dev).wait_stream(cap)
+        self.handle = handle
+
     def launch(self) -> None:
         """one replay = one training step (asynchronous)"""
         eng = self.eng
@@ -891,7 +910,6 @@ class StepGraph:
         _lib.check("cmlpl_step_graph_launch", eng.lib.cmlpl_step_graph_launch(self.handle, stream))
         if eng.teacher is not None:           # one eager launch behind the replay: the captured step is what it was
             eng._teacher_update(stream)
-        eng._cur_row = eng.step_count % eng.hist_rows
         eng._advance(self.bt + self.btu, True)
         eng._last_btu = self.btu
         if eng.pl_block is not None:
@@ -907,9 +925,3 @@ class StepGraph:
         if self.handle:
             self.eng.lib.cmlpl_step_graph_destroy(self.handle)
             self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -258,7 +258,7 @@ int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets
              const float* d_packed, const XSrc& xs, const float* d_xn, const float* d_sn, const float* d_dropmask,
              float dropout_p, int train, const float* d_dlogits, const float* d_dfeat, float* d_grads,
              int64_t grad_stride, const NetWs& w, hipStream_t st, int* dyn_cursor = nullptr, cmlpl_dyn* dyn_table = nullptr,
-             int parts = 3);
+             int parts = 3, const AdamFuse* fuse = nullptr /* the Adam step rides in the reduce launch (parts == 3, no cursor) */);
 }  // namespace
 
 int cmlpl_basenet2_fwd(const cmlpl_shape* shape, int nets, int n, const float* d_params, int64_t param_stride,
@@ -386,7 +386,8 @@ namespace {
 int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets, int n, const float* d_params, int64_t param_stride,
              const float* d_packed, const XSrc& xs, const float* d_xn, const float* d_sn, const float* d_dropmask,
              float dropout_p, int train, const float* d_dlogits, const float* d_dfeat, float* d_grads,
-             int64_t grad_stride, const NetWs& w, hipStream_t st, int* dyn_cursor, cmlpl_dyn* dyn_table, int parts) {
+             int64_t grad_stride, const NetWs& w, hipStream_t st, int* dyn_cursor, cmlpl_dyn* dyn_table, int parts,
+             const AdamFuse* fuse) {
   const float* mask = (!train || dropout_p <= 0.f) ? nullptr : (d_dropmask ? d_dropmask : w.dropgen);
   int rc;
   const bool fused_head = r.bwd == ROUTE_A;
@@ -477,12 +478,15 @@ int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets
   Wgrad3Plan wp1, wp2;
   bool wpair = false;
   if (!plan_wgrad3_both(nets, n, d.H, d.W, d.H2, d.W2, true, &wp1, &wp2, &wpair)) return CMLPL_E_SHAPE;
-  reduce_table_add(rt, w.part1, wp1.G, PART3, 1, 64, d_grads + L.param_off[2], d_grads + L.param_off[3]);
-  reduce_table_add(rt, w.part2, wp2.G, PART3, 1, 64, d_grads + L.param_off[4], d_grads + L.param_off[5]);
+  if (fuse != nullptr && (parts != 3 || dyn_cursor != nullptr || fuse->gbase != d_grads)) return CMLPL_E_ARG;
+  const int el = fuse != nullptr ? REDUCE_FUSED_EL : 256;
+  reduce_table_add(rt, w.part1, wp1.G, PART3, 1, 64, d_grads + L.param_off[2], d_grads + L.param_off[3], el);
+  reduce_table_add(rt, w.part2, wp2.G, PART3, 1, 64, d_grads + L.param_off[4], d_grads + L.param_off[5], el);
   reduce_table_add(rt, w.part0, conv0_partials(d, r, n), conv0_partial_size(d.C), 0, d.C,
-                   d_grads + L.param_off[0], d_grads + L.param_off[1]);
-  // the classifier / feat_spe weight-gradient GEMMs ride along (independent, short)
-  return TIMED(CMLPL_K_CONV1_WRED, chk(launch_reduce_gemm(nets, rt, gw_cls, gw_spe, st)));
+                   d_grads + L.param_off[0], d_grads + L.param_off[1], el);
+  // the classifier / feat_spe weight-gradient GEMMs ride along (independent, short); with `fuse` so does the Adam step
+  // of every gradient element this launch forms -- all ten live tensors
+  return TIMED(CMLPL_K_CONV1_WRED, chk(launch_reduce_gemm(nets, rt, gw_cls, gw_spe, st, fuse)));
 }
 
 // 0, or the error of a malformed batch.  Split-fed (d_cube null): the four row buffers.  Cube-fed (ABI 6): the scene, its
@@ -597,7 +601,8 @@ namespace {
 int backward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_batch* batch, const cmlpl_shard* shard,
                   const float* d_params, const float* d_packed, const float* d_dropmask, int train, uint64_t seed,
                   uint64_t step, const float* d_dlogits, const float* d_dfeat, float* d_grads, int64_t grad_stride,
-                  void* d_workspace, size_t workspace_bytes, void* stream, DynRef dyn, int* dyn_cursor, int parts = 3);
+                  void* d_workspace, size_t workspace_bytes, void* stream, DynRef dyn, int* dyn_cursor, int parts = 3,
+                  const AdamFuse* fuse = nullptr);
 }  // namespace
 extern "C" {
 
@@ -627,7 +632,8 @@ namespace {
 int backward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl_batch* batch, const cmlpl_shard* shard,
                   const float* d_params, const float* d_packed, const float* d_dropmask, int train, uint64_t seed,
                   uint64_t step, const float* d_dlogits, const float* d_dfeat, float* d_grads, int64_t grad_stride,
-                  void* d_workspace, size_t workspace_bytes, void* stream, DynRef dyn, int* dyn_cursor, int parts) {
+                  void* d_workspace, size_t workspace_bytes, void* stream, DynRef dyn, int* dyn_cursor, int parts,
+                  const AdamFuse* fuse) {
   Dims d;
   cmlpl_layout_t L;
   if (!make_dims(shape, &d) || cmlpl_layout(shape, &L)) return CMLPL_E_SHAPE;
@@ -650,7 +656,7 @@ int backward_impl(const cmlpl_shape* shape, const cmlpl_hparams* hp, const cmlpl
   const XSrc xs = xsrc_plain(sw.xn, 2, n, (long long)d.C * d.HW, seed, step, shard, dyn);
   return bwd_core(d, r, L, 2, n, d_params, L.param_total, d_packed, xs,
                   copy ? sw.xn : nullptr, sw.sn, d_dropmask, hp->dropout_p, train, d_dlogits, d_dfeat, d_grads,
-                  grad_stride, nw, (hipStream_t)stream, dyn_cursor, dyn_cursor ? (cmlpl_dyn*)dyn.table : nullptr, parts);
+                  grad_stride, nw, (hipStream_t)stream, dyn_cursor, dyn_cursor ? (cmlpl_dyn*)dyn.table : nullptr, parts, fuse);
 }
 }  // namespace
 extern "C" {
@@ -1004,9 +1010,22 @@ int cmlpl_train_step_opt(const cmlpl_shape* shape, const cmlpl_hparams* hp, cons
                       io->smooth, io->adap_mask, hp, io->d_scalars, sw.dlogits, sw.dfeat, sw.probs, sw.loss,
                       loss_ws_floats(n, n, n, d.K, io->banks.Q > n ? io->banks.Q : n) * 4, stream, &sel)))
     return rc;
+  // The eager step without clipping and without a norms row: the reduce launch applies the update itself (every live
+  // gradient comes from it and Adam is elementwise), and no optimizer launch follows.  A captured step keeps two nodes:
+  // its reduce launch advances the device cursor while Adam reads the row behind it.  CMLPL_FUSE_ADAM=0: two launches.
+  AdamFuse fuse;
+  const bool fused = io->apply_update && io->adam_t >= 1 && dyn.table == nullptr && switches().fuse_adam != 0 &&
+                     (opt == nullptr || !optim_norm_wanted(opt));
+  if (fused) {
+    fuse.params = io->d_params; fuse.m = io->d_m; fuse.v = io->d_v; fuse.pstride = L.param_total; fuse.gbase = io->d_grads;
+    adam_fuse_scalars(fuse, hp->lr, hp->beta1, hp->beta2, hp->eps, io->adam_t);
+    fuse.keep = opt != nullptr ? adam_keep(hp->lr, opt->weight_decay) : 1.f;
+    fuse.packed = io->d_packed; fuse.pi = make_pack_info(d, L);
+  }
   if ((rc = backward_impl(shape, hp, &batch, &sh, io->d_params, io->d_packed, io->d_dropmask, train, io->seed,
                           io->step, sw.dlogits, cps ? nullptr : sw.dfeat, io->d_grads, L.param_total, io->d_workspace,
-                          io->workspace_bytes, stream, dyn, io->d_dyn_cursor))) return rc;
+                          io->workspace_bytes, stream, dyn, io->d_dyn_cursor, 3, fused ? &fuse : nullptr))) return rc;
+  if (fused) return 0;
   if (io->apply_update)   // (device-side scalars: the by-value step count is not used, any valid one will do)
     return adam_impl(shape, 2, io->d_params, L.param_total, io->d_grads, L.param_total, io->d_m, io->d_v,
                      (dyn.table != nullptr && io->adam_t < 1) ? 1 : io->adam_t, hp, io->d_packed, stream, dyn, opt);

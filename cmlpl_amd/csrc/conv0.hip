@@ -454,19 +454,201 @@ __global__ __launch_bounds__(256) void reduce_gemm_kernel(ReduceTable t, int red
   else gemm_tn_block(g, bid - reduce_blocks, sh);
 }
 
-hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st) {
+// ---- the fold with the Adam step behind it (the eager, unclipped training step: no optimizer launch follows)
+// One block = REDUCE_FUSED_EL = 512 consecutive partial elements x 4 slices of g: a thread owns TWO float4 columns
+// (el and el + 64), each summed exactly as partial_reduce_block sums its one -- the slice sl, g0 in steps of 32 with
+// eight loads per group, then the four-slice fold: the block size does not enter the order, `grads` keeps its bits.
+// Behind the LDS fold the 256 threads share the 512 elements: each stores two sums to `grads`, updates m / v / p of
+// those two (loaded in front of the partial loop, so the update adds no round trip to the block's chain) and
+//   mode 1, body (one tap, 8 ci, 64 co): the updated weights meet in LDS and leave as whole 16-byte forward pieces
+//     (8 ci of one (co, tap): 64 items) and 8-byte data-gradient pieces (4 co of one (ci, tap): 128 items) of both
+//     packed families, as adam_conv_chunk writes them;
+//   mode 0, body: w0T and the conv0 bf16 fragment, element by element as adam_kernel's elementwise part;
+//   the bias tails: nothing packed.
+// The sums lie in LDS as float4 columns with the column index swizzled by the ci row (col ^ 2 * (col >> 4)): a mode-1
+// wave then reads 8 ci x 8 co (a co's 8 ci lie within 256 bytes of m / v / p / grads: 3 cache lines per co where a
+// wave of 64 co touches 64) without bank conflicts.
+__device__ __forceinline__ int red_swz(int col) { return col ^ (((col >> 4) & 7) << 1); }
+
+__device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, int net, float* sm, const AdamFuse& f) {
+  int pi = 0;
+  if (t.count > 1 && bx >= t.p[1].blk0) pi = 1;
+  if (t.count > 2 && bx >= t.p[2].blk0) pi = 2;
+  const ReduceProb pr = t.p[pi];
+  const int tid = threadIdx.x, lane = tid & 63, el = lane, sl = tid >> 6;
+  const int G = pr.G, PS = pr.PS, body = PS - 64;
+  const int eb = (bx - pr.blk0) * REDUCE_FUSED_EL;     // first partial element of the block
+  const bool conv3 = pr.mode == 1 && eb < body;         // a whole (tap, 8 ci, 64 co) unit: 36864 = 72 x 512
+  const long long offW = pr.dW - f.gbase, offB = pr.db - f.gbase;
+  // this thread's two elements: unit-local index u, parameter offset po inside the network (-1: none)
+  int u[2];
+  long long po[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (conv3) {
+      const int cil = lane & 7, co = (sl * 2 + q) * 8 + (lane >> 3);
+      u[q] = cil * 64 + co;
+      const int e = eb + u[q];
+      po[q] = offW + co * 576 + ((e >> 6) & 63) * 9 + (e >> 12);
+    } else {
+      u[q] = tid + 256 * q;
+      const int e = eb + u[q];
+      if (e >= PS) po[q] = -1;
+      else if (e >= body) po[q] = offB + (e - body);
+      else if (pr.mode == 1) po[q] = offW + (e & 63) * 576 + ((e >> 6) & 63) * 9 + (e >> 12);
+      else po[q] = (e >> 6) < pr.C ? offW + (long long)(e & 63) * pr.C + (e >> 6) : -1;
+    }
+  }
+  float* const pp = f.params + (long long)net * f.pstride;
+  float* const pm = f.m + (long long)net * f.pstride;
+  float* const pv = f.v + (long long)net * f.pstride;
+  float mq[2], vq[2], pq[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const long long o = po[q] < 0 ? 0 : po[q];
+    mq[q] = pm[o]; vq[q] = pv[o]; pq[q] = pp[o];
+  }
+  // the partial sums of the two columns
+  const float* p[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int e0 = eb + (el + 64 * c) * 4;
+    p[c] = pr.part + (long long)net * G * PS + (e0 < PS ? e0 : 0);
+  }
+  float4 s0[2], s1[2];
+  s0[0] = s0[1] = s1[0] = s1[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int g0 = sl; g0 < G; g0 += 32) {
+    float4 v[2][8];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int g = g0 + 4 * q;
+        // rows past G read row 0 and are masked to +0.0f by an AND whose mask goes through an empty asm: given a select
+        // on the loaded value, hipcc sinks each load under a branch with a full wait behind it, and the sixteen loads
+        // of a group run one after the other (32 us for the launch instead of 12)
+        uint32_t keep = g < G ? 0xffffffffu : 0u;
+        asm volatile("" : "+v"(keep));
+        const float4 x = *(const float4*)(p[c] + (size_t)(g < G ? g : 0) * PS);
+        v[c][q] = make_float4(__uint_as_float(__float_as_uint(x.x) & keep), __uint_as_float(__float_as_uint(x.y) & keep),
+                              __uint_as_float(__float_as_uint(x.z) & keep), __uint_as_float(__float_as_uint(x.w) & keep));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+#define CMLPL_ADD4(F) s0[c].F += (v[c][0].F + v[c][1].F) + (v[c][2].F + v[c][3].F); s1[c].F += (v[c][4].F + v[c][5].F) + (v[c][6].F + v[c][7].F);
+      CMLPL_ADD4(x) CMLPL_ADD4(y) CMLPL_ADD4(z) CMLPL_ADD4(w)
+#undef CMLPL_ADD4
+    }
+  }
+  float4* red4 = (float4*)sm;                          // [4 slices][128 columns, swizzled] float4 = 8 KB
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+    red4[sl * 128 + red_swz(el + 64 * c)] = make_float4(s0[c].x + s1[c].x, s0[c].y + s1[c].y, s0[c].z + s1[c].z, s0[c].w + s1[c].w);
+  __syncthreads();
+  float* const wl = sm + 2048;                         // mode 1: the unit's updated weights, [co][9: 8 ci + a pad]
+  float* const gr = const_cast<float*>(f.gbase) + (long long)net * t.grad_ns;
+  float* const pkn = f.packed + (long long)net * f.pi.stride;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (po[q] < 0) continue;
+    const int w = 4 * red_swz(u[q] >> 2) + (u[q] & 3);
+    const float sum = (sm[w] + sm[512 + w]) + (sm[1024 + w] + sm[1536 + w]);
+    gr[po[q]] = sum;
+    const float pn = conv3 ? adam_update<true, true>(mq[q], vq[q], pq[q], sum, f, 1.f, f.keep)
+                           : adam_update<true, false>(mq[q], vq[q], pq[q], sum, f, 1.f, f.keep);
+    pm[po[q]] = mq[q]; pv[po[q]] = vq[q]; pp[po[q]] = pn;
+    if (conv3) {
+      wl[(u[q] & 63) * 9 + (u[q] >> 6)] = pn;
+    } else if (pr.mode == 0 && eb + u[q] < body) {     // conv0.weight[co][c] -> w0T[c][co] + the bf16 fragment
+      const int e = eb + u[q], c = e >> 6, co = e & 63;
+      pkn[pack_off_w0t() + c * 64 + co] = pn;
+      uint32_t pcs[3];
+      b3_split(pn, pcs);
+      uint16_t* wb = (uint16_t*)(pkn + pack_off_w0b3(f.pi.C, f.pi.bands));
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) wb[conv_b3_index(0, c, co, pc)] = (uint16_t)pcs[pc];
+    }
+  }
+  if (!conv3) return;                                  // (block-uniform)
+  __syncthreads();
+  const int which = (offW == f.pi.off_w2) ? 2 : 0, tap = eb >> 12, ci0 = (eb >> 6) & 63;
+  static_assert(H2_WEXP == 13, "h2_split_w scales by 2^13");
+  bool bad = false;
+  if (tid < 64) {
+    // forward sets, as 8-element pieces: item = co -> ci = ci0 .. ci0 + 7 of this tap
+    const int co = tid;
+    uint4* bf = (uint4*)(pkn + pack_off_b3(f.pi.C, f.pi.bands, which));
+    uint4* hf = (uint4*)(pkn + pack_off_h2(f.pi.C, f.pi.bands, which));
+    uint32_t pc[8][3], ph[8][2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float w = wl[co * 9 + j];
+      b3_split(w, pc[j]);
+      bad |= h2_split_w(w, ph[j]);
+    }
+#pragma unroll
+    for (int pcs = 0; pcs < 3; ++pcs)
+      bf[conv_b3_index(tap, ci0, co, pcs) >> 3] =
+          make_uint4(pc[0][pcs] | (pc[1][pcs] << 16), pc[2][pcs] | (pc[3][pcs] << 16),
+                     pc[4][pcs] | (pc[5][pcs] << 16), pc[6][pcs] | (pc[7][pcs] << 16));
+#pragma unroll
+    for (int pcs = 0; pcs < 2; ++pcs)
+      hf[conv_h2_index(tap, ci0, co, pcs) >> 3] =
+          make_uint4(ph[0][pcs] | (ph[1][pcs] << 16), ph[2][pcs] | (ph[3][pcs] << 16),
+                     ph[4][pcs] | (ph[5][pcs] << 16), ph[6][pcs] | (ph[7][pcs] << 16));
+  } else if (tid < 64 + 128) {
+    // data-gradient sets (k = co, n = ci, tap flipped), as 4-element pieces: item = (ci, co quad)
+    const int it = tid - 64, co0 = (it & 15) * 4, cil = it >> 4, ci = ci0 + cil;
+    uint2* bd = (uint2*)(pkn + pack_off_b3(f.pi.C, f.pi.bands, which + 1));
+    uint2* hd = (uint2*)(pkn + pack_off_h2(f.pi.C, f.pi.bands, which + 1));
+    uint32_t pc[4][3], ph[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float w = wl[(co0 + j) * 9 + cil];
+      b3_split(w, pc[j]);
+      bad |= h2_split_w(w, ph[j]);
+    }
+#pragma unroll
+    for (int pcs = 0; pcs < 3; ++pcs)
+      bd[conv_b3_index(8 - tap, co0, ci, pcs) >> 2] = make_uint2(pc[0][pcs] | (pc[1][pcs] << 16), pc[2][pcs] | (pc[3][pcs] << 16));
+#pragma unroll
+    for (int pcs = 0; pcs < 2; ++pcs)
+      hd[conv_h2_index(8 - tap, co0, ci, pcs) >> 2] = make_uint2(ph[0][pcs] | (ph[1][pcs] << 16), ph[2][pcs] | (ph[3][pcs] << 16));
+  }
+  if (bad) atomicOr((unsigned int*)(pkn + pack_off_h2flag(f.pi.C, f.pi.bands)), 1u);
+}
+
+__global__ __launch_bounds__(256) void reduce_gemm_adam_kernel(ReduceTable t, int reduce_blocks, GemmTN2 g, AdamFuse f) {
+  __shared__ GemmTNShared sh;
+  __shared__ float x0[16][64];                         // the GEMM tiles' fourth accumulator set (gemm_tn.hpp, UPD)
+  const int bid = (int)blockIdx.x;
+  if (bid < reduce_blocks) reduce_adam_block(t, bid % t.total_blocks, bid / t.total_blocks, &sh.red[0][0][0], f);   // 10.3 KB of the 12 KB
+  else gemm_tn_block<true>(g, bid - reduce_blocks, sh, &f, x0);
+}
+
+hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st,
+                              const AdamFuse* fu) {
   GemmTN2 g;
   g.p[0] = g0; g.p[1] = g1; g.nblk0 = gemm_tn_blocks(g0);
   const int rb = t.total_blocks * nets, gb = g.nblk0 + gemm_tn_blocks(g1);
-  hipLaunchKernelGGL(reduce_gemm_kernel, dim3(rb + gb), dim3(256), 0, st, t, rb, g);
+  if (fu != nullptr) {
+    // the update needs what only the eager step has: no device cursor to advance, 512-element blocks, all in one buffer
+    if (t.dyn_cursor != nullptr) return hipErrorInvalidValue;
+    for (int i = 0; i < t.count; ++i)
+      if (t.p[i].el != REDUCE_FUSED_EL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(reduce_gemm_adam_kernel, dim3(rb + gb), dim3(256), 0, st, t, rb, g, *fu);
+  } else {
+    hipLaunchKernelGGL(reduce_gemm_kernel, dim3(rb + gb), dim3(256), 0, st, t, rb, g);
+  }
   return hipGetLastError();
 }
 
-void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db) {
+void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, int el) {
   ReduceProb& p = t.p[t.count++];
   p.part = part; p.dW = dW; p.db = db; p.G = G; p.PS = PS; p.mode = mode; p.C = C; p.blk0 = t.total_blocks;
-  p.el = 256;
-  t.total_blocks += (PS + 255) / 256;
+  p.el = el;
+  t.total_blocks += (PS + el - 1) / el;
 }
 
 hipError_t launch_partial_reduce(int nets, const ReduceTable& t, hipStream_t st) {

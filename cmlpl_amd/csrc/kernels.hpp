@@ -198,10 +198,25 @@ int plan_conv0_wgrad_G(int n, int C, int HW);
 struct ReduceProb { const float* part; float* dW; float* db; int G, PS, mode, C, blk0, el; };
 struct ReduceTable { ReduceProb p[3]; int count, total_blocks; long long grad_ns;
                      int* dyn_cursor; cmlpl_dyn* dyn_table; /* graph replay: cursor advanced by 1, next row -> table[0]; or null */ };
-void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db);
+// el: partial elements per block -- 256, or REDUCE_FUSED_EL for a table that launch_reduce_gemm runs with an update
+constexpr int REDUCE_FUSED_EL = 512;         // one tap x 8 ci x 64 co of a 3x3 tensor: whole 16-byte / 8-byte packed pieces
+void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, int el = 256);
 hipError_t launch_partial_reduce(int nets, const ReduceTable& t, hipStream_t st);
 struct GemmTN;
-hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st);
+// The Adam step of an eager, unclipped training step, applied by the workgroup that forms a gradient element right
+// behind the store of that element (no optimizer launch follows): every dW / db / C / bias of the launch lies inside the
+// flat gradient buffer gbase ([nets][gstride]), and gradient element gbase[net * gstride + o] belongs to
+// params / m / v [net * pstride + o].  Filled by adam_fuse_scalars (optim.hip) + the caller.
+struct AdamFuse {
+  float* params; float* m; float* v; long long pstride;
+  const float* gbase;
+  float w1, b2, w2, step_size, bc2_sqrt, eps;
+  float keep;                                // the decay factor (1: none); the clip coefficient of this path is 1
+  float* packed; PackInfo pi;
+};
+// fu != null: the table was built with el = REDUCE_FUSED_EL, and the update rides in the launch
+hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st,
+                              const AdamFuse* fu = nullptr);
 // a conv0 weight-gradient partial: [rows = C rounded up to 4][64 co] + 64 bias sums (rounds 1-3 kept whole 32-band tiles:
 // at 103 bands a fifth of the partial bytes -- written by every sample-net, re-read by the reduce -- were padding)
 __host__ __device__ inline int conv0_partial_rows(int C) { return (C + 3) & ~3; }
@@ -269,6 +284,7 @@ struct Switches {
   int dfeat_lds;                                              // CMLPL_DFEAT_LDS (-1 = wherever the operands allow, 0 = never)
   int mb_fast, unsup_onewg, unsup_3l, ntx_mfma;               // CMLPL_MB_FAST, CMLPL_UNSUP_ONEWG, CMLPL_UNSUP_3L, CMLPL_NTX_MFMA (default 1)
   int ntx_ncw;                                                // CMLPL_NTX_NCW: 1 / 2 / 4 = 64 / 128 / 256 embedding columns per workgroup of the NT-Xent gradient (0 = planner)
+  int fuse_adam;                                              // CMLPL_FUSE_ADAM: 0 = the gradient fold and the optimizer as two launches everywhere (default 1: one launch in the eager, unclipped training step)
 };
 inline Switches read_switches() {
     auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
@@ -286,6 +302,7 @@ inline Switches read_switches() {
     w.dfeat_lds = env("CMLPL_DFEAT_LDS", -1);
     w.mb_fast = env("CMLPL_MB_FAST", 1); w.unsup_onewg = env("CMLPL_UNSUP_ONEWG", 1); w.unsup_3l = env("CMLPL_UNSUP_3L", 1);
     w.ntx_mfma = env("CMLPL_NTX_MFMA", 1); w.ntx_ncw = env("CMLPL_NTX_NCW", 0);
+    w.fuse_adam = env("CMLPL_FUSE_ADAM", 1);
     return w;
 }
 // the process's table: filled on first use; cmlpl_debug_reload_switches (tests: one process walks several settings)
@@ -393,6 +410,7 @@ hipError_t launch_grad_norm_fin(int nets, const double* partials, float max_norm
                                 DynRef dyn = DynRef());
 size_t grad_norm_partials_bytes();
 void adam_bias_scalars(float lr, float b1, float b2, long long t, float* step_size, float* bc2_sqrt);
+void adam_fuse_scalars(AdamFuse& f, float lr, float b1, float b2, float eps, long long t);   // the six scalars, as launch_adam forms them
 
 // ---- ema.hip  (the weight average of reference tools/models.py:155-164: ema = fl(fl(src * oma) + fl(ema * alpha)))
 hipError_t launch_ema(const float* src, float* ema, long long count, float alpha, float oma, hipStream_t st);

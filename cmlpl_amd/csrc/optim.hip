@@ -3,6 +3,7 @@
 // the reference where their grad is None).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "gemm_tn.hpp"
 
 #ifndef CMLPL_ABL
 #define CMLPL_ABL 0
@@ -82,36 +83,7 @@ __global__ __launch_bounds__(64) void grad_norm_fin_kernel(const double* partial
   }
 }
 
-// ONE rounded fp32 multiply whose result the compiler may not fuse into what follows (a * b - c would otherwise become
-// one fma, and x * 1.0f would no longer leave the update the bits of the plain one): the product goes through an empty
-// asm, after which the update sees it as it sees a loaded value
-__device__ __forceinline__ float mul_alone(float a, float b) {
-  float r = a * b;
-  asm volatile("" : "+v"(r));
-  return r;
-}
-
-// CHUNK: called from adam_conv_chunk (the elementwise part otherwise) -- it matters to the variant only
-template <bool OPT, bool CHUNK>
-__device__ __forceinline__ float adam_update(float& mm, float& vv, float p, float g, const AdamArgs& a, float coef, float keep) {
-  if (OPT) {
-    g = mul_alone(g, coef);                              // clip_grad_norm_: grad.mul_(coef)
-    p = mul_alone(p, keep);                              // AdamW: param.mul_(1 - lr * weight_decay)
-    // The plain instantiation below leaves the fusing of its products into fmas to the compiler, which has two ways to
-    // fuse v's sum of two products and takes one in the chunk workgroups (the square is fused) and the other in the
-    // elementwise part (the decay of v is fused).  The variant spells out the same fmas, so that coef == keep == 1.0f
-    // leaves the plain step's bits (tests/test_gpu_optim.py holds the two instantiations to each other).
-    mm = fmaf(a.w1, g - mm, mm);
-    vv = CHUNK ? fmaf(g, a.w2 * g, vv * a.b2) : fmaf(vv, a.b2, (a.w2 * g) * g);
-    const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
-    return fmaf(-a.step_size, mm / denom, p);
-  }
-
-  mm = mm + a.w1 * (g - mm);                             // exp_avg.lerp_(grad, 1-beta1)
-  vv = vv * a.b2 + (a.w2 * g) * g;                       // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
-  const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
-  return p - a.step_size * (mm / denom);                 // param.addcdiv_(exp_avg, denom, -step_size)
-}
+// (mul_alone and adam_update<OPT, CHUNK>: gemm_tn.hpp -- the fused gradient fold of conv0.hip runs the same update)
 // (this launch runs behind the cursor's advance: its row is the one before the cursor)
 __device__ __forceinline__ void adam_dyn(AdamArgs& a) {
   const cmlpl_dyn* d = dyn_row(a.dyn, -1);
@@ -302,6 +274,11 @@ hipError_t launch_adam(int nets, float* params, long long pstride, const float* 
     hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, st, a);
   }
   return hipGetLastError();
+}
+
+void adam_fuse_scalars(AdamFuse& f, float lr, float b1, float b2, float eps, long long t) {
+  adam_bias_scalars(lr, b1, b2, t, &f.step_size, &f.bc2_sqrt);
+  f.w1 = (float)(1.0 - (double)b1); f.b2 = b2; f.w2 = (float)(1.0 - (double)b2); f.eps = eps;
 }
 
 float adam_keep(float lr, float weight_decay) { return (float)(1.0 - (double)lr * (double)weight_decay); }

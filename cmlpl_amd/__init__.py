@@ -7,6 +7,8 @@ Public surface:
   ensemble_logits / _cube / _pixels ... averaged probabilities, label, confidence, entropy of 1..4 networks
   TTA, tta_cube / tta_pixels, views_of ... the same from several noisy views per pixel (test-time augmentation)
   Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
+  Superpixel, segment, region_vote, superpixel_probs, asa, segment_host, region_vote_host ... superpixels: segment the scene,
+                                 vote per region
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
   Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
   embed, KnnEvaluator, KnnResult, knn_host (cmlpl_amd.knn.knn: the vote itself) ... kNN evaluation of the spectral embedding
@@ -34,6 +36,10 @@ def __getattr__(name):
     if name in ("Smooth", "smooth_probs", "smooth_cube"):
         from . import smooth
         return getattr(smooth, name)
+    if name in ("Superpixel", "Segments", "RegionVote", "segment", "region_vote", "superpixel_probs", "asa", "segment_host",
+                "region_vote_host"):
+        from . import superpixel
+        return getattr(superpixel, name)
     if name in ("PLCounts", "pl_stats_host", "pl_stats_hard_host"):
         from . import plstats
         return getattr(plstats, name)

@@ -53,6 +53,8 @@ EXPORTS = (
     "cmlpl_grad_norm_partials_bytes", "cmlpl_grad_norm", "cmlpl_adam_step_opt", "cmlpl_train_step_opt",   # added after ABI 6, no bump:
     "cmlpl_step_graph_create_opt", "cmlpl_dyn_adam_opt",                         # schedules, weight decay, gradient clipping
     "cmlpl_lp_graph_bytes", "cmlpl_lp_graph", "cmlpl_lp_propagate",              # added after ABI 6, no bump: label propagation
+    "cmlpl_sp_workspace_bytes", "cmlpl_sp_segment", "cmlpl_sp_vote_workspace_bytes",                 # added after ABI 6, no bump:
+    "cmlpl_sp_vote_probs", "cmlpl_sp_vote_labels",                               # superpixels and region votes
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -342,6 +344,13 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_lp_graph_bytes.restype = sz
     lib.cmlpl_lp_graph.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp]
     lib.cmlpl_lp_propagate.argtypes = [vp, i32, i32, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cmlpl_sp_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.cmlpl_sp_workspace_bytes.restype = sz
+    lib.cmlpl_sp_segment.argtypes = [vp, i64, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, sz, vp]
+    lib.cmlpl_sp_vote_workspace_bytes.argtypes = [i32, i32]
+    lib.cmlpl_sp_vote_workspace_bytes.restype = sz
+    lib.cmlpl_sp_vote_probs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.cmlpl_sp_vote_labels.argtypes = lib.cmlpl_sp_vote_probs.argtypes
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]
@@ -352,7 +361,8 @@ def load(path: str = LIB_PATH):
                      "cmlpl_unsup_workspace_bytes", "cmlpl_source_hash", "cmlpl_infer_workspace_bytes",
                      "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes",
                      "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes", "cmlpl_knn_workspace_bytes",
-                     "cmlpl_grad_norm_partials_bytes", "cmlpl_lp_graph_bytes"):
+                     "cmlpl_grad_norm_partials_bytes", "cmlpl_lp_graph_bytes", "cmlpl_sp_workspace_bytes",
+                     "cmlpl_sp_vote_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

@@ -1294,6 +1294,85 @@ int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float* d_Y /* [n
                        float* d_conf /* [n] or NULL */, float* d_entropy /* [n] or NULL */,
                        float* d_residual /* [1] or NULL */, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- SUPERPIXELS AND REGION VOTES: object-based classification.  The
+ * scene is over-segmented into superpixels (SLIC, Achanta et al. 2012, in its per-pixel GPU form gSLIC, Ren & Reid 2011),
+ * every region votes, and the region is labelled as one.  The reference has no counterpart: each of its labels is the
+ * product of a single window.
+ *
+ * THE DEFINITION OF A SUPERPIXEL MAP.
+ *   Inputs.  A scene of rows x cols pixels, i = y cols + x.  Guide g[i][0 .. G - 1] = the first G floats at d_guide + i
+ *     guide_stride, 0 <= G <= 8.  Grid step S, 2 .. 64.  Compactness m, finite and > 0.  Iterations T, 1 .. 100.
+ *     w = fl32(m^2 / S^2), formed in double on the host from the fp32 m; it must be finite and > 0.
+ *   Cells and centres.  ny = ceil(rows / S), nx = ceil(cols / S), N = ny nx segments; N >= 2^24 is refused.  Segment
+ *     s = a nx + b is cell (a, b).  A pixel is REGULAR when every guide channel is finite and |g| <= 2^20; with G = 0 every
+ *     pixel is regular.  Initial centre c_s = (cy, cx, g..): cy = (float)min(rows - 1, a S + S / 2) and cx likewise, with
+ *     integer division; the guide part is that pixel's guide, or all zeros if that pixel is irregular.
+ *   Assign (per pixel, from centres c^(t-1)).  Candidates are the cells (y / S + da, x / S + db) for da, db in -1, 0, 1
+ *     that lie inside the grid, scanned da ascending and, within da, db ascending.  Per candidate, in this order:
+ *       dc2 = 0;  for ch ascending:  d = g[ch] - c[ch];  dc2 = fmaf(d, d, dc2)
+ *       dy = (float)y - cy,  dx = (float)x - cx
+ *       ds2 = fmaf(dx, dx, fl(dy dy))
+ *       D = fmaf(ds2, w, dc2)
+ *     Every operation is rounded once; nothing else is contracted.  The label is the candidate with the smallest D under
+ *     strict <, starting from best = +inf and label = the pixel's own cell: a tie keeps the earlier candidate, a NaN or
+ *     +inf D never wins.  An irregular pixel computes nothing and keeps its own cell.
+ *   Update.  Over the regular pixels of segment s accumulate int64 n, Sy, Sx and Sg[ch] = sum llrintf(g[ch] * 2^24) (the
+ *     product is exact).  For n > 0: cy = (float)((double)Sy / (double)n), cx likewise, c[ch] = (float)((double)Sg[ch] /
+ *     ((double)n * 16777216.0)).  For n == 0 the centre stays what it was.  All sums are integers, so the result does not
+ *     depend on any order.
+ *   Iteration.  For t = 1 .. T: assign, then update.  Outputs: seg int32 [rows cols] from the T-th assignment; centres
+ *     float [N][2 + G] after the T-th update; counts int32 [N], the regular pixels per segment.
+ *   Consequence.  A segment's pixels lie inside its 3 x 3 block of cells, so n <= 9 S^2: no int64 can overflow, and an
+ *     implementation may gather per segment in place of scattering per pixel.
+ *   Not built: moving the seeds to the lowest gradient, and SLIC's connectivity post-pass -- small detached fragments can
+ *     exist; they are confined to a 3 x 3 cell block.
+ *
+ * THE DEFINITION OF A REGION VOTE.
+ *   Inputs.  Any int32 map seg[n], N, K <= 64, and one of two sources.
+ *   Soft source.  Probabilities p[n][K]; a row is valid when every entry is finite and 0 <= p <= 2.  P[s][c] = sum
+ *     llrintf(p[i][c] * 2^24) over the valid rows with 0 <= seg[i] < N, cnt[s] their number, q[s][c] = (float)((double)
+ *     P[s][c] / ((double)cnt[s] * 16777216.0)).
+ *   Hard source.  int64 labels l[n]; a row is valid when 0 <= l < K (and 0 <= seg[i] < N); P[s][c] counts rows, q[s][c] =
+ *     (float)((double)P / (double)cnt).
+ *   Per segment, by cmlpl_ensemble's rules: label = the FIRST maximum of q; conf = q[label]; entropy = 0 - sum_c q_c
+ *     logf(q_c), c ascending, 0 log 0 = 0.  A segment with cnt == 0 gets label -1 and NaN for q / conf / entropy (cmlpl_knn's
+ *     rule for an unreached row).
+ *   Broadcast.  Pixel i takes its segment's label, q, conf and entropy -- an invalid row inside a voted segment is repaired
+ *     by its region; a pixel with seg[i] outside 0 .. N - 1 gets -1 and NaNs.
+ *   Optional outputs: int64 P[N][K], int64 cnt[N], the per-segment table q[N][K] and the segment labels int64 [N].
+ *   ASA (achievable segmentation accuracy): hard-vote a truth map -- the scene's labels at the listed test pixels, -1
+ *     everywhere else, so those rows are invalid and left out; ASA = sum_s max_c P[s][c] / sum_s cnt[s], host arithmetic
+ *     on P.  It is the best overall accuracy ANY region-level labelling of the map could reach.
+ *
+ * cmlpl_sp_workspace_bytes(rows, cols, G, S) = 4 (N (2 + G) + G n) + n rounded up to 4, n = rows cols: the centres, the
+ *   guide packed planar [G][n] once per call, and a regular-pixel byte per pixel; 0 for arguments outside the ranges.
+ * cmlpl_sp_segment: pack, init, then T times assign (a workgroup per tile of 32 x 8 pixels, its candidate centres staged in
+ *   LDS) and update (one wavefront gathers a segment's clipped 3S x 3S block: no atomics, no memset).  d_seg [rows cols];
+ *   d_centres [N][2 + G] and d_counts [N] each or NULL.  The result does not depend on the workspace's prior contents.
+ *   CMLPL_E_ARG before any launch: rows or cols < 1 (or rows cols past 2^31 - 1), G outside 0 .. 8, S outside 2 .. 64,
+ *   N >= 2^24, iters outside 1 .. 100, m not finite or <= 0, w not finite or zero, G > 0 with a null d_guide or guide_stride
+ *   < G, a null d_seg or d_ws, a misaligned pointer (4 bytes), ws_bytes < cmlpl_sp_workspace_bytes.
+ * cmlpl_sp_vote_workspace_bytes(N, K) = 12 N (K + 2): int64 P [N][K], cnt [N], segment labels [N]; float q [N][K], conf
+ *   [N], entropy [N]; 0 for N < 1, K outside 1 .. 64 or N K past 2^31 - 1.
+ * cmlpl_sp_vote_probs / cmlpl_sp_vote_labels: a memset node over P and cnt, the accumulation (64-bit INTEGER atomics; a run
+ *   of neighbouring lanes with one segment id is summed inside the wave first), one finishing launch per segment, and a
+ *   broadcast launch when a per-pixel output is asked for (d_out_probs [n][K], d_labels [n] int64, d_conf, d_entropy [n],
+ *   each or NULL); d_sums int64 [N][K], d_cnt int64 [N], d_seg_probs [N][K], d_seg_labels int64 [N], each or NULL.
+ *   CMLPL_E_ARG before any launch: n or N < 1, K outside 1 .. 64, N K past 2^31 - 1, a null d_seg / source / d_ws, every
+ *   output null, a misaligned pointer (8 bytes for int64 arrays and the workspace, else 4), ws_bytes too small.
+ * Nothing allocates or synchronises; everything can be captured in a graph.  No float atomics: every output is the same
+ * bytes on every run. */
+size_t cmlpl_sp_workspace_bytes(int rows, int cols, int G, int S);
+int cmlpl_sp_segment(const float* d_guide, int64_t guide_stride, int G, int rows, int cols, int S, float m, int iters,
+                     int32_t* d_seg, float* d_centres, int32_t* d_counts, void* d_ws, size_t ws_bytes, void* stream);
+size_t cmlpl_sp_vote_workspace_bytes(int N, int K);
+int cmlpl_sp_vote_probs(const int32_t* d_seg, const float* d_probs, int n, int K, int N, float* d_out_probs,
+                        int64_t* d_labels, float* d_conf, float* d_entropy, int64_t* d_sums, int64_t* d_cnt,
+                        float* d_seg_probs, int64_t* d_seg_labels, void* d_ws, size_t ws_bytes, void* stream);
+int cmlpl_sp_vote_labels(const int32_t* d_seg, const int64_t* d_src_labels, int n, int K, int N, float* d_out_probs,
+                         int64_t* d_labels, float* d_conf, float* d_entropy, int64_t* d_sums, int64_t* d_cnt,
+                         float* d_seg_probs, int64_t* d_seg_labels, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,14 @@ single network.  No label map is written: the vote is over the test list, not th
 propagation over its kNN graph (cmlpl_amd.labelprop) -- the nodes are the labelled training pixels, which are the seeds (the
 gallery of ``--knn_gallery train``), followed by the labelled test pixels.  Per network of ``--net`` one line ``propagate<tag>: nodes=..
 edges=.. max_in_degree=.. unreached=.. residual=..`` and a ``Result:`` block with the tag ``_lp`` scored on the test pixels (one the seeds
-do not reach counts as wrong); ``--reliability`` prints its line behind it.  With ``--knn`` both appear: ``_knn`` first, then ``_lp``."""
+do not reach counts as wrong); ``--reliability`` prints its line behind it.  With ``--knn`` both appear: ``_knn`` first, then ``_lp``.
+``--superpixel S`` classifies REGIONS: the scene is over-segmented into superpixels on a grid of step S under the cube's leading
+channels and every region votes with the class probabilities of its pixels (cmlpl_amd.superpixel; ``--sp_compact`` / ``--sp_iters`` /
+``--sp_guide`` / ``--sp_vote soft | hard``), with any single network or ensemble, with or without ``--tta``, behind ``--smooth`` when
+given and in front of ``--temperature``: one line ``superpixel: segments=.. empty=.. mean_size=.. max_size=.. ASA=..`` (ASA: the
+accuracy on the labelled test pixels that no region-level labelling of this map can exceed), a further ``Result:`` block with
+``_sp`` appended to the tag, and ``--out`` / ``--proba`` / ``--confidence`` / ``--entropy`` describe the last stage.  ``--save_segments
+FILE`` writes the int32 segment map."""
 import argparse
 import os
 
@@ -52,9 +59,9 @@ import torch
 
 from cmlpl_amd import checkpoint
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SPATIAL_MODES, SYNTH, RelScore, add_propagate_flags, add_smooth_flags,
-                   calibration_split, ensemble_whole, evaluate_whole, propagate_nodes, propagate_of, smooth_of, smooth_whole,
-                   temper_stage, tta_tag, tta_whole)
+from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SP_TAG, SPATIAL_MODES, SYNTH, RelScore, add_propagate_flags, add_smooth_flags,
+                   add_superpixel_flags, calibration_split, ensemble_whole, evaluate_whole, propagate_nodes, propagate_of,
+                   smooth_of, smooth_whole, superpixel_of, superpixel_whole, temper_stage, tta_tag, tta_whole)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
@@ -108,6 +115,13 @@ def check_args(args):
     if smooth_of(args) is not None and args.net in ('both', 'ema_both'):
         raise SystemExit("--smooth gives ONE prediction: --net %s writes two label maps (name one network, or --net "
                          "ensemble for the two together)" % args.net)
+    if superpixel_of(args) is not None:
+        if args.net in ('both', 'ema_both'):
+            raise SystemExit("--superpixel gives ONE prediction: --net %s writes two label maps (name one network, or --net "
+                             "ensemble for the two together)" % args.net)
+        if args.knn is not None or args.embed or getattr(args, 'propagate', False):
+            raise SystemExit("--superpixel votes over the scene's map: --knn / --embed / --propagate describe the labelled test "
+                             "pixels, a list without a map")
 
 
 def check_knn_args(args):
@@ -276,7 +290,7 @@ def main(args, device=None):
         if args.save_reliability and (args.knn is not None or propagate):
             score.save(args.save_reliability)
         return out
-    smooth, tta = smooth_of(args), None
+    smooth, sp, tta = smooth_of(args), superpixel_of(args), None
     if args.tta is not None:
         from cmlpl_amd.tta import TTA
         tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
@@ -297,9 +311,16 @@ def main(args, device=None):
         if args.reliability:
             score = calib['score'] = RelScore(test_array, Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins, held)
         if temperature is not None:
-            calib['then'] = [temper_stage(tag + (SMOOTH_TAG if smooth is not None else ''), None if temperature == 'fit' else temperature,
+            calib['then'] = [temper_stage(tag + (SMOOTH_TAG if smooth is not None else '') + (SP_TAG if sp is not None else ''),
+                                          None if temperature == 'fit' else temperature,
                                           fit=fit, **dict(extras, probs=extras['probs'] or args.reliability))]
-    if smooth is not None and together:
+    if sp is not None:              # the regions vote behind --smooth and in front of --temperature
+        if not together:            # one network: its Result: block as ever, then its own softmax (a one-member ensemble)
+            evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
+        out = superpixel_whole(shape, whole, members, device, sp, smooth=smooth, tta=tta, tag=tag, raw_block=together,
+                               save_segments=args.save_segments, **common, **extras, **calib,
+                               **(dict(score_raw=True) if score is not None and not together else {}))
+    elif smooth is not None and together:
         out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=tag, raw_block=True, **common, **extras, **calib)
     elif tta is not None:
         out = tta_whole(shape, whole, members, device, tta, **common, **extras, **calib)
@@ -361,6 +382,7 @@ def build_parser():
                              "view t under element (t + 1) mod 4 / 8 (t mod 4 / 8 with --tta_no_clean); with --tta_noise 0 pure "
                              "geometry; the Result: tag becomes _tta_flips / _tta_d4")
     add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
+    add_superpixel_flags(parser, 'the prediction of --net (with or without --tta, behind --smooth; not with both / ema_both)')
     parser.add_argument('--reliability', action='store_true',
                         help='behind every Result: block one line Reliability<tag>: ECE, MCE, NLL, Brier score, mean confidence '
                              'and accuracy of the block\'s class probabilities over the labelled test pixels (not with both / '

@@ -36,6 +36,11 @@ Differences from the reference that are deliberate, MI355X-first choices:
     SMOOTHED over the scene -- an edge-preserving filter of radius R guided by the cube's leading principal components
     (cmlpl_amd.smooth; ``--smooth_sigma_s`` / ``--smooth_sigma_r`` / ``--smooth_guide`` / ``--smooth_iters``): one more
     ``Result:`` block (``OA_ens_smooth``).  The run itself is untouched.
+  * ``--superpixel S``: after the run Base and Base1 are scored together once more as REGIONS -- the scene is over-segmented
+    into superpixels on a grid of step S under the cube's leading principal components and every region votes as one
+    (cmlpl_amd.superpixel; ``--sp_compact`` / ``--sp_iters`` / ``--sp_guide`` / ``--sp_vote`` / ``--save_segments``): a
+    ``superpixel:`` line (segments, empty ones, sizes, ASA) and one more ``Result:`` block (``OA_ens_sp``; behind ``--smooth``:
+    ``OA_ens_smooth_sp``).  One GPU.  The run itself is untouched and no checkpoint records the flag.
   * ``--aug_spatial flips | d4``: flip (and rotate) augmentation of the training windows, the reference's ``flip`` /
     ``Random_rot`` (hsi_loader.py:58-88): every batch row takes one element of the dihedral group per step, the same for
     both networks, applied inside the gather of ``--windows cube`` (which it needs; one GPU).  ``--tta --tta_spatial
@@ -50,7 +55,8 @@ Differences from the reference that are deliberate, MI355X-first choices:
   * ``--reliability``: behind every ``_ens`` / ``_tta..`` / ``.._smooth`` block of the end-of-run report one ``Reliability<tag>:``
     line -- ECE, MCE, NLL, Brier score, mean confidence and accuracy of that block's class probabilities over the labelled
     test pixels, from integer counters kept on the device (cmlpl_amd.calibrate).  It needs ``--ensemble``, ``--tta`` or
-    ``--smooth``; ``loss_hist``, checkpoints and every other line are what they are without the flag.
+    ``--smooth`` (or ``--superpixel``, whose ``.._sp`` block it scores as well); ``loss_hist``, checkpoints and every other line
+    are what they are without the flag.
   * ``--knn K`` (``--knn_T T``, default ``--temperature``): the embedding itself is scored -- the weighted kNN vote
     (cmlpl_amd.knn: K neighbours by cosine similarity of the spectral branch's ``feat``, each weighted by exp(s / T)) of the
     test split's pixels over the labelled training pixels, untiled.  With ``--eval_every`` two more lines per evaluation
@@ -152,7 +158,7 @@ def saved_args(args):
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
             'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
             'knn': None, 'knn_T': None, **OPTIM_FLAGS}
-    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS}
+    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS and k not in SP_FLAGS}
 
 
 LP_FLAGS = ('propagate', 'lp_k', 'lp_alpha', 'lp_gamma', 'lp_iters')     # --propagate: cmlpl_amd.labelprop.LabelProp's fields
@@ -310,6 +316,48 @@ def smooth_of(args):
     return smooth
 
 
+SP_TAG = '_sp'                                                     # superpixel_stage: appended to the tag of what votes
+SP_FLAGS = ('superpixel', 'sp_compact', 'sp_iters', 'sp_guide', 'sp_vote', 'save_segments')
+
+
+def add_superpixel_flags(parser, what):
+    """``--superpixel S`` and its sub-flags (train.py and predict.py); every default is None: the flag was not given"""
+    parser.add_argument('--superpixel', type=int, default=None, metavar='S',
+                        help='object-based classification of %s: the scene is over-segmented into superpixels on a grid of '
+                             'step S (2 .. 64) under the leading channels of the scene cube, and every region votes as one: '
+                             'one more Result: block, tag ..._sp' % what)
+    parser.add_argument('--sp_compact', type=float, default=None, metavar='M',
+                        help='--superpixel: the compactness, the weight of the distance in the image (default 1)')
+    parser.add_argument('--sp_iters', type=int, default=None, metavar='T',
+                        help='--superpixel: rounds of assign and update (default 10, 1 .. 100)')
+    parser.add_argument('--sp_guide', type=int, default=None, metavar='G',
+                        help='--superpixel: how many leading channels of the cube guide the segmentation (default 3, 0 .. 8; 0: '
+                             'a plain grid)')
+    parser.add_argument('--sp_vote', choices=('soft', 'hard'), default=None,
+                        help="--superpixel: a region sums its pixels' class probabilities (soft, the default) or counts their "
+                             "labels (hard)")
+    parser.add_argument('--save_segments', default=None, metavar='FILE',
+                        help='--superpixel: write the int32 segment map [rows*cols] as .npy')
+
+
+def superpixel_of(args):
+    """the ``cmlpl_amd.superpixel.Superpixel`` of the command line, or None without ``--superpixel``; what it cannot mean is
+    a SystemExit before anything is loaded"""
+    given = [k for k in SP_FLAGS[1:] if getattr(args, k, None) is not None]
+    if getattr(args, 'superpixel', None) is None:
+        if given:
+            raise SystemExit("%s belong%s to --superpixel S" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
+        return None
+    from cmlpl_amd.superpixel import Superpixel
+    asked = {k: getattr(args, 'sp_' + k, None) for k in ('compact', 'iters', 'guide', 'vote')}
+    sp = Superpixel(args.superpixel, **{k: v for k, v in asked.items() if v is not None})
+    try:
+        sp.params()
+    except ValueError as e:
+        raise SystemExit("--superpixel: %s" % str(e).replace("Superpixel: ", ""))
+    return sp
+
+
 def tta_tag(tta):
     """the tag of a TTA prediction's ``Result:`` lines: ``_tta``, with ``_flips`` / ``_d4`` behind it when its views are spatial"""
     return NET_TAGS['tta'] + ('' if tta.spatial == 'none' else '_' + tta.spatial)
@@ -465,6 +513,70 @@ def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout
         shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube, then=then, score=score)
 
 
+def raw_prediction(tta=None, weights=None):
+    """(predict, timing) of ``together_whole`` for the prediction that later stages read: ``ensemble_cube`` (``tta``:
+    ``tta_cube``) with its probabilities"""
+    if tta is None:
+        from cmlpl_amd.ensemble import ensemble_cube
+        return (lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=True),
+                'ensemble inference time == %.3f s (%d networks)')
+    from cmlpl_amd.tta import tta_cube
+    return lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True), tta_timing(tta)
+
+
+def smooth_stage(tag, smooth, probs=False, conf=False, entropy=False):
+    """the stage of ``together_whole`` that smooths the probabilities in front of it (cmlpl_amd.smooth.smooth_probs): its
+    ``Result:`` lines carry ``tag`` + ``_smooth``"""
+    from cmlpl_amd.smooth import smooth_probs
+    R, ss, sr, G, iters = smooth.params()
+    return ('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
+            (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
+            lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy))
+
+
+def superpixel_stage(tag, sp, K, probs=False, conf=False, entropy=False, test_array=None, Y_test=None, save_segments=None):
+    """the stage of ``together_whole`` in which the regions vote (cmlpl_amd.superpixel.superpixel_probs): the scene is
+    segmented, every superpixel votes with the probabilities (``--sp_vote hard``: the labels) in front of it, and one line
+    ``superpixel: segments= empty= mean_size= max_size= ASA=`` says what the map is (ASA on the labelled test pixels: the
+    accuracy no region-level labelling of this map can exceed).  Its ``Result:`` lines carry ``tag`` + ``_sp``."""
+    from cmlpl_amd.superpixel import asa, superpixel_probs
+    S, m, T, G, vote = sp.params()
+
+    def call(res, cube):
+        out = superpixel_probs(res.probs, cube, sp, labels=res.labels, probs_out=probs, conf=conf, entropy=entropy)
+        segs = out.segments
+        counts = segs.counts.cpu().numpy()
+        bound = 'n/a' if test_array is None else '%.4f' % asa(segs.seg, segs.N, test_array, Y_test, K)
+        print('superpixel: segments=%d empty=%d mean_size=%.1f max_size=%d ASA=%s' %
+              (segs.N, int((counts == 0).sum()), counts.sum() / segs.N, counts.max(), bound))
+        if save_segments:
+            np.save(save_segments, segs.seg.cpu().numpy())
+        return out
+    return ('superpixel time == %%.3f s (step %d, compactness %g, %d iterations, up to %d guide channels, %s vote)' %
+            (S, m, T, G, vote), tag + SP_TAG, call)
+
+
+def superpixel_whole(shape, whole, nets, device, sp, smooth=None, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None,
+                     dataID=1, dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False,
+                     entropy=False, then=(), score=None, score_raw=None, save_segments=None):
+    """``ensemble_whole`` (``tta``: ``tta_whole``), smoothed first when ``smooth`` is given (its block under ``tag`` +
+    ``_smooth``, as ``smooth_whole`` prints it), followed by the region vote over the scene's superpixels (``sp``: a
+    cmlpl_amd.superpixel.Superpixel).  Same returns, of the VOTED prediction; its ``Result:`` lines carry the tag in front
+    of it + ``_sp``.  ``raw_block``: the ``Result:`` block of the first prediction is printed, under ``tag``."""
+    raw, timing = raw_prediction(tta, weights)
+    sp.params()
+    probs = probs or bool(then) or score is not None            # (what follows the vote reads its probabilities)
+    stages, at = [], tag
+    if smooth is not None:
+        stages.append(smooth_stage(at, smooth, probs=True))
+        at += SMOOTH_TAG
+    stages.append(superpixel_stage(at, sp, shape[4], probs=probs, conf=conf, entropy=entropy, test_array=test_array,
+                                   Y_test=Y_test, save_segments=save_segments))
+    return together_whole(
+        raw, timing, tag, "the superpixel vote", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test,
+        resident_cube, then=[*stages, *then], raw_block=raw_block, score=score, score_raw=score_raw)
+
+
 def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None, dataID=1,
                  dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False, entropy=False,
                  then=(), score=None, score_raw=None):
@@ -472,22 +584,11 @@ def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens
     maps under the guide of the scene cube (``smooth``: a cmlpl_amd.smooth.Smooth; what cmlpl_amd.smooth.smooth_cube
     does, in its two halves).  Same returns, of the SMOOTHED prediction; its ``Result:`` lines carry ``tag`` + ``_smooth``.
     ``raw_block``: the ``Result:`` block of the un-smoothed prediction is printed in front of it, under ``tag``."""
-    from cmlpl_amd.smooth import smooth_probs
-    if tta is None:
-        from cmlpl_amd.ensemble import ensemble_cube
-        raw = lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=True)
-        timing = 'ensemble inference time == %.3f s (%d networks)'
-    else:
-        from cmlpl_amd.tta import tta_cube
-        raw = lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True)
-        timing = tta_timing(tta)
-    R, ss, sr, G, iters = smooth.params()
+    raw, timing = raw_prediction(tta, weights)
     probs = probs or bool(then) or score is not None            # (what follows the smoothing reads its probabilities)
     return together_whole(
         raw, timing, tag, "spatial smoothing", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-        then=[('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
-               (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
-               lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy)), *then],
+        then=[smooth_stage(tag, smooth, probs=probs, conf=conf, entropy=entropy), *then],
         raw_block=raw_block, score=score, score_raw=score_raw)
 
 
@@ -915,15 +1016,18 @@ def report(run, args):
     if args.tta:
         from cmlpl_amd.tta import TTA
         tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise, spatial=args.tta_spatial), **scene, **rel)
-    if run.smooth is not None:
+    if run.sp is not None:            # --superpixel: behind the smoothed block when --smooth is given, else behind the pair's
+        superpixel_whole(run.shape, run.whole, nets[:2], device, run.sp, smooth=run.smooth, save_segments=args.save_segments,
+                         **scene, **rel)
+    elif run.smooth is not None:
         smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene, **rel)
 
 
-def check_reliability_args(args, smooth):
+def check_reliability_args(args, smooth, sp=None):
     """what --reliability cannot mean, said before any device or communicator work"""
-    if args.reliability and not (args.ensemble or args.tta or smooth is not None):
+    if args.reliability and not (args.ensemble or args.tta or smooth is not None or sp is not None):
         raise SystemExit("--reliability scores the class probabilities of the end-of-run report's _ens / _tta / _smooth blocks: "
-                         "it needs --ensemble, --tta or --smooth")
+                         "it needs --ensemble, --tta or --smooth (or --superpixel, whose _sp block it scores as well)")
     if args.reliability and args.no_eval:
         raise SystemExit("--reliability belongs to the end-of-run report: not with --no_eval")
 
@@ -946,6 +1050,11 @@ def main(args, make_engine=None, device=None):
     on CPU around a stand-in engine); the product path leaves them None."""
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     smooth = smooth_of(args)                                        # (refused before any device or communicator work)
+    sp = superpixel_of(args)
+    if sp is not None and world > 1:
+        raise SystemExit(f"--superpixel runs on one GPU (this job has {world} ranks)")
+    if sp is not None and args.no_eval:
+        raise SystemExit("--superpixel belongs to the end-of-run report: not with --no_eval")
     if args.method != "cmlpl" and world > 1:      # before any device or communicator work
         raise SystemExit(f"--method {args.method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
                          f"{world} ranks)")
@@ -962,7 +1071,7 @@ def main(args, make_engine=None, device=None):
                          "ranks)" % (optim_on[0], world))
     if args.save_optim and not optim_on:
         raise SystemExit("--save_optim belongs to --lr_schedule / --warmup_steps / --weight_decay / --clip_grad")
-    check_reliability_args(args, smooth)
+    check_reliability_args(args, smooth, sp)
     if args.knn is not None and world > 1:
         raise SystemExit(f"--knn runs on one GPU (this job has {world} ranks)")
     if args.knn is not None and not 1 <= args.knn <= 32:
@@ -984,7 +1093,7 @@ def main(args, make_engine=None, device=None):
                              gen=torch.Generator().manual_seed(1088), curves={curve.suffix: curve for curve in curves},
                              from_scene=False, whole=None, test_array=None, Y_test=None, resumed=None, cube_kw={},
                              evaluator=None, start_epoch=0, best_oa=None, best_state=None, best_extra=None, smooth=smooth,
-                             pl_curve=[], knn=None, optim=None, optim_hist=None, total_steps=0, lp=lp)
+                             pl_curve=[], knn=None, optim=None, optim_hist=None, total_steps=0, lp=lp, sp=sp)
     load_data(run, args)              # labeled, unlabeled, shape, from_scene; whole, test_array, Y_test if anything is evaluated
     build_engine(run, args, make_engine)      # hp; eng, this rank's engine at its default initial parameters
     if args.save_best and args.eval_every <= 0:
@@ -1087,6 +1196,7 @@ def build_parser():
     parser.add_argument('--save_optim', default=None, metavar='PATH',
                         help='with an optimiser flag on: write [num_steps][5] = lr, norm, norm1, coef, coef1 of every step as .npy')
     add_smooth_flags(parser, 'Base and Base1 together after the run')
+    add_superpixel_flags(parser, 'Base and Base1 together after the run (behind --smooth when given; one GPU)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

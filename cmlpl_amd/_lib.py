@@ -55,6 +55,7 @@ EXPORTS = (
     "cmlpl_lp_graph_bytes", "cmlpl_lp_graph", "cmlpl_lp_propagate",              # added after ABI 6, no bump: label propagation
     "cmlpl_sp_workspace_bytes", "cmlpl_sp_segment", "cmlpl_sp_vote_workspace_bytes",                 # added after ABI 6, no bump:
     "cmlpl_sp_vote_probs", "cmlpl_sp_vote_labels",                               # superpixels and region votes
+    "cmlpl_patches_fit",                                                         # added after ABI 6, no bump: which windows the cuts take
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -351,6 +352,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_sp_vote_workspace_bytes.restype = sz
     lib.cmlpl_sp_vote_probs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_sp_vote_labels.argtypes = lib.cmlpl_sp_vote_probs.argtypes
+    lib.cmlpl_patches_fit.argtypes = [i32, i32]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]

@@ -1159,10 +1159,16 @@ int cmlpl_step_graph_destroy(void* graph) {
   return 0;
 }
 
+// which cuts take w x w windows of C channels (include/cmlpl.h): the launchers' own LDS sizes against their own limit
+int cmlpl_patches_fit(int C, int w) {
+  if (C < 1 || w < 1 || w > 4096 || C > 65536) return 0;          // (far past any fit; w * C below stays inside int)
+  return (extract_lds(C, w) <= LDS_MAX ? 1 : 0) | (tta_patches_lds(C, w) <= LDS_MAX ? 2 : 0);
+}
+
 int cmlpl_extract_patches(const float* d_cube, int rows, int cols, int C, int w, const int64_t* d_pixel_idx, int n,
                           float* d_out, void* stream) {
   if (!d_cube || !d_pixel_idx || !d_out || rows < 1 || cols < 1 || C < 1 || w < 1 || n < 1) return CMLPL_E_ARG;
-  if (w / 2 > rows || w / 2 > cols || (size_t)w * w * (C | 1) * 4 > LDS_MAX) return CMLPL_E_SHAPE;
+  if (w / 2 > rows || w / 2 > cols || !(cmlpl_patches_fit(C, w) & 1)) return CMLPL_E_SHAPE;
   return chk(launch_extract_patches(d_cube, rows, cols, C, w, (const long long*)d_pixel_idx, n, d_out,
                                     (hipStream_t)stream));
 }
@@ -1199,7 +1205,8 @@ static int infer_impl(const cmlpl_shape* shape, int nets, const float* d_params,
       (view && !view_args_ok(view->sigma)))
     return CMLPL_E_ARG;
   if (view) if (int src = view_sym_check(view->sym, d.H, d.W)) return src;
-  if (listed ? (!d_pix || nets < 1 || nets > 2 || rows < d.H / 2 || cols < d.W / 2 ||
+  if (rows < d.H / 2 || cols < d.W / 2) return CMLPL_E_ARG;      // (one mirror fold: what the launcher refuses, either feed)
+  if (listed ? (!d_pix || nets < 1 || nets > 2 ||
                 (nets == 2 && (param_stride < L.param_total || packed_stride < L.packed_total)))
              : (pixel0 < 0 || pixel0 + n > (int64_t)rows * cols))
     return CMLPL_E_ARG;
@@ -1209,7 +1216,7 @@ static int infer_impl(const cmlpl_shape* shape, int nets, const float* d_params,
   if (listed && big) return CMLPL_E_ARG;
   if (infer_workspace(shape, nets, n, view != nullptr) > workspace_bytes) return CMLPL_E_WORKSPACE;
   if (view && view->sigma == 0.f && view->sym == 0u) view = nullptr;      // the clean forward, its launches and its bytes
-  if (view && !listed && (big || d.W / 2 > rows || d.W / 2 > cols)) return CMLPL_E_ARG;   // (what the launcher refuses)
+  if (view && !listed && big) return CMLPL_E_ARG;                         // (what the launcher refuses)
   hipStream_t st = (hipStream_t)stream;
   float* y = (float*)d_workspace;
   const float* sn = listed ? d_spectra : d_spectra + (long long)pixel0 * d.bands;
@@ -1324,7 +1331,7 @@ int cmlpl_tta_patches_sym(const float* d_cube, int rows, int cols, int C, int w,
   if (!d_pixel_idx || (!d_out && !d_spectra_out) || rows < 1 || cols < 1 || n < 1 || !view_args_ok(sigma)) return CMLPL_E_ARG;
   if (d_out && (!d_cube || C < 1 || w < 1)) return CMLPL_E_ARG;
   if (d_spectra_out && (!d_spectra || bands < 1)) return CMLPL_E_ARG;
-  if (d_out && (w / 2 > rows || w / 2 > cols || tta_patches_lds(C, w) > LDS_MAX)) return CMLPL_E_SHAPE;
+  if (d_out && (w / 2 > rows || w / 2 > cols || !(cmlpl_patches_fit(C, w) & 2))) return CMLPL_E_SHAPE;
   const ViewKey key = {sigma, seed, view, sym};
   int rc;
   if (d_out && (rc = chk(launch_tta_patches(d_cube, rows, cols, C, w, (const long long*)d_pixel_idx, n, d_out, key,

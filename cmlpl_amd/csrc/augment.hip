@@ -334,7 +334,7 @@ __global__ __launch_bounds__(512) void extract_patches_kernel(const float* __res
   }
 }
 
-static size_t extract_lds(int C, int w) {
+size_t extract_lds(int C, int w) {
   const size_t rs = (C & 1) ? (size_t)((w * C + 3) & ~3) : (size_t)w * (C + 1);
   return (size_t)w * rs * 4;
 }

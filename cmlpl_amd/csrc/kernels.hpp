@@ -86,6 +86,7 @@ hipError_t launch_augment(int which, int nets, int bt, int btu, int per_xp, int 
 hipError_t launch_dist_unpack(const float* recv_f, const float* recv_z, int W, int bt_l, int btu_l, int K, float* logits_g,
                               float* feat_g, long long* labels_g, hipStream_t st);
 
+size_t extract_lds(int C, int w);      // dynamic LDS of the cut of one w x w x C window (cmlpl_patches_fit asks it)
 hipError_t launch_extract_patches(const float* cube, int rows, int cols, int C, int w, const long long* idx, int n,
                                   float* out, hipStream_t st);
 

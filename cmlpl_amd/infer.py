@@ -43,10 +43,14 @@ def infer_supported(shape) -> bool:
     """can ``infer_cube`` label a scene of this window shape straight from its cube?  Every square window the network
     runs on: the fused kernel where it applies (``infer_fused``), else -- the reference's own 20 x 20 x 60 windows -- the
     windows of a few thousand pixels at a time cut on the device (cmlpl_extract_patches) and run through the general
-    forward (cmlpl_basenet2_fwd).  Either way the scene stays in HBM as its cube; the 19.9 GB patch tensor never exists."""
+    forward (cmlpl_basenet2_fwd).  Either way the scene stays in HBM as its cube; the 19.9 GB patch tensor never exists.
+    By patches one window has to fit the cut's LDS (``cmlpl_patches_fit``: about w * w * C <= 40,960 -- 101 channels at
+    20 x 20), for the clean cut and the view cut alike: ``infer_cube``, the ensemble and TTA answer to the same promise."""
     lib = _lib.load()
     cs = _lib.Shape(shape.C, shape.H, shape.W, shape.bands, shape.K)
-    return shape.H == shape.W and lib.cmlpl_workspace_bytes(C.byref(cs), 1, 8, 8) > 0
+    if shape.H != shape.W or lib.cmlpl_workspace_bytes(C.byref(cs), 1, 8, 8) == 0:
+        return False
+    return infer_fused(shape) or lib.cmlpl_patches_fit(shape.C, shape.H) == 3
 
 
 def _nets_buffers(nets):
@@ -90,6 +94,9 @@ def _check_scene(cube, spectra, cs=None, whole: bool = False):
     if cs is not None and (cube.shape[2] != cs.C or spectra.shape[1] != cs.bands):
         raise ValueError(f"cube has {cube.shape[2]} channels / spectra {spectra.shape[1]} bands, the network wants "
                          f"{cs.C} / {cs.bands}")
+    if cs is not None and (cube.shape[0] < cs.H // 2 or cube.shape[1] < cs.W // 2):      # (the mirror index folds once)
+        raise ValueError(f"scene of {cube.shape[0]} x {cube.shape[1]} pixels: a {cs.H} x {cs.W} window needs at least "
+                         f"{cs.H // 2} x {cs.W // 2}")
 
 
 class _Range(NamedTuple):
@@ -173,6 +180,9 @@ class _Forward:
             need = lib.cmlpl_workspace_bytes(C.byref(cs), 1, chunk, chunk)
             if need == 0:
                 raise _lib.CmlplError("cmlpl_workspace_bytes", -2)
+            cuts = 3 if views else 1          # (a view call cuts its clean block with cmlpl_extract_patches)
+            if lib.cmlpl_patches_fit(cs.C, cs.H) & cuts != cuts:      # before anything is allocated or launched
+                raise _lib.CmlplError("cmlpl_tta_patches_sym" if views else "cmlpl_extract_patches", -2)
             self.xp = torch.empty(chunk, cs.C, cs.H, cs.W, dtype=torch.float32, device=dev)
             self.x = torch.empty(chunk, cs.bands, dtype=torch.float32, device=dev) if views else None
             self.z = torch.empty(chunk, cs.K, dtype=torch.float32, device=dev)      # the logits nobody asked for

@@ -466,7 +466,8 @@ int cmlpl_extract_patches(const float* d_cube, int rows, int cols, int C, int w,
  * (cmlpl_layout / cmlpl_pack_weights with nets = 1).  Workspace: cmlpl_infer_workspace_bytes(shape, n) -- which is 0 for
  * a shape this entry point does not take.
  * Returns CMLPL_E_SHAPE for windows the per-sample forward does not take (more than 256 window pixels, final pooled
- * maps of more than 12 pixels: extract patches and use cmlpl_basenet2_fwd there). */
+ * maps of more than 12 pixels: extract patches and use cmlpl_basenet2_fwd there), CMLPL_E_ARG for a scene with fewer
+ * rows or columns than half a window (the mirror index folds once) -- as every error here, before any launch. */
 size_t cmlpl_infer_workspace_bytes(const cmlpl_shape* shape, int n);
 int cmlpl_infer_cube(const cmlpl_shape* shape, const float* d_params, const float* d_packed, const float* d_cube,
                      int rows, int cols, const float* d_spectra, int64_t pixel0, int n, int64_t* d_labels,
@@ -1372,6 +1373,15 @@ int cmlpl_sp_vote_probs(const int32_t* d_seg, const float* d_probs, int n, int K
 int cmlpl_sp_vote_labels(const int32_t* d_seg, const int64_t* d_src_labels, int n, int K, int N, float* d_out_probs,
                          int64_t* d_labels, float* d_conf, float* d_entropy, int64_t* d_sums, int64_t* d_cnt,
                          float* d_seg_probs, int64_t* d_seg_labels, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Added after ABI 6, no bump (nothing existing moves) -- WHICH WINDOWS THE CUTS TAKE.  cmlpl_extract_patches and
+ * cmlpl_tta_patches(_sym) hold one window of w x w pixels x C channels in LDS and return CMLPL_E_SHAPE for one that does
+ * not fit in 160 KiB (about w w C <= 40,960 floats: at 20 x 20, 101 channels fit and 102 do not).  A caller that scores a
+ * scene by patches -- windows the fused forward of cmlpl_infer_cube does not take -- asks here BEFORE it builds anything:
+ * bit 0 = the clean cut (cmlpl_extract_patches) takes (C, w), bit 1 = the view cut (cmlpl_tta_patches / _sym, d_out != NULL)
+ * does; 0 for C < 1 or w < 1.  Answered from the two launchers' own LDS sizes, which the entry points above compare as well.
+ * Host arithmetic only. */
+int cmlpl_patches_fit(int C, int w);
 
 #ifdef __cplusplus
 }

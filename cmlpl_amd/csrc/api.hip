@@ -479,11 +479,11 @@ int bwd_core(const Dims& d, const NetRoute& r, const cmlpl_layout_t& L, int nets
   bool wpair = false;
   if (!plan_wgrad3_both(nets, n, d.H, d.W, d.H2, d.W2, true, &wp1, &wp2, &wpair)) return CMLPL_E_SHAPE;
   if (fuse != nullptr && (parts != 3 || dyn_cursor != nullptr || fuse->gbase != d_grads)) return CMLPL_E_ARG;
-  const int el = fuse != nullptr ? REDUCE_FUSED_EL : 256;
-  reduce_table_add(rt, w.part1, wp1.G, PART3, 1, 64, d_grads + L.param_off[2], d_grads + L.param_off[3], el);
-  reduce_table_add(rt, w.part2, wp2.G, PART3, 1, 64, d_grads + L.param_off[4], d_grads + L.param_off[5], el);
+  const bool fused = fuse != nullptr;                   // block widths of the fused launch (kernels.hpp: reduce_el)
+  reduce_table_add(rt, w.part1, wp1.G, PART3, 1, 64, d_grads + L.param_off[2], d_grads + L.param_off[3], fused);
+  reduce_table_add(rt, w.part2, wp2.G, PART3, 1, 64, d_grads + L.param_off[4], d_grads + L.param_off[5], fused);
   reduce_table_add(rt, w.part0, conv0_partials(d, r, n), conv0_partial_size(d.C), 0, d.C,
-                   d_grads + L.param_off[0], d_grads + L.param_off[1], el);
+                   d_grads + L.param_off[0], d_grads + L.param_off[1], fused);
   // the classifier / feat_spe weight-gradient GEMMs ride along (independent, short); with `fuse` so does the Adam step
   // of every gradient element this launch forms -- all ten live tensors
   return TIMED(CMLPL_K_CONV1_WRED, chk(launch_reduce_gemm(nets, rt, gw_cls, gw_spe, st, fuse)));

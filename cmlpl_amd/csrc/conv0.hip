@@ -376,13 +376,69 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
   }
 }
 
-// out[map(e)] = sum_g part[g][e]: 64 elements x 4 slices of g per block, 8 loads in flight per thread,
-// fixed summation order (bit-reproducible, unlike float atomics).  Up to 3 tensors per launch.
+// out[map(e)] = sum_g part[g][e], in a fixed summation order (bit-reproducible, unlike float atomics).  Up to 3 tensors
+// per launch.
 // mode 0: conv0  e = c*64+co -> dW[co*C + c] (c < C), tail 64 -> db
 // mode 1: conv3x3 e = s*4096 + ci*64 + co -> dW[co*576 + ci*9 + s], tail 64 -> db
-// One block = 256 consecutive elements x 4 slices of g: a thread owns 4 consecutive elements (one 16-B load per
-// partial row, a wave reads 1 KiB of a row at a time -- the 4-B-per-lane version read 256-B pieces of rows that lie
-// tens of KB apart and reached 3.1 TB/s), 8 loads in flight, fixed summation order.
+// THE ORDER, which no blocking below may change: slice sl (of 4) takes the rows g = sl (mod 4) in groups of 32 rows
+// (eight of the slice's), the groups in order; a group's rows v0 .. v7 enter as s0 += (v0+v1)+(v2+v3) and
+// s1 += (v4+v5)+(v6+v7); the slice's sum is s0 + s1 and the element's (a+b)+(c+d) over the slices.  s0 and s1 start at
+// +0.0f and a sum that started there is never -0.0f, so a group of rows past G -- they are masked to +0.0f -- adds
+// nothing: a loop may run past the last group of the slice.
+//
+// A partial row that does not exist (g >= G) reads row 0 and is masked to +0.0f by an AND whose mask goes through an
+// empty asm: given a select on the loaded value, hipcc sinks each load under a branch with a full wait behind it, and the
+// loads of a group run one after the other (32 us for the fused launch instead of 12).  No load stands under a branch.
+__device__ __forceinline__ float4 part_row(const float* p, int g, int G, int PS) {
+  uint32_t keep = g < G ? 0xffffffffu : 0u;
+  asm volatile("" : "+v"(keep));
+  const float4 x = *(const float4*)(p + (size_t)(g < G ? g : 0) * PS);
+  return make_float4(__uint_as_float(__float_as_uint(x.x) & keep), __uint_as_float(__float_as_uint(x.y) & keep),
+                     __uint_as_float(__float_as_uint(x.z) & keep), __uint_as_float(__float_as_uint(x.w) & keep));
+}
+// s += (a+b)+(c+d), per component
+__device__ __forceinline__ void add_quad(float4& s, const float4& a, const float4& b, const float4& c, const float4& d) {
+  s.x += (a.x + b.x) + (c.x + d.x); s.y += (a.y + b.y) + (c.y + d.y);
+  s.z += (a.z + b.z) + (c.z + d.z); s.w += (a.w + b.w) + (c.w + d.w);
+}
+
+// conv0 has one partial per sample and network (G up to 256) where a 3x3 tensor has a few tens, so its blocks would
+// carry by far the longest chain of dependent loads in the launch.  One block = REDUCE_CONV0_EL = 128 consecutive
+// elements = 32 float4 columns, and a (column, slice) is shared by TWO threads: h = 0 loads v0 .. v3 of every group and
+// carries s0, h = 1 loads v4 .. v7 and carries s1 -- the two chains never met before the end of the loop anyway.  Four
+// groups (16 loads a thread) are requested before the first is added: G = 256 is two round trips where it was eight, and
+// a block pulls 128 KB of partials through its CU where the fused launch pulled 512.
+// All 256 threads call; returns the sum of element eb + tid to the threads tid < REDUCE_CONV0_EL (red4: 4 KB of LDS).
+__device__ __forceinline__ float conv0_fold(const ReduceProb& pr, int eb, int net, float4* red4) {
+  const int tid = threadIdx.x, col = tid & 31, h = (tid >> 5) & 1, sl = tid >> 6;
+  const int G = pr.G, PS = pr.PS;                      // PS is a multiple of 64
+  const int e0 = eb + col * 4;
+  const float* p = pr.part + (long long)net * G * PS + (e0 < PS ? e0 : 0);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int g0 = sl + 16 * h; g0 - 16 * h < G; g0 += 128) {
+    const float4 a0 = part_row(p, g0, G, PS), a1 = part_row(p, g0 + 4, G, PS);
+    const float4 a2 = part_row(p, g0 + 8, G, PS), a3 = part_row(p, g0 + 12, G, PS);
+    const float4 b0 = part_row(p, g0 + 32, G, PS), b1 = part_row(p, g0 + 36, G, PS);
+    const float4 b2 = part_row(p, g0 + 40, G, PS), b3 = part_row(p, g0 + 44, G, PS);
+    const float4 c0 = part_row(p, g0 + 64, G, PS), c1 = part_row(p, g0 + 68, G, PS);
+    const float4 c2 = part_row(p, g0 + 72, G, PS), c3 = part_row(p, g0 + 76, G, PS);
+    const float4 d0 = part_row(p, g0 + 96, G, PS), d1 = part_row(p, g0 + 100, G, PS);
+    const float4 d2 = part_row(p, g0 + 104, G, PS), d3 = part_row(p, g0 + 108, G, PS);
+    add_quad(s, a0, a1, a2, a3);
+    add_quad(s, b0, b1, b2, b3);
+    add_quad(s, c0, c1, c2, c3);
+    add_quad(s, d0, d1, d2, d3);
+  }
+  red4[tid] = s;                                       // [slice][h][column]
+  __syncthreads();
+  const float* sm = (const float*)red4;
+  const int w = tid & 127;                             // column w / 4, component w % 4
+  return ((sm[w] + sm[128 + w]) + (sm[256 + w] + sm[384 + w])) + ((sm[512 + w] + sm[640 + w]) + (sm[768 + w] + sm[896 + w]));
+}
+
+// The unfused fold.  A 3x3 tensor: one block = 256 consecutive elements x 4 slices of g: a thread owns 4 consecutive
+// elements (one 16-B load per partial row, a wave reads 1 KiB of a row at a time -- the 4-B-per-lane version read 256-B
+// pieces of rows that lie tens of KB apart and reached 3.1 TB/s), two groups (16 loads) in flight.  conv0: conv0_fold.
 __device__ __forceinline__ void partial_reduce_block(const ReduceTable& t, int bx, int net, float (*red)[64]) {
   int pi = 0;
   if (t.count > 1 && bx >= t.p[1].blk0) pi = 1;
@@ -400,21 +456,31 @@ __device__ __forceinline__ void partial_reduce_block(const ReduceTable& t, int b
     dst[0] = r0; dst[1] = r1; dst[2] = r2; dst[3] = r3;
   }
   const int G = pr.G, PS = pr.PS;                      // PS is a multiple of 4 (64-float tail, 4096-float taps)
+  const int body = PS - 64;
+  if (pr.mode == 0) {                                  // (block-uniform)
+    const int eb = (bx - pr.blk0) * REDUCE_CONV0_EL, e = eb + tid;
+    const float sum = conv0_fold(pr, eb, net, (float4*)&red[0][0]);
+    if (tid < REDUCE_CONV0_EL && e < PS) {
+      if (e >= body) pr.db[(long long)net * t.grad_ns + (e - body)] = sum;
+      else if ((e >> 6) < pr.C) pr.dW[(long long)net * t.grad_ns + (e & 63) * pr.C + (e >> 6)] = sum;
+    }
+    return;
+  }
   const int e0 = ((bx - pr.blk0) * 64 + el) * 4;
   const bool ev = e0 < PS;
   const float* p = pr.part + (long long)net * G * PS + (ev ? e0 : 0);
   float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-  for (int g0 = sl; g0 < G; g0 += 32) {
-    float4 v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int g = g0 + 4 * q;
-      const float4 x = *(const float4*)(p + (size_t)(g < G ? g : 0) * PS);
-      v[q] = (g < G) ? x : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#define CMLPL_ADD4(F) s0.F += (v[0].F + v[1].F) + (v[2].F + v[3].F); s1.F += (v[4].F + v[5].F) + (v[6].F + v[7].F);
-    CMLPL_ADD4(x) CMLPL_ADD4(y) CMLPL_ADD4(z) CMLPL_ADD4(w)
-#undef CMLPL_ADD4
+  for (int g0 = sl; g0 < G; g0 += 64) {
+    const float4 a0 = part_row(p, g0, G, PS), a1 = part_row(p, g0 + 4, G, PS);
+    const float4 a2 = part_row(p, g0 + 8, G, PS), a3 = part_row(p, g0 + 12, G, PS);
+    const float4 a4 = part_row(p, g0 + 16, G, PS), a5 = part_row(p, g0 + 20, G, PS);
+    const float4 a6 = part_row(p, g0 + 24, G, PS), a7 = part_row(p, g0 + 28, G, PS);
+    const float4 b0 = part_row(p, g0 + 32, G, PS), b1 = part_row(p, g0 + 36, G, PS);
+    const float4 b2 = part_row(p, g0 + 40, G, PS), b3 = part_row(p, g0 + 44, G, PS);
+    const float4 b4 = part_row(p, g0 + 48, G, PS), b5 = part_row(p, g0 + 52, G, PS);
+    const float4 b6 = part_row(p, g0 + 56, G, PS), b7 = part_row(p, g0 + 60, G, PS);
+    add_quad(s0, a0, a1, a2, a3); add_quad(s1, a4, a5, a6, a7);
+    add_quad(s0, b0, b1, b2, b3); add_quad(s1, b4, b5, b6, b7);
   }
   float4* red4 = (float4*)&red[0][0];                  // [4 slices][64] float4 = 4 KB
   red4[sl * 64 + el] = make_float4(s0.x + s1.x, s0.y + s1.y, s0.z + s1.z, s0.w + s1.w);
@@ -423,15 +489,11 @@ __device__ __forceinline__ void partial_reduce_block(const ReduceTable& t, int b
     const float4 a = red4[el], b = red4[64 + el], c = red4[128 + el], d = red4[192 + el];
     const float sum[4] = {(a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z),
                           (a.w + b.w) + (c.w + d.w)};
-    const int body = PS - 64;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int e = e0 + j;
       if (e >= body) {
         pr.db[(long long)net * t.grad_ns + (e - body)] = sum[j];
-      } else if (pr.mode == 0) {
-        const int c2 = e >> 6, co = e & 63;
-        if (c2 < pr.C) pr.dW[(long long)net * t.grad_ns + co * pr.C + c2] = sum[j];
       } else {
         const int s = e >> 12, ci = (e >> 6) & 63, co = e & 63;
         pr.dW[(long long)net * t.grad_ns + co * 576 + ci * 9 + s] = sum[j];
@@ -455,6 +517,7 @@ __global__ __launch_bounds__(256) void reduce_gemm_kernel(ReduceTable t, int red
 }
 
 // ---- the fold with the Adam step behind it (the eager, unclipped training step: no optimizer launch follows)
+// A 3x3 tensor (mode 1) and the bias tails:
 // One block = REDUCE_FUSED_EL = 512 consecutive partial elements x 4 slices of g: a thread owns TWO float4 columns
 // (el and el + 64), each summed exactly as partial_reduce_block sums its one -- the slice sl, g0 in steps of 32 with
 // eight loads per group, then the four-slice fold: the block size does not enter the order, `grads` keeps its bits.
@@ -463,22 +526,57 @@ __global__ __launch_bounds__(256) void reduce_gemm_kernel(ReduceTable t, int red
 //   mode 1, body (one tap, 8 ci, 64 co): the updated weights meet in LDS and leave as whole 16-byte forward pieces
 //     (8 ci of one (co, tap): 64 items) and 8-byte data-gradient pieces (4 co of one (ci, tap): 128 items) of both
 //     packed families, as adam_conv_chunk writes them;
-//   mode 0, body: w0T and the conv0 bf16 fragment, element by element as adam_kernel's elementwise part;
 //   the bias tails: nothing packed.
+// conv0 (mode 0): reduce_adam_block_conv0 below, on conv0_fold's narrow blocks.
 // The sums lie in LDS as float4 columns with the column index swizzled by the ci row (col ^ 2 * (col >> 4)): a mode-1
 // wave then reads 8 ci x 8 co (a co's 8 ci lie within 256 bytes of m / v / p / grads: 3 cache lines per co where a
 // wave of 64 co touches 64) without bank conflicts.
 __device__ __forceinline__ int red_swz(int col) { return col ^ (((col >> 4) & 7) << 1); }
+
+// conv0: the threads tid < 128 own one element each -- m / v / p asked for in front of the fold, the sum to `grads`, the
+// update, and for the body w0T and the conv0 bf16 fragment, element by element as adam_kernel's elementwise part
+__device__ __forceinline__ void reduce_adam_block_conv0(const ReduceTable& t, const ReduceProb& pr, int bx, int net,
+                                                        float* sm, const AdamFuse& f) {
+  const int tid = threadIdx.x;
+  const int PS = pr.PS, body = PS - 64;
+  const int eb = (bx - pr.blk0) * REDUCE_CONV0_EL, e = eb + tid, c = e >> 6, co = e & 63;
+  long long po = -1;                                   // parameter offset inside the network (-1: none)
+  if (tid < REDUCE_CONV0_EL && e < PS) {
+    if (e >= body) po = (pr.db - f.gbase) + (e - body);
+    else if (c < pr.C) po = (pr.dW - f.gbase) + (long long)co * pr.C + c;
+  }
+  float* const pp = f.params + (long long)net * f.pstride;
+  float* const pm = f.m + (long long)net * f.pstride;
+  float* const pv = f.v + (long long)net * f.pstride;
+  const long long o = po < 0 ? 0 : po;
+  float mq = pm[o], vq = pv[o];
+  const float pq = pp[o];
+  const float sum = conv0_fold(pr, eb, net, (float4*)sm);
+  if (po < 0) return;
+  const_cast<float*>(f.gbase)[(long long)net * t.grad_ns + po] = sum;
+  const float pn = adam_update<true, false>(mq, vq, pq, sum, f, 1.f, f.keep);
+  pm[po] = mq; pv[po] = vq; pp[po] = pn;
+  if (e < body) {                                      // conv0.weight[co][c] -> w0T[c][co] + the bf16 fragment
+    float* const pkn = f.packed + (long long)net * f.pi.stride;
+    pkn[pack_off_w0t() + c * 64 + co] = pn;
+    uint32_t pcs[3];
+    b3_split(pn, pcs);
+    uint16_t* wb = (uint16_t*)(pkn + pack_off_w0b3(f.pi.C, f.pi.bands));
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) wb[conv_b3_index(0, c, co, pc)] = (uint16_t)pcs[pc];
+  }
+}
 
 __device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, int net, float* sm, const AdamFuse& f) {
   int pi = 0;
   if (t.count > 1 && bx >= t.p[1].blk0) pi = 1;
   if (t.count > 2 && bx >= t.p[2].blk0) pi = 2;
   const ReduceProb pr = t.p[pi];
+  if (pr.mode == 0) { reduce_adam_block_conv0(t, pr, bx, net, sm, f); return; }     // (block-uniform)
   const int tid = threadIdx.x, lane = tid & 63, el = lane, sl = tid >> 6;
   const int G = pr.G, PS = pr.PS, body = PS - 64;
   const int eb = (bx - pr.blk0) * REDUCE_FUSED_EL;     // first partial element of the block
-  const bool conv3 = pr.mode == 1 && eb < body;         // a whole (tap, 8 ci, 64 co) unit: 36864 = 72 x 512
+  const bool conv3 = eb < body;                         // a whole (tap, 8 ci, 64 co) unit: 36864 = 72 x 512
   const long long offW = pr.dW - f.gbase, offB = pr.db - f.gbase;
   // this thread's two elements: unit-local index u, parameter offset po inside the network (-1: none)
   int u[2];
@@ -495,8 +593,7 @@ __device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, 
       const int e = eb + u[q];
       if (e >= PS) po[q] = -1;
       else if (e >= body) po[q] = offB + (e - body);
-      else if (pr.mode == 1) po[q] = offW + (e & 63) * 576 + ((e >> 6) & 63) * 9 + (e >> 12);
-      else po[q] = (e >> 6) < pr.C ? offW + (long long)(e & 63) * pr.C + (e >> 6) : -1;
+      else po[q] = offW + (e & 63) * 576 + ((e >> 6) & 63) * 9 + (e >> 12);
     }
   }
   float* const pp = f.params + (long long)net * f.pstride;
@@ -523,15 +620,7 @@ __device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, 
     for (int c = 0; c < 2; ++c) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const int g = g0 + 4 * q;
-        // rows past G read row 0 and are masked to +0.0f by an AND whose mask goes through an empty asm: given a select
-        // on the loaded value, hipcc sinks each load under a branch with a full wait behind it, and the sixteen loads
-        // of a group run one after the other (32 us for the launch instead of 12)
-        uint32_t keep = g < G ? 0xffffffffu : 0u;
-        asm volatile("" : "+v"(keep));
-        const float4 x = *(const float4*)(p[c] + (size_t)(g < G ? g : 0) * PS);
-        v[c][q] = make_float4(__uint_as_float(__float_as_uint(x.x) & keep), __uint_as_float(__float_as_uint(x.y) & keep),
-                              __uint_as_float(__float_as_uint(x.z) & keep), __uint_as_float(__float_as_uint(x.w) & keep));
+        v[c][q] = part_row(p[c], g0 + 4 * q, G, PS);     // (masked past G, never a select: see part_row)
       }
     }
 #pragma unroll
@@ -558,17 +647,7 @@ __device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, 
     const float pn = conv3 ? adam_update<true, true>(mq[q], vq[q], pq[q], sum, f, 1.f, f.keep)
                            : adam_update<true, false>(mq[q], vq[q], pq[q], sum, f, 1.f, f.keep);
     pm[po[q]] = mq[q]; pv[po[q]] = vq[q]; pp[po[q]] = pn;
-    if (conv3) {
-      wl[(u[q] & 63) * 9 + (u[q] >> 6)] = pn;
-    } else if (pr.mode == 0 && eb + u[q] < body) {     // conv0.weight[co][c] -> w0T[c][co] + the bf16 fragment
-      const int e = eb + u[q], c = e >> 6, co = e & 63;
-      pkn[pack_off_w0t() + c * 64 + co] = pn;
-      uint32_t pcs[3];
-      b3_split(pn, pcs);
-      uint16_t* wb = (uint16_t*)(pkn + pack_off_w0b3(f.pi.C, f.pi.bands));
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc) wb[conv_b3_index(0, c, co, pc)] = (uint16_t)pcs[pc];
-    }
+    if (conv3) wl[(u[q] & 63) * 9 + (u[q] >> 6)] = pn;
   }
   if (!conv3) return;                                  // (block-uniform)
   __syncthreads();
@@ -632,11 +711,11 @@ hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, 
   GemmTN2 g;
   g.p[0] = g0; g.p[1] = g1; g.nblk0 = gemm_tn_blocks(g0);
   const int rb = t.total_blocks * nets, gb = g.nblk0 + gemm_tn_blocks(g1);
+  for (int i = 0; i < t.count; ++i)                    // the table was built for this launch's block widths
+    if (t.p[i].el != reduce_el(t.p[i].mode, fu != nullptr)) return hipErrorInvalidValue;
   if (fu != nullptr) {
-    // the update needs what only the eager step has: no device cursor to advance, 512-element blocks, all in one buffer
+    // the update needs what only the eager step has: no device cursor to advance, all in one buffer
     if (t.dyn_cursor != nullptr) return hipErrorInvalidValue;
-    for (int i = 0; i < t.count; ++i)
-      if (t.p[i].el != REDUCE_FUSED_EL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(reduce_gemm_adam_kernel, dim3(rb + gb), dim3(256), 0, st, t, rb, g, *fu);
   } else {
     hipLaunchKernelGGL(reduce_gemm_kernel, dim3(rb + gb), dim3(256), 0, st, t, rb, g);
@@ -644,7 +723,8 @@ hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, 
   return hipGetLastError();
 }
 
-void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, int el) {
+void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, bool fused) {
+  const int el = reduce_el(mode, fused);
   ReduceProb& p = t.p[t.count++];
   p.part = part; p.dW = dW; p.db = db; p.G = G; p.PS = PS; p.mode = mode; p.C = C; p.blk0 = t.total_blocks;
   p.el = el;
@@ -652,6 +732,8 @@ void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode
 }
 
 hipError_t launch_partial_reduce(int nets, const ReduceTable& t, hipStream_t st) {
+  for (int i = 0; i < t.count; ++i)
+    if (t.p[i].el != reduce_el(t.p[i].mode, false)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(partial_reduce_kernel, dim3(t.total_blocks, nets), dim3(256), 0, st, t);
   return hipGetLastError();
 }

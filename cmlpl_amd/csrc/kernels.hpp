@@ -199,9 +199,14 @@ int plan_conv0_wgrad_G(int n, int C, int HW);
 struct ReduceProb { const float* part; float* dW; float* db; int G, PS, mode, C, blk0, el; };
 struct ReduceTable { ReduceProb p[3]; int count, total_blocks; long long grad_ns;
                      int* dyn_cursor; cmlpl_dyn* dyn_table; /* graph replay: cursor advanced by 1, next row -> table[0]; or null */ };
-// el: partial elements per block -- 256, or REDUCE_FUSED_EL for a table that launch_reduce_gemm runs with an update
+// el: partial elements per block -- a 3x3 tensor (mode 1): 256, or REDUCE_FUSED_EL for a table that launch_reduce_gemm
+// runs with an update; conv0 (mode 0): REDUCE_CONV0_EL on both paths
 constexpr int REDUCE_FUSED_EL = 512;         // one tap x 8 ci x 64 co of a 3x3 tensor: whole 16-byte / 8-byte packed pieces
-void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, int el = 256);
+// conv0 has one partial per sample (G up to 256) where a 3x3 tensor has a few tens: its blocks are narrow, so that the
+// deepest stack of partial rows in the launch is read by many CUs (128 elements x 256 rows = 128 KB per block)
+constexpr int REDUCE_CONV0_EL = 128;
+inline int reduce_el(int mode, bool fused) { return mode == 0 ? REDUCE_CONV0_EL : fused ? REDUCE_FUSED_EL : 256; }
+void reduce_table_add(ReduceTable& t, const float* part, int G, int PS, int mode, int C, float* dW, float* db, bool fused = false);
 hipError_t launch_partial_reduce(int nets, const ReduceTable& t, hipStream_t st);
 struct GemmTN;
 // The Adam step of an eager, unclipped training step, applied by the workgroup that forms a gradient element right
@@ -215,7 +220,7 @@ struct AdamFuse {
   float keep;                                // the decay factor (1: none); the clip coefficient of this path is 1
   float* packed; PackInfo pi;
 };
-// fu != null: the table was built with el = REDUCE_FUSED_EL, and the update rides in the launch
+// fu != null: the table was built with fused = true, and the update rides in the launch
 hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st,
                               const AdamFuse* fu = nullptr);
 // a conv0 weight-gradient partial: [rows = C rounded up to 4][64 co] + 64 bias sums (rounds 1-3 kept whole 32-band tiles:

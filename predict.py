@@ -53,15 +53,19 @@ accuracy on the labelled test pixels that no region-level labelling of this map 
 FILE`` writes the int32 segment map."""
 import argparse
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from cmlpl_amd import checkpoint
+from cmlpl_amd.tta import TTA
 from hsi_loader import HSIDataSet, SyntheticScene
-from train import (DATASETS, NET_TAGS, SMOOTH_TAG, SP_TAG, SPATIAL_MODES, SYNTH, RelScore, add_propagate_flags, add_smooth_flags,
-                   add_superpixel_flags, calibration_split, ensemble_whole, evaluate_whole, propagate_nodes, propagate_of,
-                   smooth_of, smooth_whole, superpixel_of, superpixel_whole, temper_stage, tta_tag, tta_whole)
+from scene_report import (NET_TAGS, PRINT, SCORE, SILENT, RelScore, SceneJob, build_nets, calibration_split, ensemble_first,
+                          evaluate_whole, print_block, print_result, run_scene, smooth_stage, superpixel_stage, temper_stage,
+                          tta_first, tta_tag)
+from train import (DATASETS, SPATIAL_MODES, SYNTH, add_propagate_flags, add_smooth_flags, add_superpixel_flags, on_device,
+                   propagate_nodes, propagate_of, smooth_of, superpixel_of)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
@@ -159,59 +163,55 @@ def check_propagate_args(args):
                          "--entropy, --tta, --smooth or --temperature")
 
 
-def training_pixels(args, ck, shape, whole, on):
-    """(spectra, labels) of the labelled training pixels on the device: the gallery of --knn_gallery train, the seeds of
-    --propagate"""
+def training_pixels(args, ck, job):
+    """(spectra, labels) of the labelled training pixels on the device: the gallery of --knn_gallery train, --propagate's seeds"""
     if args.synthetic:          # the labelled split train.py --synthetic drew (its flags are in the checkpoint)
         from hsi_loader import SyntheticHSIDataSet
         saved = ck["extra"].get("args", {})
-        scene = whole if (saved.get("windows") == "cube" or saved.get("synthetic_scene")) else None
-        lab = SyntheticHSIDataSet(shape, saved.get("num_unlabel", 10000), 'label', seed=1, scene=scene)
+        scene = job.whole if (saved.get("windows") == "cube" or saved.get("synthetic_scene")) else None
+        lab = SyntheticHSIDataSet(job.shape, saved.get("num_unlabel", 10000), 'label', seed=1, scene=scene)
     else:
         lab = HSIDataSet(int(args.dataID), 'label')
-    return on(lab.X, torch.float32), on(lab.Y, torch.int64)
+    return on_device(lab.X, torch.float32, job.device), on_device(lab.Y, torch.int64, job.device)
 
 
-def propagate_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=None):
+def labelled_spectra(job):
+    """the spectra of the labelled test pixels, as the dataset keeps them"""
+    rows = np.asarray(job.test_array, np.int64)
+    return job.whole.X[rows] if torch.is_tensor(job.whole.X) else np.asarray(job.whole.X[rows])
+
+
+def propagate_main(args, ck, job, hp, which, members, score=None):
     """--propagate: label propagation over the kNN graph of the embedding of the training and test pixels, per network of --net"""
     from cmlpl_amd.labelprop import propagate_embedding, score_labels
-    from train import build_nets
-    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
-    rows = np.asarray(test_array, np.int64)
-    Xt = whole.X[rows] if torch.is_tensor(whole.X) else np.asarray(whole.X[rows])
-    spectra, seeds = propagate_nodes(*training_pixels(args, ck, shape, whole, on), Xt, device)
-    first, truth = len(seeds) - len(rows), np.asarray(Y_test, np.int64)
+    K = job.shape[4]
+    spectra, seeds = propagate_nodes(*training_pixels(args, ck, job), labelled_spectra(job), job.device)
+    first, truth = len(seeds) - len(job.test_array), np.asarray(job.Y_test, np.int64)
     cfg = propagate_of(args)
-    models = build_nets(shape, members, device, hp["dropout"])
+    models = build_nets(job.shape, members, job.device, job.dropout)
     out = None
     for key, model in zip(which, models):
         model.eval()
         with torch.no_grad():
-            graph, res = propagate_embedding(model, spectra, seeds, shape[4], cfg, residual=True)[0]
+            graph, res = propagate_embedding(model, spectra, seeds, K, cfg, residual=True)[0]
         labels = res.labels[first:].cpu().numpy()
         tag = '_lp' + NET_TAGS[key]
         print('propagate%s: nodes=%d edges=%d max_in_degree=%d unreached=%d residual=%.3e' %
               (NET_TAGS[key], len(seeds), graph.edges(), graph.max_in_degree(), int((labels < 0).sum()), float(res.residual.cpu()[0])))
-        OA, Kappa, producerA, AA, _ = score_labels(labels, truth, shape[4])
-        print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
-        print('producerA%s:' % tag, producerA * 100)
-        print('AA%s=%.2f' % (tag, AA * 100))
+        print_block(tag, *score_labels(labels, truth, K)[:4])     # (an unreached node is -1: not CalAccuracy's to score)
         if score is not None:
             score(tag, res._replace(probs=res.probs[first:].clone()))      # (a buffer of its own: the test rows' block)
         out = labels if out is None else out
     return out
 
 
-def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=None):
+def knn_main(args, ck, job, hp, which, members, score=None):
     """--knn / --embed: the embedding of the labelled test pixels under the networks of --net, and its kNN vote"""
     from cmlpl_amd import NetShape
     from cmlpl_amd.knn import KnnEvaluator, embed
-    from train import build_nets, print_result
-    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
-    rows = np.asarray(test_array, np.int64)
-    Xt = on(whole.X[rows] if torch.is_tensor(whole.X) else np.asarray(whole.X[rows]), torch.float32)
-    Yt = on(np.asarray(Y_test), torch.int64)
-    models = build_nets(shape, members, device, hp["dropout"])
+    Xt = on_device(labelled_spectra(job), torch.float32, job.device)
+    Yt = on_device(np.asarray(job.Y_test), torch.int64, job.device)
+    models = build_nets(job.shape, members, job.device, job.dropout)
     for model in models:
         model.eval()
     if args.embed:
@@ -219,22 +219,75 @@ def knn_main(args, ck, shape, hp, device, whole, test_array, Y_test, which, memb
     if args.knn is None:
         return None
     loo = args.knn_gallery == 'loo'
-    if loo:
-        gallery = (Xt, Yt)
-    else:
-        gallery = training_pixels(args, ck, shape, whole, on)
+    gallery = (Xt, Yt) if loo else training_pixels(args, ck, job)
     T = hp.get("temperature", 0.3) if args.knn_T is None else args.knn_T
-    ev = KnnEvaluator(NetShape(*shape), *gallery, *((None, None) if loo else (Xt, Yt)), k=args.knn, T=T, loo=loo)
+    ev = KnnEvaluator(NetShape(*job.shape), *gallery, *((None, None) if loo else (Xt, Yt)), k=args.knn, T=T, loo=loo)
     first = None
     for key, model in zip(which, models):
         ev.evaluate(model)
         tag = '_knn' + NET_TAGS[key]
         labels = ev.last.labels[0].cpu().numpy()
-        print_result(tag, labels, np.arange(len(rows)), np.asarray(Y_test))
+        print_result(tag, labels, np.arange(len(job.test_array)), np.asarray(job.Y_test))
         if score is not None:
             score(tag, ev.last._replace(probs=ev.last.probs[0]))
         first = labels if first is None else first
     return first
+
+
+def networks_of(args):
+    """the networks --net names: keys of NET_TAGS, in the order of their blocks"""
+    return {'both': [0, 1], 'ema_both': ['ema0', 'ema1'], **ENSEMBLES}.get(args.net) or \
+        [args.net if args.net.startswith('ema') else int(args.net)]
+
+
+# What a scene prediction does.  ``evaluate``: ``evaluate_whole`` first (networks one by one: their ``Result:`` blocks as ever).
+# ``first_block`` None: nothing more; else one ``run_scene`` -- ``tta`` (None: ``ensemble_first``; of one network: its own softmax)
+# under ``tag``, then ``stages`` = (('smooth' | 'superpixel' | 'temper', its configuration), ..).  ``labels``: the map is the LAST
+# stage's, the argmax of one network's logits from EVALUATE, or two such maps STACKED.
+Plan = namedtuple('Plan', 'evaluate tta tag stages first_block labels')
+LAST, EVALUATE, STACKED = 'last', 'evaluate', 'stacked'
+
+
+def plan(args, has_test, noise=0.0):
+    """the ``Plan`` of a checked command line; ``has_test``: the labelled test pixels exist; ``noise``: the default of --tta_noise"""
+    temperature = temperature_of(args)
+    if not has_test and (args.reliability or temperature == 'fit'):
+        raise SystemExit("--reliability / --temperature fit need the labelled test pixels (test_array.npy and Y.npy in the "
+                         "dataset directory)")
+    tta = None if args.tta is None else TTA(args.tta, noise if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
+                                            clean=not args.tta_no_clean, spatial=args.tta_spatial)
+    together = tta is not None or args.net in ENSEMBLES
+    tag = (NET_TAGS['ens'] if tta is None else tta_tag(tta)) if together else NET_TAGS[networks_of(args)[0]]
+    # the regions vote behind --smooth and in front of --temperature, which tempers the FINAL probabilities
+    stages = tuple((name, cfg) for name, cfg in (('smooth', smooth_of(args)), ('superpixel', superpixel_of(args)),
+                                                 ('temper', temperature)) if cfg is not None)
+    if together:
+        return Plan(False, tta, tag, stages, PRINT, LAST)
+    # one network: its block comes from evaluate_whole; its own softmax is scored, handed to the stages or written, silently
+    runs = stages or args.reliability or args.proba or args.confidence or args.entropy
+    return Plan(True, None, tag, stages, (SCORE if args.reliability else SILENT) if runs else None,
+                LAST if stages else STACKED if args.net in ('both', 'ema_both') else EVALUATE)
+
+
+def build_stages(todo, job, args, fit=None):
+    """the ``scene_report`` stages of ``Plan.stages``; ``fit``: the (rows, truth) on the device that --temperature fit fits on"""
+    make = dict(smooth=smooth_stage, superpixel=lambda sp: superpixel_stage(sp, job, args.save_segments),
+                temper=lambda T: temper_stage(None if T == 'fit' else T, fit))
+    return [make[name](cfg) for name, cfg in todo]
+
+
+def calibration(args, todo, job):
+    """(fit, score) of a scene prediction: the (rows, truth) on the device that --temperature fit fits on -- a seeded share of
+    the labelled test pixels -- and the ``RelScore`` of --reliability, which then counts on the held-out remainder (or None)"""
+    fit = held = None
+    if ('temper', 'fit') in todo.stages:
+        fit, held = calibration_split(len(job.test_array), CALIB_FRAC if args.calib_frac is None else args.calib_frac,
+                                      CALIB_SEED if args.calib_seed is None else args.calib_seed)
+        if len(fit) < 1 or len(held) < 1:
+            raise SystemExit("--temperature fit: the calibration share or its remainder is empty (%d labelled test pixels)" % len(job.test_array))
+        fit = tuple(torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.int64)[fit])).to(job.device) for v in (job.test_array, job.Y_test))
+    bins = REL_BINS if args.rel_bins is None else args.rel_bins
+    return fit, RelScore(job.test_array, job.Y_test, job.device, bins, held) if args.reliability else None
 
 
 def main(args, device=None):
@@ -262,18 +315,13 @@ def main(args, device=None):
         if os.path.exists(whole.root + 'test_array.npy') and os.path.exists(whole.root + 'Y.npy'):
             test_array = np.load(whole.root + 'test_array.npy')
             Y_test = (np.load(whole.root + 'Y.npy') - 1)[test_array]
-    which = {'both': [0, 1], 'ema_both': ['ema0', 'ema1'], **ENSEMBLES}.get(args.net) or \
-        [args.net if args.net.startswith('ema') else int(args.net)]
-    temperature = temperature_of(args)
-    if test_array is None and (args.reliability or temperature == 'fit'):
-        raise SystemExit("--reliability / --temperature fit need the labelled test pixels (test_array.npy and Y.npy in the "
-                         "dataset directory)")
+    which = networks_of(args)
+    todo = plan(args, test_array is not None, hp["noise"])
     if any(str(k).startswith('ema') for k in which) and ("Teacher" not in ck or "Teacher1" not in ck):
         raise SystemExit("--net %s: %s holds no EMA teacher (\"Teacher\" / \"Teacher1\"): it was written by a run "
                          "without train.py --ema" % (args.net, args.ckpt))
     keys = {0: "Base", 1: "Base1", 'ema0': "Teacher", 'ema1': "Teacher1"}
-    extras = dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy))
-    common = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=hp["dropout"], test_array=test_array, Y_test=Y_test)
+    job = SceneJob(shape, whole, device, args.synthetic, args.dataID, hp["dropout"], test_array, Y_test)
     members = [(k, ck[keys[k]]) for k in which]
     propagate = getattr(args, 'propagate', False)
     if args.knn is not None or args.embed or propagate:
@@ -283,66 +331,25 @@ def main(args, device=None):
         # (the blocks are over the test LIST: position i of a probability map is test pixel i)
         score = RelScore(np.arange(len(test_array)), Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins) \
             if args.reliability else None
-        out, todo = None, [knn_main] * (args.knn is not None or bool(args.embed)) + [propagate_main] * bool(propagate)
-        for stage in todo:                  # _knn first, then _lp
-            labels = stage(args, ck, shape, hp, device, whole, test_array, Y_test, which, members, score=score)
+        out = None
+        for stage in [knn_main] * (args.knn is not None or bool(args.embed)) + [propagate_main] * bool(propagate):  # _knn, then _lp
+            labels = stage(args, ck, job, hp, which, members, score=score)
             out = labels if out is None else out
         if args.save_reliability and (args.knn is not None or propagate):
             score.save(args.save_reliability)
         return out
-    smooth, sp, tta = smooth_of(args), superpixel_of(args), None
-    if args.tta is not None:
-        from cmlpl_amd.tta import TTA
-        tta = TTA(args.tta, hp["noise"] if args.tta_noise is None else args.tta_noise, seed=args.tta_seed,
-                  clean=not args.tta_no_clean, spatial=args.tta_spatial)
-    # calibration (no keyword at all without its flags): the Reliability line behind every block, the tempering stage behind the last
-    together = tta is not None or args.net in ENSEMBLES
-    tag = (NET_TAGS['ens'] if tta is None else tta_tag(tta)) if together else NET_TAGS[which[0]]
-    calib, score = {}, None
-    if args.reliability or temperature is not None:
-        fit = held = None
-        if temperature == 'fit':
-            fit, held = calibration_split(len(test_array), CALIB_FRAC if args.calib_frac is None else args.calib_frac,
-                                          CALIB_SEED if args.calib_seed is None else args.calib_seed)
-            if len(fit) < 1 or len(held) < 1:
-                raise SystemExit("--temperature fit: the calibration share or its remainder is empty (%d labelled test pixels)" % len(test_array))
-            on = lambda v: torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.int64)[fit])).to(device)
-            fit = (on(test_array), on(Y_test))
-        if args.reliability:
-            score = calib['score'] = RelScore(test_array, Y_test, device, REL_BINS if args.rel_bins is None else args.rel_bins, held)
-        if temperature is not None:
-            calib['then'] = [temper_stage(tag + (SMOOTH_TAG if smooth is not None else '') + (SP_TAG if sp is not None else ''),
-                                          None if temperature == 'fit' else temperature,
-                                          fit=fit, **dict(extras, probs=extras['probs'] or args.reliability))]
-    if sp is not None:              # the regions vote behind --smooth and in front of --temperature
-        if not together:            # one network: its Result: block as ever, then its own softmax (a one-member ensemble)
-            evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
-        out = superpixel_whole(shape, whole, members, device, sp, smooth=smooth, tta=tta, tag=tag, raw_block=together,
-                               save_segments=args.save_segments, **common, **extras, **calib,
-                               **(dict(score_raw=True) if score is not None and not together else {}))
-    elif smooth is not None and together:
-        out = smooth_whole(shape, whole, members, device, smooth, tta=tta, tag=tag, raw_block=True, **common, **extras, **calib)
-    elif tta is not None:
-        out = tta_whole(shape, whole, members, device, tta, **common, **extras, **calib)
-    elif args.net in ENSEMBLES:
-        out = ensemble_whole(shape, whole, members, device, **common, **extras, **calib)
-    elif smooth is not None:        # one network: its Result: block as ever, then its own softmax (a one-member ensemble) smoothed
-        evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
-        out = smooth_whole(shape, whole, members, device, smooth, tag=tag, **common, **extras, **calib,
-                           **(dict(score_raw=True) if score is not None else {}))
-    elif calib:                     # one network: its Result: block as ever, then its own softmax scored and / or tempered
-        preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
-        out = ensemble_whole(shape, whole, members[:1], device, **common, **extras, **calib, raw_block=False, tag=tag,
-                             **(dict(score_raw=True) if score is not None else {}))
-        if temperature is None:     # (its label map stays the argmax of its logits)
-            out["labels"] = np.asarray(preds[which[0]]).astype(np.int64)
-    else:
-        preds = evaluate_whole(shape, whole, members, device, val_batch_size=args.val_batch_size, **common)
+    fit, score = calibration(args, todo, job)
+    preds = evaluate_whole(job, members, val_batch_size=args.val_batch_size) if todo.evaluate else None
+    out = {}
+    if todo.first_block is not None:
+        if todo.first_block == SILENT and not todo.stages:     # (nothing is printed: the softmax is only written)
+            job = job._replace(test_array=None)
+        first = ensemble_first(todo.tag) if todo.tta is None else tta_first(todo.tta)
+        out = run_scene(job, members, first, build_stages(todo.stages, job, args, fit), first_block=todo.first_block, score=score,
+                        want=dict(probs=bool(args.proba), conf=bool(args.confidence), entropy=bool(args.entropy)))
+    if todo.labels != LAST:         # (a network nothing re-labels keeps the argmax of its logits as its label map)
         labels = np.stack([preds[k] for k in which]).astype(np.int64)
-        # the network's own softmax: a one-member ensemble, silent (the Result: lines above are the argmax of its logits)
-        out = ensemble_whole(shape, whole, members[:1], device, **dict(common, test_array=None), **extras) \
-            if any(extras.values()) else {}
-        out["labels"] = labels if args.net in ('both', 'ema_both') else labels[0]
+        out["labels"] = labels if todo.labels == STACKED else labels[0]
     for path, key in ((args.proba, "probs"), (args.confidence, "conf"), (args.entropy, "entropy")):
         if path:
             np.save(path, out[key])

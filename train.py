@@ -86,8 +86,8 @@ import torch
 
 from cmlpl_amd import HyperParams, NetShape, checkpoint
 from hsi_loader import HSIDataSet, SyntheticHSIDataSet, SyntheticScene
-from tools.hyper_tools import CalAccuracy, test_whole
-from tools.models import BaseNet2
+from scene_report import (NET_TAGS, PRINT, SILENT, SMOOTH_TAG, SP_TAG, RelScore, SceneJob, build_nets, calibration_split,  # noqa: F401
+                          ensemble_first, evaluate_whole, run_scene, smooth_stage, superpixel_stage, tta_first, tta_tag, tta_timing)
 
 DATASETS = {1: (9, 103), 2: (16, 204), 3: (15, 144), 4: (16, 200)}     # num_classes, num_features (train.py:75-90)
 SYNTH = {"B2": (103, 11, 11, 103, 9), "P": (60, 20, 20, 103, 9), "B4": (200, 11, 11, 200, 16),
@@ -193,11 +193,16 @@ def propagate_of(args):
         raise SystemExit("--propagate: --lp_%s" % e)
 
 
+def on_device(a, dt, device):
+    """a tensor or array as a contiguous tensor of dtype ``dt`` on ``device``"""
+    return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
+
+
 def propagate_nodes(seeds_X, seeds_Y, test_X, device):
     """the nodes of --propagate: (spectra float32 [n, bands], seed labels int64 [n], -1 for a test pixel) -- the labelled
     training pixels followed by the labelled test pixels"""
-    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
-    seeds_X, seeds_Y, test_X = on(seeds_X, torch.float32), on(seeds_Y, torch.int64), on(test_X, torch.float32)
+    seeds_X, seeds_Y, test_X = (on_device(a, dt, device) for a, dt in
+                                ((seeds_X, torch.float32), (seeds_Y, torch.int64), (test_X, torch.float32)))
     return (torch.cat([seeds_X, test_X]).contiguous(),
             torch.cat([seeds_Y, torch.full((test_X.shape[0],), -1, dtype=torch.int64, device=device)]))
 
@@ -276,11 +281,7 @@ class EvalCurve:
         return 'best validation%s%s: epoch %d OA = %.2f' % (self.suffix, NET_TAGS[net or 0], self.epochs[int(np.argmax(oa))], oa.max() * 100)
 
 
-NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whole: a network, or a network's EMA teacher
-            'ens': '_ens',                                         # ensemble_whole: several of them together
-            'tta': '_tta'}                                         # tta_whole: over noisy views of every pixel
 SPATIAL_MODES = ('none', 'flips', 'd4')                            # --aug_spatial / --tta_spatial (cmlpl_amd._lib.SPATIAL)
-SMOOTH_TAG = '_smooth'                                             # smooth_whole: appended to the tag of what it smooths
 SMOOTH_FLAGS = ('smooth', 'smooth_sigma_s', 'smooth_sigma_r', 'smooth_guide', 'smooth_iters')
 
 
@@ -316,7 +317,6 @@ def smooth_of(args):
     return smooth
 
 
-SP_TAG = '_sp'                                                     # superpixel_stage: appended to the tag of what votes
 SP_FLAGS = ('superpixel', 'sp_compact', 'sp_iters', 'sp_guide', 'sp_vote', 'save_segments')
 
 
@@ -356,281 +356,6 @@ def superpixel_of(args):
     except ValueError as e:
         raise SystemExit("--superpixel: %s" % str(e).replace("Superpixel: ", ""))
     return sp
-
-
-def tta_tag(tta):
-    """the tag of a TTA prediction's ``Result:`` lines: ``_tta``, with ``_flips`` / ``_d4`` behind it when its views are spatial"""
-    return NET_TAGS['tta'] + ('' if tta.spatial == 'none' else '_' + tta.spatial)
-
-
-def tta_timing(tta):
-    """the timing line of a TTA prediction (a format of the seconds and the number of networks)"""
-    return 'tta inference time == %%.3f s (%%d networks x %d views%s, noise %g%s)' % (
-        tta.views, ' + the clean window' if tta.clean else '', tta.sigma,
-        '' if tta.spatial == 'none' else ', spatial ' + tta.spatial)
-
-
-def print_result(tag, pred, test_array, Y_test):
-    """the ``Result:`` / ``producerA`` / ``AA`` lines (train.py:297-306) of one label map; returns its OA"""
-    OA, Kappa, producerA = CalAccuracy(pred[test_array], Y_test)
-    print('Result:\n OA%s=%.2f,Kappa=%.2f' % (tag, OA * 100, Kappa * 100))
-    print('producerA%s:' % tag, producerA * 100)
-    print('AA%s=%.2f' % (tag, np.mean(producerA) * 100))
-    return OA
-
-
-def scene_source(shape, whole, device, synthetic, dataID, resident_cube):
-    """the scene as a ``CubeSource`` for the cube-fed forward, or None: a window shape the per-sample forward does not
-    take, or a dataset directory without its cube.  ``resident_cube``: the scene already on the device."""
-    from cmlpl_amd.infer import infer_supported
-    if not infer_supported(NetShape(*shape)):
-        return None
-    if synthetic:      # (a SyntheticScene is its own scene; a directory without scene.json looks its scene up by dataID)
-        return whole.cube_source(device, resident_cube=resident_cube)
-    return whole.cube_source(device, dataID=dataID, resident_cube=resident_cube)
-
-
-def build_nets(shape, nets, device, dropout):
-    """the ``BaseNet2`` modules of ``nets`` = [(key, state_dict)], on ``device``, in that order"""
-    models = [BaseNet2(num_features=shape[3], dropout=dropout, num_classes=shape[4], in_channels=shape[0],
-                       window=shape[1]).to(device) for _ in nets]
-    for model, (_, sd) in zip(models, nets):
-        model.load_state_dict(sd)
-    return models
-
-
-TEMPER_TAG = '_T'                                                  # temper_stage: appended to the tag of what it tempers
-
-
-class RelScore:
-    """``--reliability``: the ``Reliability<tag>:`` line behind a ``Result:`` block -- the reliability counters of the block's
-    class probabilities over the labelled test pixels (cmlpl_amd.calibrate.reliability: one launch, one read-back).
-    ``held_out``: positions in ``test_array`` the lines are counted on (the rest fitted a temperature); the line says so.
-    ``blocks`` keeps the int64 counter block of every line, by tag."""
-
-    def __init__(self, test_array, Y_test, device, bins=15, held_out=None):
-        rows, truth = np.asarray(test_array, np.int64), np.asarray(Y_test, np.int64)
-        self.note = ''
-        if held_out is not None:
-            rows, truth = rows[held_out], truth[held_out]
-            self.note = ' (held-out n=%d)' % len(rows)
-        self.rows, self.truth = (torch.from_numpy(np.ascontiguousarray(v)).to(device) for v in (rows, truth))
-        self.bins, self.blocks = bins, {}
-
-    def __call__(self, tag, res):
-        from cmlpl_amd.calibrate import reliability
-        rel = reliability(res.probs, self.truth, self.rows, self.bins)
-        self.blocks[tag] = rel.counts
-        print(rel.line(tag, self.note))
-
-    def save(self, path):
-        np.savez(path, **{'Reliability' + tag: block for tag, block in self.blocks.items()})
-
-
-def calibration_split(n, frac, seed):
-    """(calibration, held-out) positions among n labelled test pixels: a seeded random share ``frac`` fits the temperature
-    (the first round(frac n) of numpy.random.default_rng(seed).permutation(n)), the remainder scores it"""
-    perm = np.random.default_rng(seed).permutation(n)
-    k = int(round(frac * n))
-    return perm[:k], perm[k:]
-
-
-def temper_stage(tag, T, probs=False, conf=False, entropy=False, fit=None):
-    """the stage of ``together_whole`` that tempers the probabilities in front of it (cmlpl_amd.calibrate.temper_probs): its
-    ``Result:`` lines carry ``tag`` + ``_T``.  ``T`` None: fitted first, on the pixels ``fit`` = (rows, truth) on the device"""
-    from cmlpl_amd.calibrate import fit_temperature, temper_probs
-
-    def call(res, cube):
-        t = T
-        if t is None:
-            t, before, after = fit_temperature(res.probs, fit[1], fit[0])
-            print('temperature = %.4f (NLL %.4f -> %.4f on the calibration share)' % (t, before, after))
-        return temper_probs(res.probs, t, probs_out=probs, conf=conf, entropy=entropy)
-    return ('tempering time == %%.3f s (T %s)' % ('fitted' if T is None else '%g' % T), tag + TEMPER_TAG, call)
-
-
-def together_whole(predict, timing, tag, noun, shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-                   then=(), raw_block=True, score=None, score_raw=None):
-    """the body of ``ensemble_whole``, ``tta_whole`` and ``smooth_whole``: ``predict(models, cube, spectra)`` is the library call,
-    ``timing`` its printed line (a format of the seconds and the number of networks), ``tag`` that of its ``Result:`` lines
-    (``raw_block`` False: not printed), ``noun`` who asks.  ``then`` = [(timing, tag, call), ..]: further stages, each
-    ``call(result, cube)`` on the result in front of it, with a line and a block of its own; the outputs of the last one are
-    the ones returned.  ``score(tag, result)`` (a ``RelScore``) is called behind every block (``score_raw``: behind the first
-    stage also where its block is printed elsewhere; default: where ``raw_block``)."""
-    source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
-    if source is None:
-        raise SystemExit("%s needs the scene cube (cube.npy + scene.json in the dataset directory, "
-                         "sample_generation.py) and a square window" % noun)
-    models = [model.eval() for model in build_nets(shape, nets, device, dropout)]
-    t1 = time.time()
-    res = predict(models, source.cube, source.spectra)
-    out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
-    print(timing % (time.time() - t1, len(models)))
-    if test_array is not None and raw_block:
-        print_result(tag, out["labels"], test_array, Y_test)
-    if score is not None and (raw_block if score_raw is None else score_raw):
-        score(tag, res)
-    for timing, tag, call in then or ():
-        t1 = time.time()
-        res = call(res, source.cube)
-        out = {k: v.cpu().numpy() for k, v in zip(("labels", "probs", "conf", "entropy"), res[:4]) if v is not None}
-        print(timing % (time.time() - t1))
-        if test_array is not None:
-            print_result(tag, out["labels"], test_array, Y_test)
-        if score is not None:
-            score(tag, res)
-    return out
-
-
-def ensemble_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
-                   resident_cube=None, weights=None, probs=False, conf=False, entropy=False, raw_block=True, then=(), score=None,
-                   score_raw=None, tag=None):
-    """Whole-image ENSEMBLE of ``nets`` = [(key, state_dict)] (1..4 networks, ``evaluate_whole``'s list): the label of their
-    averaged softmax for every scene pixel, and its probabilities / confidence / entropy when asked for
-    (cmlpl_amd.ensemble.ensemble_cube: every member's eval forward from the resident cube, one launch behind each chunk).
-    Returns {'labels': int64 [pixels], 'probs': float32 [pixels, K], 'conf', 'entropy': float32 [pixels]} (numpy; what was
-    not asked for is absent) and prints the ``Result:`` lines with the tag ``_ens`` when the test pixels are given.  It
-    needs the scene as its cube: there is no loader fall-back."""
-    from cmlpl_amd.ensemble import ensemble_cube
-    probs = probs or bool(then) or score is not None            # (what follows reads the probabilities)
-    return together_whole(
-        lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=probs, conf=conf, entropy=entropy),
-        'ensemble inference time == %.3f s (%d networks)', NET_TAGS['ens'] if tag is None else tag, "the ensemble",
-        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-        then=then, raw_block=raw_block, score=score, score_raw=score_raw)
-
-
-def tta_whole(shape, whole, nets, device, tta, synthetic=None, dataID=1, dropout=0.8, test_array=None, Y_test=None,
-              resident_cube=None, weights=None, probs=False, conf=False, entropy=False, then=(), score=None):
-    """``ensemble_whole`` over the noisy views of ``tta`` (cmlpl_amd.tta.TTA): every network of ``nets`` scores every view
-    of every scene pixel, one label map from the average of all their softmaxes (cmlpl_amd.tta.tta_cube).  Same returns;
-    the ``Result:`` lines carry the tag ``_tta`` (``_tta_flips`` / ``_tta_d4`` when the views are spatial, ``tta_tag``)."""
-    from cmlpl_amd.tta import tta_cube
-    probs = probs or bool(then) or score is not None
-    return together_whole(
-        lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=probs, conf=conf, entropy=entropy),
-        tta_timing(tta), tta_tag(tta), "test-time augmentation",
-        shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube, then=then, score=score)
-
-
-def raw_prediction(tta=None, weights=None):
-    """(predict, timing) of ``together_whole`` for the prediction that later stages read: ``ensemble_cube`` (``tta``:
-    ``tta_cube``) with its probabilities"""
-    if tta is None:
-        from cmlpl_amd.ensemble import ensemble_cube
-        return (lambda models, cube, spectra: ensemble_cube(models, cube, spectra, weights=weights, probs=True),
-                'ensemble inference time == %.3f s (%d networks)')
-    from cmlpl_amd.tta import tta_cube
-    return lambda models, cube, spectra: tta_cube(models, cube, spectra, tta, weights=weights, probs=True), tta_timing(tta)
-
-
-def smooth_stage(tag, smooth, probs=False, conf=False, entropy=False):
-    """the stage of ``together_whole`` that smooths the probabilities in front of it (cmlpl_amd.smooth.smooth_probs): its
-    ``Result:`` lines carry ``tag`` + ``_smooth``"""
-    from cmlpl_amd.smooth import smooth_probs
-    R, ss, sr, G, iters = smooth.params()
-    return ('smoothing time == %%.3f s (radius %d, sigma_s %g, sigma_r %g, up to %d guide channels, %d pass%s)' %
-            (R, ss, sr, G, iters, '' if iters == 1 else 'es'), tag + SMOOTH_TAG,
-            lambda res, cube: smooth_probs(res.probs, cube, smooth, probs_out=probs, conf=conf, entropy=entropy))
-
-
-def superpixel_stage(tag, sp, K, probs=False, conf=False, entropy=False, test_array=None, Y_test=None, save_segments=None):
-    """the stage of ``together_whole`` in which the regions vote (cmlpl_amd.superpixel.superpixel_probs): the scene is
-    segmented, every superpixel votes with the probabilities (``--sp_vote hard``: the labels) in front of it, and one line
-    ``superpixel: segments= empty= mean_size= max_size= ASA=`` says what the map is (ASA on the labelled test pixels: the
-    accuracy no region-level labelling of this map can exceed).  Its ``Result:`` lines carry ``tag`` + ``_sp``."""
-    from cmlpl_amd.superpixel import asa, superpixel_probs
-    S, m, T, G, vote = sp.params()
-
-    def call(res, cube):
-        out = superpixel_probs(res.probs, cube, sp, labels=res.labels, probs_out=probs, conf=conf, entropy=entropy)
-        segs = out.segments
-        counts = segs.counts.cpu().numpy()
-        bound = 'n/a' if test_array is None else '%.4f' % asa(segs.seg, segs.N, test_array, Y_test, K)
-        print('superpixel: segments=%d empty=%d mean_size=%.1f max_size=%d ASA=%s' %
-              (segs.N, int((counts == 0).sum()), counts.sum() / segs.N, counts.max(), bound))
-        if save_segments:
-            np.save(save_segments, segs.seg.cpu().numpy())
-        return out
-    return ('superpixel time == %%.3f s (step %d, compactness %g, %d iterations, up to %d guide channels, %s vote)' %
-            (S, m, T, G, vote), tag + SP_TAG, call)
-
-
-def superpixel_whole(shape, whole, nets, device, sp, smooth=None, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None,
-                     dataID=1, dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False,
-                     entropy=False, then=(), score=None, score_raw=None, save_segments=None):
-    """``ensemble_whole`` (``tta``: ``tta_whole``), smoothed first when ``smooth`` is given (its block under ``tag`` +
-    ``_smooth``, as ``smooth_whole`` prints it), followed by the region vote over the scene's superpixels (``sp``: a
-    cmlpl_amd.superpixel.Superpixel).  Same returns, of the VOTED prediction; its ``Result:`` lines carry the tag in front
-    of it + ``_sp``.  ``raw_block``: the ``Result:`` block of the first prediction is printed, under ``tag``."""
-    raw, timing = raw_prediction(tta, weights)
-    sp.params()
-    probs = probs or bool(then) or score is not None            # (what follows the vote reads its probabilities)
-    stages, at = [], tag
-    if smooth is not None:
-        stages.append(smooth_stage(at, smooth, probs=True))
-        at += SMOOTH_TAG
-    stages.append(superpixel_stage(at, sp, shape[4], probs=probs, conf=conf, entropy=entropy, test_array=test_array,
-                                   Y_test=Y_test, save_segments=save_segments))
-    return together_whole(
-        raw, timing, tag, "the superpixel vote", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test,
-        resident_cube, then=[*stages, *then], raw_block=raw_block, score=score, score_raw=score_raw)
-
-
-def smooth_whole(shape, whole, nets, device, smooth, tta=None, tag=NET_TAGS['ens'], raw_block=False, synthetic=None, dataID=1,
-                 dropout=0.8, test_array=None, Y_test=None, resident_cube=None, weights=None, probs=False, conf=False, entropy=False,
-                 then=(), score=None, score_raw=None):
-    """``ensemble_whole`` (``tta``: ``tta_whole``) followed by the edge-preserving spatial smoothing of its class probability
-    maps under the guide of the scene cube (``smooth``: a cmlpl_amd.smooth.Smooth; what cmlpl_amd.smooth.smooth_cube
-    does, in its two halves).  Same returns, of the SMOOTHED prediction; its ``Result:`` lines carry ``tag`` + ``_smooth``.
-    ``raw_block``: the ``Result:`` block of the un-smoothed prediction is printed in front of it, under ``tag``."""
-    raw, timing = raw_prediction(tta, weights)
-    probs = probs or bool(then) or score is not None            # (what follows the smoothing reads its probabilities)
-    return together_whole(
-        raw, timing, tag, "spatial smoothing", shape, whole, nets, device, synthetic, dataID, dropout, test_array, Y_test, resident_cube,
-        then=[smooth_stage(tag, smooth, probs=probs, conf=conf, entropy=entropy), *then],
-        raw_block=raw_block, score=score, score_raw=score_raw)
-
-
-def evaluate_whole(shape, whole, nets, device, synthetic=None, dataID=1, dropout=0.8, val_batch_size=512,
-                   test_array=None, Y_test=None, resident_cube=None, last_eval=None):
-    """Whole-image inference + accuracy (train.py:291-306) of ``nets`` = [(network index -- or 'ema0' / 'ema1', a network's
-    EMA teacher --, state_dict)]: the end of a training run, and all of predict.py.  Returns {network index: int64 label per scene pixel}.
-    The scene stays in HBM as its cube and the forward gathers the windows itself (cmlpl_infer_cube): no 19.9 GB patch
-    tensor, no DataLoader (train.py:291-294 streams the materialised patches).  Window shapes the per-sample forward does
-    not take, or a dataset directory without the cube, fall back to the loader.  The source is built ONCE for all
-    networks, and its load time is printed (the reference's "inference time" includes streaming the data).
-    ``test_array`` / ``Y_test``: the labelled test pixels and their classes -- the ``Result:`` lines are printed when
-    they are given.  ``resident_cube``: the scene already on the device (a cube-fed run evaluates on the cube it trained
-    from).  ``last_eval``: the [net][OA, AA, Kappa] row of --eval_every when it scored the same parameters."""
-    t_src = time.time()
-    source = scene_source(shape, whole, device, synthetic, dataID, resident_cube)
-    if source is None:
-        if synthetic:      # (cut the scene's windows on the device, then the reference's loader path)
-            from cmlpl_amd.patches import extract_patches
-            XPw = extract_patches(whole.cube_source(device).cube, torch.arange(len(whole), device=device), shape[1]).cpu()
-            source = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(XPw, whole.X),
-                                                 batch_size=val_batch_size, shuffle=False)
-        else:
-            source = torch.utils.data.DataLoader(whole, batch_size=val_batch_size, shuffle=False)
-    if device.type == "cuda":
-        torch.cuda.synchronize()
-    print('evaluation source ready in %.3f s' % (time.time() - t_src))
-    preds = {}
-    for (net, _), model in zip(nets, build_nets(shape, nets, device, dropout)):      # (test_whole sets .eval() itself)
-        t1 = time.time()
-        pred = preds[net] = test_whole(model, source, print_per_batches=10 ** 9)
-        print('inference time == %.3f s' % (time.time() - t1))
-        if test_array is None:
-            continue
-        tag = NET_TAGS[net]
-        OA = print_result(tag, pred, test_array, Y_test)
-        if last_eval is not None and net in (0, 1):
-            # the last epoch was scored by --eval_every too: both are exact counts on the same pixels
-            same = last_eval[net][0] == OA
-            print('validation check%s: matrix OA %s whole-image OA (%.6f / %.6f)' %
-                  (tag, '==' if same else '!=', last_eval[net][0] * 100, OA * 100))
-    return preds
 
 
 def load_data(run, args):
@@ -750,14 +475,12 @@ def build_knn(run, args):
     labelled training pixels UNTILED (5 per class: fewer candidates of a class than k is the normal case), the queries are
     the test split's; spectra and labels only, no cube"""
     from cmlpl_amd.knn import KnnEvaluator
-    device = run.device
-    on = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt).to(device).contiguous()
     if args.synthetic:
         gallery, queries = run.labeled, run.whole
     else:
         gallery, queries = HSIDataSet(int(args.dataID), 'label'), HSIDataSet(int(args.dataID), 'test')
-    run.knn = KnnEvaluator(NetShape(*run.shape), on(gallery.X, torch.float32), on(gallery.Y, torch.int64),
-                           on(queries.X, torch.float32), on(queries.Y, torch.int64), k=args.knn,
+    arrays = ((gallery.X, torch.float32), (gallery.Y, torch.int64), (queries.X, torch.float32), (queries.Y, torch.int64))
+    run.knn = KnnEvaluator(NetShape(*run.shape), *(on_device(a, dt, run.device) for a, dt in arrays), k=args.knn,
                            T=args.temperature if args.knn_T is None else args.knn_T)
 
 
@@ -1005,22 +728,22 @@ def report(run, args):
     nets = [(net, eng.state_dict(net)) for net in range(2)]
     if args.ema:
         nets += [('ema%d' % net, eng.teacher.state_dict(net)) for net in range(2)]
-    scene = dict(synthetic=args.synthetic, dataID=args.dataID, dropout=args.dropout, test_array=run.test_array,
-                 Y_test=run.Y_test, resident_cube=run.cube_kw.get("cube"))
-    evaluate_whole(run.shape, run.whole, nets, device, val_batch_size=args.val_batch_size,
-                   last_eval=base.rows[-1] if base.epochs and base.epochs[-1] == args.num_epochs else None, **scene)
-    # --reliability: one Reliability<tag>: line behind every block below (no keyword at all without the flag)
-    rel = dict(score=RelScore(run.test_array, run.Y_test, device)) if args.reliability and run.test_array is not None else {}
+    job = SceneJob(run.shape, run.whole, device, args.synthetic, args.dataID, args.dropout, run.test_array, run.Y_test,
+                   run.cube_kw.get("cube"))
+    evaluate_whole(job, nets, val_batch_size=args.val_batch_size,
+                   last_eval=base.rows[-1] if base.epochs and base.epochs[-1] == args.num_epochs else None)
+    # every report below is a prediction of its own, Base and Base1 together; --reliability: a Reliability<tag>: line behind each block
+    score = RelScore(run.test_array, run.Y_test, device) if args.reliability and run.test_array is not None else None
     if args.ensemble:
-        ensemble_whole(run.shape, run.whole, nets[:2], device, **scene, **rel)
+        run_scene(job, nets[:2], ensemble_first(), first_block=PRINT, score=score)
     if args.tta:
         from cmlpl_amd.tta import TTA
-        tta_whole(run.shape, run.whole, nets[:2], device, TTA(args.m, args.noise, spatial=args.tta_spatial), **scene, **rel)
-    if run.sp is not None:            # --superpixel: behind the smoothed block when --smooth is given, else behind the pair's
-        superpixel_whole(run.shape, run.whole, nets[:2], device, run.sp, smooth=run.smooth, save_segments=args.save_segments,
-                         **scene, **rel)
-    elif run.smooth is not None:
-        smooth_whole(run.shape, run.whole, nets[:2], device, run.smooth, **scene, **rel)
+        run_scene(job, nets[:2], tta_first(TTA(args.m, args.noise, spatial=args.tta_spatial)), first_block=PRINT, score=score)
+    # --smooth, then --superpixel behind the smoothed block (else behind the pair's, which is not printed again)
+    stages = ([smooth_stage(run.smooth)] if run.smooth is not None else []) + \
+        ([superpixel_stage(run.sp, job, args.save_segments)] if run.sp is not None else [])
+    if stages:
+        run_scene(job, nets[:2], ensemble_first(), stages, first_block=SILENT, score=score)
 
 
 def check_reliability_args(args, smooth, sp=None):

@@ -56,6 +56,7 @@ EXPORTS = (
     "cmlpl_sp_workspace_bytes", "cmlpl_sp_segment", "cmlpl_sp_vote_workspace_bytes",                 # added after ABI 6, no bump:
     "cmlpl_sp_vote_probs", "cmlpl_sp_vote_labels",                               # superpixels and region votes
     "cmlpl_patches_fit",                                                         # added after ABI 6, no bump: which windows the cuts take
+    "cmlpl_debug_ntxent_plan",                                                   # added after ABI 6, no bump: test aid (ntxent.hip)
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -333,6 +334,7 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_debug_loss_plan.argtypes = [SP, C.POINTER(Shard), i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_unsup_plan.argtypes = [i32, i32, C.POINTER(i32)]
     lib.cmlpl_debug_memobank_plan.argtypes = [i32, i32, i32, i32, C.POINTER(i32)]
+    lib.cmlpl_debug_ntxent_plan.argtypes = [i32, i32, i32, C.POINTER(i32)]
     OP = C.POINTER(Optim)
     lib.cmlpl_grad_norm_partials_bytes.argtypes = []
     lib.cmlpl_grad_norm_partials_bytes.restype = sz

@@ -1349,6 +1349,9 @@ int cmlpl_ntxent_fwd_bwd(const float* d_emb_i, const float* d_emb_j, int B, int 
   if (!d_emb_i || !d_emb_j || !d_loss || !d_grad_i || !d_grad_j || !d_workspace || B < 1 || D < 1 ||
       !(temperature > 0.f))
     return CMLPL_E_ARG;
+  NtxPlan plan;              // (a batch no route holds is refused here: nothing is launched, every output keeps its bytes)
+  const bool aligned = D % 4 == 0 && (((uintptr_t)d_emb_i | (uintptr_t)d_emb_j) & 15) == 0;
+  if (!plan_ntxent(B, D, aligned, &plan)) return CMLPL_E_ARG;
   if (ntxent_ws_floats(B, D) * 4 > workspace_bytes) return CMLPL_E_WORKSPACE;
   return chk(launch_ntxent(d_emb_i, d_emb_j, B, D, temperature, d_loss, d_grad_i, d_grad_j, (float*)d_workspace,
                            (hipStream_t)stream));
@@ -1610,6 +1613,15 @@ int cmlpl_debug_memobank_plan(int D, int K, int queries, int negatives, int* out
   MbPlan p;
   if (!out || !plan_mb_onepass(D, K, queries, negatives, &p)) return CMLPL_E_ARG;
   out[0] = p.kernel; out[1] = (int)p.lds_infonce; out[2] = (int)p.lds_scatter;
+  return 0;
+}
+
+int cmlpl_debug_ntxent_plan(int B, int D, int aligned, int* out) {
+  NtxPlan p;
+  if (!out || !plan_ntxent(B, D, aligned != 0 && D % 4 == 0, &p)) return CMLPL_E_ARG;
+  int* o = out;
+  *o++ = p.route; *o++ = p.ncw; *o++ = p.kc; *o++ = p.waves; *o++ = p.sim_gx; *o++ = p.sim_gy; *o++ = p.grad_gx;
+  *o++ = p.grad_gy; *o++ = (int)p.lds; *o++ = p.ct;
   return 0;
 }
 

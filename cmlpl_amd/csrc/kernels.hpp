@@ -399,6 +399,10 @@ hipError_t launch_cps_loss(const CpsArgs& a, float* ws, hipStream_t st);
 
 // ---- ntxent.hip
 size_t ntxent_ws_floats(int B, int D);
+// the launch plan of one call (plan_ntxent; launch_ntxent runs what it says and decides nothing itself)
+enum { NTX_VECTOR = 0, NTX_MFMA = 1 };              // NtxPlan.route: ntx_grad_kernel, ntx_grad_mfma_kernel<ncw, kc, waves>
+struct NtxPlan { int route, ncw, kc, waves, sim_gx, sim_gy, grad_gx, grad_gy, ct; size_t lds; };
+bool plan_ntxent(int B, int D, bool aligned, NtxPlan* p);
 hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T, float* loss, float* gi, float* gj,
                          float* ws, hipStream_t st);
 

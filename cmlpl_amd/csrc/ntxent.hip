@@ -438,22 +438,20 @@ size_t ntxent_ws_floats(int B, int D) {
   return N2 * N2 + CT * N2 + N2 + 64;
 }
 
-hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T, float* loss, float* gi, float* gj,
-                         float* ws, hipStream_t st) {
+// What one call runs, decided once on the host (cmlpl_debug_ntxent_plan shows it; launch_ntxent obeys it).  `aligned`:
+// D a multiple of 4 AND both embedding pointers on 16-byte boundaries -- the rows are then whole 16-byte pieces.
+//   * the MFMA gradient wherever the rows are aligned (CMLPL_NTX_MFMA=0: the vector kernel always), with the widest
+//     column slice (64 NCW columns per workgroup) that still gives 256 workgroups and fits LDS; CMLPL_NTX_NCW = 1 / 2 / 4
+//     names the slice instead (any other non-zero value: 1);
+//   * a slice that does not fit LDS -- planned or forced -- leaves the call to the vector kernel;
+//   * the vector kernel holds ten floats per row in 64 KiB: 2B <= 1632.  Beyond it (and beyond the single-slice MFMA
+//     kernel's 2B <= 1664 where the rows are aligned) no route fits: false, and nothing is launched.
+bool plan_ntxent(int B, int D, bool aligned, NtxPlan* p) {
+  if (B < 1 || D < 1) return false;
   const size_t N2 = 2 * (size_t)B;
-  const int CT = (int)((N2 + 31) / 32);
-  NtxArgs a;
-  a.ei = ei; a.ej = ej; a.B = B; a.D = D; a.T = T; a.loss = loss; a.gi = gi; a.gj = gj;
-  a.S = ws; ws += N2 * N2;
-  a.rs_part = ws; ws += (size_t)CT * N2;
-  a.nrm = ws;
-  const bool aligned = D % 4 == 0 && (((uintptr_t)ei | (uintptr_t)ej) & 15) == 0;
-  hipLaunchKernelGGL(ntx_sim_kernel, dim3(CT, (unsigned)((N2 + 15) / 16)), dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  // the MFMA gradient wherever the rows are whole 16-byte pieces (CMLPL_NTX_MFMA=0: the vector kernel always); the widest
-  // column slice (64 NCW columns per workgroup) that still gives every CU a workgroup and fits LDS
   const size_t N2p = ((N2 + 63) / 64) * 64;
+  p->ct = (int)((N2 + 31) / 32);
+  p->sim_gx = p->ct; p->sim_gy = (int)((N2 + 15) / 16);
   if (aligned && switches().ntx_mfma != 0) {
     const unsigned rg = (unsigned)((N2 + NTG_R - 1) / NTG_R);
     auto lds_of = [&](int ncw, int kc) { return ((((2 * N2 + 128) + 3) & ~(size_t)3) + N2p * NTG_R + 2 * (size_t)kc * ntg_bs(ncw)) * 4; };
@@ -465,29 +463,54 @@ hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T
       if (wgs_of(2) >= 256 && lds_of(2, 64) <= LDS_MAX) ncw = 2;
       if (wgs_of(4) >= 256 && lds_of(4, 32) <= LDS_MAX) ncw = 4;
     }
-    const size_t lds_m = lds_of(ncw, ncw == 4 ? 32 : 64);
+    const int kc = ncw == 4 ? 32 : 64;
+    const size_t lds_m = lds_of(ncw, kc);
     if (lds_m <= LDS_MAX) {
-      const dim3 grid(rg, (unsigned)((D + 64 * ncw - 1) / (64 * ncw)));
-      if (ncw == 4) {
-        static DevOnce once;
-        if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<4, 32, 8>)) != hipSuccess) return e;
-        hipLaunchKernelGGL((ntx_grad_mfma_kernel<4, 32, 8>), grid, dim3(512), lds_m, st, a, CT);
-      } else if (ncw == 2) {
-        static DevOnce once;
-        if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<2, 64>)) != hipSuccess) return e;
-        hipLaunchKernelGGL((ntx_grad_mfma_kernel<2, 64>), grid, dim3(256), lds_m, st, a, CT);
-      } else {
-        static DevOnce once;
-        if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<1, 64>)) != hipSuccess) return e;
-        hipLaunchKernelGGL((ntx_grad_mfma_kernel<1, 64>), grid, dim3(256), lds_m, st, a, CT);
-      }
-      return hipGetLastError();
+      p->route = NTX_MFMA; p->ncw = ncw; p->kc = kc; p->waves = ncw == 4 ? 8 : 4;
+      p->grad_gx = (int)rg; p->grad_gy = (D + 64 * ncw - 1) / (64 * ncw); p->lds = lds_m;
+      return true;
     }
   }
   const size_t lds = (2 * N2 + (size_t)NTX_R * N2 + 64) * 4;
-  if (lds > 64 * 1024) return hipErrorInvalidValue;        // 2B <= 1600 rows
-  hipLaunchKernelGGL(ntx_grad_kernel, dim3((unsigned)((N2 + NTX_R - 1) / NTX_R), (unsigned)((D + 255) / 256)), dim3(256),
-                     lds, st, a, CT);
+  if (lds > 64 * 1024) return false;
+  p->route = NTX_VECTOR; p->ncw = 0; p->kc = 0; p->waves = 4;
+  p->grad_gx = (int)((N2 + NTX_R - 1) / NTX_R); p->grad_gy = (D + 255) / 256; p->lds = lds;
+  return true;
+}
+
+hipError_t launch_ntxent(const float* ei, const float* ej, int B, int D, float T, float* loss, float* gi, float* gj,
+                         float* ws, hipStream_t st) {
+  const bool aligned = D % 4 == 0 && (((uintptr_t)ei | (uintptr_t)ej) & 15) == 0;
+  NtxPlan p;
+  if (!plan_ntxent(B, D, aligned, &p)) return hipErrorInvalidValue;        // before anything is launched
+  const size_t N2 = 2 * (size_t)B;
+  const int CT = p.ct;
+  NtxArgs a;
+  a.ei = ei; a.ej = ej; a.B = B; a.D = D; a.T = T; a.loss = loss; a.gi = gi; a.gj = gj;
+  a.S = ws; ws += N2 * N2;
+  a.rs_part = ws; ws += (size_t)CT * N2;
+  a.nrm = ws;
+  hipLaunchKernelGGL(ntx_sim_kernel, dim3((unsigned)p.sim_gx, (unsigned)p.sim_gy), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)p.grad_gx, (unsigned)p.grad_gy);
+  if (p.route == NTX_MFMA) {
+    if (p.ncw == 4) {
+      static DevOnce once;
+      if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<4, 32, 8>)) != hipSuccess) return e;
+      hipLaunchKernelGGL((ntx_grad_mfma_kernel<4, 32, 8>), grid, dim3(512), p.lds, st, a, CT);
+    } else if (p.ncw == 2) {
+      static DevOnce once;
+      if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<2, 64>)) != hipSuccess) return e;
+      hipLaunchKernelGGL((ntx_grad_mfma_kernel<2, 64>), grid, dim3(256), p.lds, st, a, CT);
+    } else {
+      static DevOnce once;
+      if ((e = ensure_max_lds(once, ntx_grad_mfma_kernel<1, 64>)) != hipSuccess) return e;
+      hipLaunchKernelGGL((ntx_grad_mfma_kernel<1, 64>), grid, dim3(256), p.lds, st, a, CT);
+    }
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(ntx_grad_kernel, grid, dim3(256), p.lds, st, a, CT);
   return hipGetLastError();
 }
 

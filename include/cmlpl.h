@@ -721,7 +721,8 @@ int cmlpl_scene_project(const void* d_raw, int dtype, int64_t pixels, int bands,
 
 /* Caller-side row N4: tools.models.ContrastiveLoss (tools/models.py:14-39) -- NT-Xent over the
  * pairwise cosine similarity of the 2B normalised embeddings, forward + analytic backward.
- * d_emb_i, d_emb_j [B][D]; d_loss [1]; d_grad_i, d_grad_j [B][D] = dLoss/d emb. */
+ * d_emb_i, d_emb_j [B][D]; d_loss [1]; d_grad_i, d_grad_j [B][D] = dLoss/d emb.
+ * CMLPL_E_ARG for a batch no kernel holds (cmlpl_debug_ntxent_plan tells), before anything is launched. */
 size_t cmlpl_ntxent_workspace_bytes(int B, int D);
 int cmlpl_ntxent_fwd_bwd(const float* d_emb_i, const float* d_emb_j, int B, int D, float temperature,
                          float* d_loss, float* d_grad_i, float* d_grad_j,
@@ -919,6 +920,23 @@ int cmlpl_debug_loss_plan(const cmlpl_shape* shape, const cmlpl_shard* shard, in
 #define CMLPL_MEMOBANK_PLAN_INTS 3
 int cmlpl_debug_unsup_plan(int B, int K, int* out);
 int cmlpl_debug_memobank_plan(int D, int K, int queries, int negatives, int* out);
+
+/* Added after ABI 6, no bump (nothing existing moves).  Test aid: what the launcher of cmlpl_ntxent_fwd_bwd (plan_ntxent,
+ * the one function it obeys) decides under the current switches for B pairs of D floats.  `aligned`: what the call forms
+ * from its arguments -- D a multiple of 4 AND both embedding pointers on 16-byte boundaries (a D that is no multiple of 4
+ * is never aligned, whatever is passed).  out[CMLPL_NTXENT_PLAN_INTS]:
+ *   [0] the gradient kernel: 0 = ntx_grad_kernel (vector: rows that are not whole 16-byte pieces, CMLPL_NTX_MFMA=0, or a
+ *       column slice that does not fit LDS), 1 = ntx_grad_mfma_kernel
+ *   [1] NCW: 64 NCW embedding columns per workgroup (1 / 2 / 4: the widest that still gives 256 workgroups and fits LDS,
+ *       or what CMLPL_NTX_NCW names; 0 on the vector kernel)   [2] KC: embedding rows per staged chunk (64, 32 at NCW = 4;
+ *       0 on the vector kernel)   [3] waves per workgroup (4, 8 at NCW = 4)
+ *   [4], [5] grid x and y of ntx_sim_kernel (32-column tiles, 16-row tiles)   [6], [7] grid x and y of the gradient launch
+ *   [8] the dynamic LDS bytes of the gradient launch   [9] CT: the 32-column tiles whose partial denominators are folded
+ * Host arithmetic only, nothing is launched.  CMLPL_E_ARG where no route fits (the vector kernel holds 2B <= 1632 rows,
+ * the single-slice MFMA kernel 2B <= 1664): cmlpl_ntxent_fwd_bwd returns the same BEFORE anything is launched, every
+ * output keeps its bytes. */
+#define CMLPL_NTXENT_PLAN_INTS 10
+int cmlpl_debug_ntxent_plan(int B, int D, int aligned, int* out);
 
 /* Added after ABI 6, no bump (nothing existing moves) -- EDGE-PRESERVING SPATIAL SMOOTHING of class probability maps: the
  * probabilities of every class are averaged over a small neighbourhood in which a neighbour counts less the farther away

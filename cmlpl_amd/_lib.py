@@ -395,6 +395,17 @@ def check(fn: str, rc: int):
         raise CmlplError(fn, rc)
 
 
+def stream(device):
+    """the current stream of `device`, as the `void* stream` argument of a call"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    """a tensor's address as a pointer argument; None (a null pointer) for an optional tensor that is absent"""
+    return None if t is None else t.data_ptr()
+
+
 def layout(shape: Shape) -> Layout:
     out = Layout()
     check("cmlpl_layout", load().cmlpl_layout(C.byref(shape), C.byref(out)))

@@ -317,11 +317,6 @@ def _check_device_items(probs, truth, rows):
     return n, K
 
 
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def reliability_block(probs, truth, rows=None, bins: int = 15, counts=None):
     """one launch of cmlpl_reliability on the current stream, no synchronisation: the int64 cuda block it ADDED to
     (``counts``, or a fresh zeroed one)"""
@@ -335,8 +330,8 @@ def reliability_block(probs, truth, rows=None, bins: int = 15, counts=None):
     elif not (counts.is_cuda and counts.dtype == torch.int64 and counts.shape == (rel_size(bins),) and counts.is_contiguous()):
         raise ValueError("counts: a contiguous int64 cuda block of 16 + 3 bins words")
     _lib.check("cmlpl_reliability", _lib.load().cmlpl_reliability(
-        probs.data_ptr(), K, None if rows is None else rows.data_ptr(), truth.data_ptr(), n, int(bins), counts.data_ptr(),
-        _stream(probs.device)))
+        probs.data_ptr(), K, _lib.ptr(rows), truth.data_ptr(), n, int(bins), counts.data_ptr(),
+        _lib.stream(probs.device)))
     return counts
 
 
@@ -371,9 +366,9 @@ def temper_probs(probs, T: float, probs_out: bool = True, conf: bool = False, en
     res = EnsembleResult(torch.empty(n, dtype=torch.int64, device=dev), q if probs_out else None,
                          torch.empty(n, dtype=torch.float32, device=dev) if conf else None,
                          torch.empty(n, dtype=torch.float32, device=dev) if entropy else None)
-    ptr = lambda t: None if t is None else t.data_ptr()
     _lib.check("cmlpl_temper_probs", _lib.load().cmlpl_temper_probs(
-        probs.data_ptr(), n, K, beta, ptr(q), ptr(res.labels), ptr(res.conf), ptr(res.entropy), _stream(dev)))
+        probs.data_ptr(), n, K, beta, _lib.ptr(q), _lib.ptr(res.labels), _lib.ptr(res.conf), _lib.ptr(res.entropy),
+        _lib.stream(dev)))
     return res
 
 
@@ -386,8 +381,8 @@ def nll_temps(probs, truth, rows, betas, sums=None):
     if sums is None:
         sums = torch.zeros(2, b.size, dtype=torch.int64, device=probs.device)
     _lib.check("cmlpl_nll_temps", _lib.load().cmlpl_nll_temps(
-        probs.data_ptr(), K, None if rows is None else rows.data_ptr(), truth.data_ptr(), n, (C.c_float * b.size)(*b.tolist()),
-        int(b.size), sums.data_ptr(), _stream(probs.device)))
+        probs.data_ptr(), K, _lib.ptr(rows), truth.data_ptr(), n, (C.c_float * b.size)(*b.tolist()),
+        int(b.size), sums.data_ptr(), _lib.stream(probs.device)))
     return sums
 
 

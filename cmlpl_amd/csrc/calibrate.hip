@@ -1,8 +1,8 @@
 // Calibration of the prediction products (include/cmlpl.h, "THE DEFINITION OF THE RELIABILITY COUNTERS" and the two calls
 // behind it): does a written confidence mean what it says, and the smallest standard remedy, one scalar temperature.
-//   cmlpl_reliability   READS a probability map and ADDS to a block of int64 counters.  cmlpl_ensemble's lane scheme: a group
-//                       of G lanes per item, G the smallest power of two >= K, lane c of a group owns class c; the row maximum,
-//                       its first index and the Brier sum are __shfl_xor butterflies of width G.  The first lane of a group
+//   cmlpl_reliability   READS a probability map and ADDS to a block of int64 counters.  rowgroup.hpp's lane scheme, a group
+//                       of G lanes per item: the row maximum, its first index (the first-maximum rule) and the Brier sum
+//                       are its butterflies.  The first lane of a group
 //                       scores its item: one LDS atomic per scored row into the workgroup's tile of the bins (int32 count /
 //                       hits, int64 conf_sum: 16 KB at 1024 bins), the head counts by ballot and popcount per wave, the
 //                       fixed-point sums in its registers.  At the end one 64-bit global integer atomic per NON-ZERO word
@@ -21,6 +21,7 @@
 
 #include "../../include/cmlpl.h"
 #include "common.hpp"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -37,27 +38,11 @@ constexpr float FIX20 = 1048576.f;    // 2^20
 
 typedef unsigned long long u64;
 
-template <int G> __device__ __forceinline__ float gsum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <int G> __device__ __forceinline__ float gmax(float v) {          // (fmaxf: the maximum of what is not NaN)
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-template <int G> __device__ __forceinline__ u64 gmask() { return G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull); }
-// the first index of the maximum of the row a group holds one class per lane; a NaN counts as the maximum and the first NaN
-// wins (cmlpl_ensemble's rule).  mx = gmax(v); kv = this lane owns a class.  Lane 0 of a group always owns one: never -1
+// group_argmax with its -1 clamped to 0 (lane 0 of a group always owns a class, so the clamp never acts; the compiler
+// cannot see that, and the label indexes a shuffle)
 template <int G> __device__ __forceinline__ int gargmax(float v, float mx, bool kv, int shift) {
-  const u64 nanb = (__ballot(kv && v != v) >> shift) & gmask<G>();
-  const u64 eqb = (__ballot(kv && v == mx) >> shift) & gmask<G>();
-  const int l = __ffsll((long long)(nanb ? nanb : eqb)) - 1;
+  const int l = group_argmax<G>(v, mx, kv, shift);
   return l < 0 ? 0 : l;
-}
-template <int G> __device__ __forceinline__ bool gany(bool f, int shift) {
-  return ((__ballot(f) >> shift) & gmask<G>()) != 0ull;
 }
 
 // ------------------------------------------------------------------ the reliability counters
@@ -105,11 +90,11 @@ template <int G> __global__ __launch_bounds__(CAL_THREADS) void reliability_kern
     if (base + stride < n) fetch(base + stride, t_next, p_next);
     const bool known = in && t >= 0 && t < K;
     const int tt = known ? (int)t : 0;
-    const int label = gargmax<G>(p, gmax<G>(p), kv, shift);
+    const int label = gargmax<G>(p, group_max<G>(p), kv, shift);
     const float conf = __shfl(p, shift + label, 64);
     const float pt = __shfl(p, shift + tt, 64);
     const float d = c == tt ? p - 1.f : p;
-    const float brier = gsum<G>(kv ? __fmul_rn(d, d) : 0.f);
+    const float brier = group_sum<G>(kv ? __fmul_rn(d, d) : 0.f);
     const bool lead = in && c == 0;
     const bool isnan = known && conf != conf;
     const bool scored = known && !isnan;
@@ -159,24 +144,6 @@ template <int G> __global__ __launch_bounds__(CAL_THREADS) void reliability_kern
   }
 }
 
-template <int G> hipError_t launch_rel_g(const RelArgs& a, hipStream_t st) {
-  constexpr int PPW = CAL_THREADS / G;
-  long long wgs = ((long long)a.n + PPW - 1) / PPW;
-  if (wgs > REL_WG_MAX) wgs = REL_WG_MAX;
-  hipLaunchKernelGGL(reliability_kernel<G>, dim3((unsigned)wgs), dim3(CAL_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_rel(const RelArgs& a, hipStream_t st) {
-  if (a.K <= 1) return launch_rel_g<1>(a, st);
-  if (a.K <= 2) return launch_rel_g<2>(a, st);
-  if (a.K <= 4) return launch_rel_g<4>(a, st);
-  if (a.K <= 8) return launch_rel_g<8>(a, st);
-  if (a.K <= 16) return launch_rel_g<16>(a, st);
-  if (a.K <= 32) return launch_rel_g<32>(a, st);
-  return launch_rel_g<64>(a, st);
-}
-
 // ------------------------------------------------------------------ tempered probabilities
 struct TmpArgs {
   const float* probs; int n, K; float beta;
@@ -195,17 +162,17 @@ template <int G> __global__ __launch_bounds__(CAL_THREADS) void temper_kernel(Tm
     const long long i = base + tid / G;
     const bool live = kv && i < n;                      // (a group past the last row runs on padding and stores nothing)
     const float p = live ? a.probs[i * K + c] : -INFINITY;      // the whole row is read in front of every store of the group
-    const float pmx = gmax<G>(p);
+    const float pmx = group_max<G>(p);
     const int label = gargmax<G>(p, pmx, kv, shift);
-    const bool bad = gany<G>(live && (p != p || p < 0.f || p == INFINITY), shift) || !(pmx > 0.f);
+    const bool bad = group_any<G>(live && (p != p || p < 0.f || p == INFINITY), shift) || !(pmx > 0.f);
     const float l = live ? logf(p) : -INFINITY;         // (padding: -inf into the maximum, 0 into the sum)
-    const float m = gmax<G>(l);
+    const float m = group_max<G>(l);
     const float e = live ? expf(__fmul_rn(beta, __fsub_rn(l, m))) : 0.f;
-    const float s = gsum<G>(e);
+    const float s = group_sum<G>(e);
     const float q = bad ? NAN : e / s;
     const float qlab = __shfl(q, shift + label, 64);
     const float t = (q == 0.f) ? 0.f : __fmul_rn(q, logf(q));   // (a NaN q is not 0: it goes through)
-    const float ent = 0.f - gsum<G>(kv ? t : 0.f);
+    const float ent = 0.f - group_sum<G>(kv ? t : 0.f);
     if (live) {
       if (a.out != nullptr) a.out[i * K + c] = q;
       if (c == 0) {
@@ -217,22 +184,12 @@ template <int G> __global__ __launch_bounds__(CAL_THREADS) void temper_kernel(Tm
   }
 }
 
-template <int G> hipError_t launch_tmp_g(const TmpArgs& a, hipStream_t st) {
-  constexpr int PPW = CAL_THREADS / G;
-  long long wgs = ((long long)a.n + PPW - 1) / PPW;
-  if (wgs > TMP_WG_MAX) wgs = TMP_WG_MAX;
-  hipLaunchKernelGGL(temper_kernel<G>, dim3((unsigned)wgs), dim3(CAL_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_tmp(const TmpArgs& a, hipStream_t st) {
-  if (a.K <= 1) return launch_tmp_g<1>(a, st);
-  if (a.K <= 2) return launch_tmp_g<2>(a, st);
-  if (a.K <= 4) return launch_tmp_g<4>(a, st);
-  if (a.K <= 8) return launch_tmp_g<8>(a, st);
-  if (a.K <= 16) return launch_tmp_g<16>(a, st);
-  if (a.K <= 32) return launch_tmp_g<32>(a, st);
-  return launch_tmp_g<64>(a, st);
+// the launch of kernel_of(G), the kernel for the G of a.K (rowgroup.hpp), over a.n rows on at most wg_max workgroups
+template <class Args, class KernelOf> hipError_t launch_rows(const Args& a, int wg_max, hipStream_t st, KernelOf kernel_of) {
+  return with_group(a.K, [&](auto g) {
+    hipLaunchKernelGGL(kernel_of(g), dim3(group_grid(a.n, CAL_THREADS, g, wg_max)), dim3(CAL_THREADS), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------ the negative log-likelihood at S temperatures
@@ -298,14 +255,6 @@ __global__ __launch_bounds__(CAL_THREADS) void nll_temps_kernel(NllArgs a) {
   }
 }
 
-bool aligned4(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-            reinterpret_cast<uintptr_t>(d)) & 3);
-}
-bool aligned8(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 7);
-}
-
 }  // namespace
 }  // namespace cmlpl
 
@@ -313,11 +262,11 @@ extern "C" int cmlpl_reliability(const float* d_probs, int K, const int64_t* d_r
                                  int64_t* d_counts, void* stream) {
   using namespace cmlpl;
   if (!d_probs || !d_truth || !d_counts || n < 1 || K < 1 || K > CAL_KMAX || bins < 1 || bins > REL_BINS_MAX) return CMLPL_E_ARG;
-  if (!aligned4(d_probs) || !aligned8(d_row, d_truth, d_counts)) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_probs) || !aligned_to(7, d_row, d_truth, d_counts)) return CMLPL_E_ARG;
   RelArgs a = {};
   a.probs = d_probs; a.row = reinterpret_cast<const long long*>(d_row); a.truth = reinterpret_cast<const long long*>(d_truth);
   a.n = n; a.K = K; a.B = bins; a.counts = reinterpret_cast<u64*>(d_counts);
-  const hipError_t e = launch_rel(a, (hipStream_t)stream);
+  const hipError_t e = launch_rows(a, REL_WG_MAX, (hipStream_t)stream, [](auto g) { return reliability_kernel<g>; });
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -325,11 +274,11 @@ extern "C" int cmlpl_temper_probs(const float* d_probs, int n, int K, float beta
                                   float* d_conf, float* d_entropy, void* stream) {
   using namespace cmlpl;
   if (!d_probs || n < 1 || K < 1 || K > CAL_KMAX || !(beta > 0.f) || !std::isfinite(beta)) return CMLPL_E_ARG;
-  if (!aligned4(d_probs, d_out_probs, d_conf, d_entropy) || !aligned8(d_labels)) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_probs, d_out_probs, d_conf, d_entropy) || !aligned_to(7, d_labels)) return CMLPL_E_ARG;
   TmpArgs a = {};
   a.probs = d_probs; a.n = n; a.K = K; a.beta = beta;
   a.out = d_out_probs; a.labels = reinterpret_cast<long long*>(d_labels); a.conf = d_conf; a.entropy = d_entropy;
-  const hipError_t e = launch_tmp(a, (hipStream_t)stream);
+  const hipError_t e = launch_rows(a, TMP_WG_MAX, (hipStream_t)stream, [](auto g) { return temper_kernel<g>; });
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -337,7 +286,7 @@ extern "C" int cmlpl_nll_temps(const float* d_probs, int K, const int64_t* d_row
                                const float* betas, int S, int64_t* d_sums, void* stream) {
   using namespace cmlpl;
   if (!d_probs || !d_truth || !betas || !d_sums || n < 1 || K < 1 || K > CAL_KMAX || S < 1 || S > NLL_SMAX) return CMLPL_E_ARG;
-  if (!aligned4(d_probs) || !aligned8(d_row, d_truth, d_sums)) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_probs) || !aligned_to(7, d_row, d_truth, d_sums)) return CMLPL_E_ARG;
   NllArgs a = {};
   for (int s = 0; s < S; ++s) {
     if (!(betas[s] >= 0.0625f && betas[s] <= 16.f)) return CMLPL_E_ARG;     // (a NaN fails the comparison)

@@ -8,18 +8,16 @@
 //   entropy  = -sum_c p_c logf(p_c), 0 log 0 = 0; NaN when p is NaN
 //   disagree = the number of members whose own label (the same rule on p_m) is not `label`
 //
-// A group of G lanes per pixel, G the smallest power of two >= K (1 .. 64): a wave holds 64 / G pixels, lane c of a group
-// owns class c, padding lanes carry -inf into the maxima and 0 into the sums and never store.  Every reduction is a
-// __shfl_xor butterfly of width G: both partners of a stage add (or compare) the same two values, so every lane of a
-// group ends with the same bits, in an order that depends on G alone -- the results are the same bytes on every run,
-// whatever the grid.  No LDS, no atomics, no scratch; a grid-stride loop over blocks of 256 / G pixels, whose trip count
-// is the same for every lane of a workgroup (the shuffles are never divergent); plain loads and stores.
+// A group of G lanes per pixel in rowgroup.hpp's lane scheme: the results are the same bytes on every run, whatever the
+// grid.  No LDS, no atomics, no scratch; a grid-stride loop over blocks of 256 / G pixels, whose trip count is the same
+// for every lane of a workgroup (the shuffles are never divergent); plain loads and stores.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
 #include <stdint.h>
 
 #include "../../include/cmlpl.h"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -34,25 +32,6 @@ struct EnsArgs {
   int members, n, K;
   long long* labels; float* probs; float* conf; float* entropy; int* disagree;
 };
-
-template <int G> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <int G> __device__ __forceinline__ float group_max(float v) {     // (fmaxf: the maximum of what is not NaN)
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// torch.max(v, 1)[1] of the row a group holds one class per lane: the first index of the maximum; a NaN counts as the
-// maximum and the first NaN wins.  mx = group_max(v); kv = this lane owns a class
-template <int G> __device__ __forceinline__ int group_argmax(float v, float mx, bool kv, int shift) {
-  const unsigned long long mask = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
-  const unsigned long long nanb = (__ballot(kv && v != v) >> shift) & mask;
-  const unsigned long long eqb = (__ballot(kv && v == mx) >> shift) & mask;
-  return __ffsll((long long)(nanb ? nanb : eqb)) - 1;
-}
 
 template <int G> __global__ __launch_bounds__(ENS_THREADS) void ensemble_kernel(EnsArgs a) {
   constexpr int PPW = ENS_THREADS / G;                  // pixels per workgroup and trip
@@ -98,14 +77,6 @@ template <int G> __global__ __launch_bounds__(ENS_THREADS) void ensemble_kernel(
       }
     }
   }
-}
-
-template <int G> hipError_t launch_g(const EnsArgs& a, hipStream_t st) {
-  constexpr int PPW = ENS_THREADS / G;
-  long long wgs = ((long long)a.n + PPW - 1) / PPW;
-  if (wgs > ENS_WG_MAX) wgs = ENS_WG_MAX;
-  hipLaunchKernelGGL(ensemble_kernel<G>, dim3((unsigned)wgs), dim3(ENS_THREADS), 0, st, a);
-  return hipGetLastError();
 }
 
 // ---- members x views blocks (test-time augmentation: every member scores several noisy views of a pixel; include/cmlpl.h,
@@ -168,40 +139,12 @@ template <int G> __global__ __launch_bounds__(ENS_THREADS) void ensemble_views_k
   }
 }
 
-template <int G> hipError_t launch_views_g(const EnsViewsArgs& a, hipStream_t st) {
-  constexpr int PPW = ENS_THREADS / G;
-  long long wgs = ((long long)a.n + PPW - 1) / PPW;
-  if (wgs > ENS_WG_MAX) wgs = ENS_WG_MAX;
-  hipLaunchKernelGGL(ensemble_views_kernel<G>, dim3((unsigned)wgs), dim3(ENS_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_ensemble_views(const EnsViewsArgs& a, hipStream_t st) {
-  if (a.K <= 1) return launch_views_g<1>(a, st);
-  if (a.K <= 2) return launch_views_g<2>(a, st);
-  if (a.K <= 4) return launch_views_g<4>(a, st);
-  if (a.K <= 8) return launch_views_g<8>(a, st);
-  if (a.K <= 16) return launch_views_g<16>(a, st);
-  if (a.K <= 32) return launch_views_g<32>(a, st);
-  return launch_views_g<64>(a, st);
-}
-
-hipError_t launch_ensemble(const EnsArgs& a, hipStream_t st) {
-  if (a.K <= 1) return launch_g<1>(a, st);
-  if (a.K <= 2) return launch_g<2>(a, st);
-  if (a.K <= 4) return launch_g<4>(a, st);
-  if (a.K <= 8) return launch_g<8>(a, st);
-  if (a.K <= 16) return launch_g<16>(a, st);
-  if (a.K <= 32) return launch_g<32>(a, st);
-  return launch_g<64>(a, st);
-}
-
-// ---- what the two exported calls check alike
-bool ens_aligned(const float* logits, const int64_t* labels, const float* probs, const float* conf, const float* entropy,
-                 const int32_t* disagree) {
-  return !((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(conf) |
-            reinterpret_cast<uintptr_t>(entropy) | reinterpret_cast<uintptr_t>(disagree)) & 3) &&
-         !(reinterpret_cast<uintptr_t>(labels) & 7);
+// the launch of kernel_of(G), the kernel for the G of a.K (rowgroup.hpp), over a.n pixels
+template <class Args, class KernelOf> hipError_t launch_ens(const Args& a, hipStream_t st, KernelOf kernel_of) {
+  return with_group(a.K, [&](auto g) {
+    hipLaunchKernelGGL(kernel_of(g), dim3(group_grid(a.n, ENS_THREADS, g, ENS_WG_MAX)), dim3(ENS_THREADS), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 // w[m] = fl32(weights[m] / sum / views) in double (nullptr: equal weights); false: a weight that is negative or not
@@ -227,14 +170,15 @@ extern "C" int cmlpl_ensemble(const float* d_logits, int members, int64_t member
   if (members < 1 || members > cmlpl::ENS_MAX_MEMBERS || K < 1 || K > 64 || n < 1) return CMLPL_E_ARG;
   if (!d_logits || !d_labels) return CMLPL_E_ARG;
   if (members > 1 && member_stride < (int64_t)n * K) return CMLPL_E_ARG;          // the members' blocks must not overlap
-  if (!cmlpl::ens_aligned(d_logits, d_labels, d_probs, d_conf, d_entropy, d_disagree)) return CMLPL_E_ARG;
+  if (!cmlpl::aligned_to(3, d_logits, d_probs, d_conf, d_entropy, d_disagree) || !cmlpl::aligned_to(7, d_labels))
+    return CMLPL_E_ARG;
   cmlpl::EnsArgs a = {};
   if (!cmlpl::ens_weights(weights, members, 1, a.w)) return CMLPL_E_ARG;
   a.logits = d_logits; a.member_stride = members > 1 ? (long long)member_stride : 0;
   a.members = members; a.n = n; a.K = K;
   a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
   a.disagree = d_disagree;
-  const hipError_t e = cmlpl::launch_ensemble(a, (hipStream_t)stream);
+  const hipError_t e = cmlpl::launch_ens(a, (hipStream_t)stream, [](auto g) { return cmlpl::ensemble_kernel<g>; });
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -252,7 +196,8 @@ extern "C" int cmlpl_ensemble_views(const float* d_logits, int members, int view
     const bool m_in_v = (members == 1 || ms >= B) && (views == 1 || vs >= (members == 1 ? B : (int64_t)members * ms));
     if (!v_in_m && !m_in_v) return CMLPL_E_ARG;
   }
-  if (!cmlpl::ens_aligned(d_logits, d_labels, d_probs, d_conf, d_entropy, d_disagree)) return CMLPL_E_ARG;
+  if (!cmlpl::aligned_to(3, d_logits, d_probs, d_conf, d_entropy, d_disagree) || !cmlpl::aligned_to(7, d_labels))
+    return CMLPL_E_ARG;
   cmlpl::EnsViewsArgs a = {};
   if (!cmlpl::ens_weights(weights, members, views, a.w)) return CMLPL_E_ARG;
   a.logits = d_logits;
@@ -260,6 +205,6 @@ extern "C" int cmlpl_ensemble_views(const float* d_logits, int members, int view
   a.members = members; a.views = views; a.n = n; a.K = K;
   a.labels = reinterpret_cast<long long*>(d_labels); a.probs = d_probs; a.conf = d_conf; a.entropy = d_entropy;
   a.disagree = d_disagree;
-  const hipError_t e = cmlpl::launch_ensemble_views(a, (hipStream_t)stream);
+  const hipError_t e = cmlpl::launch_ens(a, (hipStream_t)stream, [](auto g) { return cmlpl::ensemble_views_kernel<g>; });
   return e == hipSuccess ? 0 : (int)e;
 }

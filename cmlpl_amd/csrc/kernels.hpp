@@ -425,9 +425,6 @@ void adam_fuse_scalars(AdamFuse& f, float lr, float b1, float b2, float eps, lon
 // ---- ema.hip  (the weight average of reference tools/models.py:155-164: ema = fl(fl(src * oma) + fl(ema * alpha)))
 hipError_t launch_ema(const float* src, float* ema, long long count, float alpha, float oma, hipStream_t st);
 
-// ---- labelprop.hip  (label propagation over the kNN graph: cmlpl_lp_graph / cmlpl_lp_propagate, include/cmlpl.h)
-int lp_group(int K);   // the lanes of a node's group: 2^ceil(log2 K)
-
 // ---- memobank.hip  (loss_helper.py)
 hipError_t launch_mb_select(const float* prob, const float* label, const float* low_mask, const float* high_mask, int N,
                             int Nl, int K, int* lists, int* counts, hipStream_t st);

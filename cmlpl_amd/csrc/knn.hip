@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -270,12 +271,8 @@ extern "C" int cmlpl_knn(const float* d_query, int n, const float* d_gallery, in
   if (!d_query || !d_gallery || !d_workspace || n < 1 || m < 1 || k < 1 || k > KNN_KMAX) return CMLPL_E_ARG;
   if (d_gallery_label ? (K < 1 || K > KNN_CMAX || !(inv_T > 0.f) || !std::isfinite(inv_T))
                       : (K != 0 || d_probs || d_labels)) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_query) | reinterpret_cast<uintptr_t>(d_gallery) |
-       reinterpret_cast<uintptr_t>(d_workspace)) & 15) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_gallery_label) | reinterpret_cast<uintptr_t>(d_skip) |
-       reinterpret_cast<uintptr_t>(d_labels)) & 7) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_nbr_idx) | reinterpret_cast<uintptr_t>(d_nbr_sim) |
-       reinterpret_cast<uintptr_t>(d_probs)) & 3) return CMLPL_E_ARG;
+  if (!aligned_to(15, d_query, d_gallery, d_workspace) || !aligned_to(7, d_gallery_label, d_skip, d_labels) ||
+      !aligned_to(3, d_nbr_idx, d_nbr_sim, d_probs)) return CMLPL_E_ARG;
   if (cmlpl_knn_workspace_bytes(n, m, k) > workspace_bytes) return CMLPL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int splits, per;

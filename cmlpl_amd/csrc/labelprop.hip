@@ -14,7 +14,7 @@
 //   lp_coef_kernel   : one thread per slot: the forward coefficient (c_i a) c_j; the reverse slot's owner by bisection of
 //                      rev_ptr, its coefficient (c_i a) c_src in place of the weight; slots past the last edge are cleared,
 //                      so every byte of the workspace is a function of the lists.
-//   lp_step_kernel<G>: an iteration.  A group of G = 2^ceil(log2 K) lanes per node, one class per lane; indices and
+//   lp_step_kernel<G>: an iteration.  A group of G lanes per node (rowgroup.hpp's G of K), one class per lane; indices and
 //                      coefficients are read G at a time, one per lane, and handed round by shuffles; a neighbour's F row is
 //                      one contiguous 4 K-byte segment.  One fmaf per edge and class, in list order.
 //   lp_finish_kernel : p = F / z, the first maximum, confidence, entropy.
@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -298,25 +299,7 @@ LpLayout lp_layout(int n, int k) {
 
 bool lp_shape_ok(int n, int k) { return n >= 1 && k >= 1 && k <= LP_KMAX && (long long)n * k < (1ll << 31); }
 
-template <int G>
-void lp_launch_step(const LpStep& s, hipStream_t st) {
-  const unsigned blocks = (unsigned)(((long long)s.n + 256 / G - 1) / (256 / G));
-  hipLaunchKernelGGL(lp_step_kernel<G>, dim3(blocks), dim3(256), 0, st, s);
-}
-template <int G>
-void lp_launch_finish(const LpFinish& f, hipStream_t st) {
-  const unsigned blocks = (unsigned)(((long long)f.n + 256 / G - 1) / (256 / G));
-  hipLaunchKernelGGL(lp_finish_kernel<G>, dim3(blocks), dim3(256), 0, st, f);
-}
-
 }  // namespace
-
-int lp_group(int K) {
-  int g = 1;
-  while (g < K) g <<= 1;
-  return g;
-}
-
 }  // namespace cmlpl
 
 extern "C" size_t cmlpl_lp_graph_bytes(int n, int k) {
@@ -328,8 +311,7 @@ extern "C" int cmlpl_lp_graph(const int32_t* d_nbr_idx, const float* d_nbr_sim, 
                               size_t bytes, void* stream) {
   using namespace cmlpl;
   if (!d_nbr_idx || !d_nbr_sim || !d_graph || !lp_shape_ok(n, k) || gamma < 1 || gamma > LP_GAMMA_MAX) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_nbr_idx) | reinterpret_cast<uintptr_t>(d_nbr_sim) |
-       reinterpret_cast<uintptr_t>(d_graph)) & 3) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_nbr_idx, d_nbr_sim, d_graph)) return CMLPL_E_ARG;
   if (cmlpl_lp_graph_bytes(n, k) > bytes) return CMLPL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const LpLayout l = lp_layout(n, k);
@@ -367,11 +349,8 @@ extern "C" int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float
   if ((long long)n * K >= (1ll << 31)) return CMLPL_E_ARG;
   const float* start = d_F0 ? d_F0 : d_Y;
   if (d_F == d_tmp || start == d_F || start == d_tmp || d_Y == d_F || d_Y == d_tmp) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_graph) | reinterpret_cast<uintptr_t>(d_Y) |
-       reinterpret_cast<uintptr_t>(d_F0) | reinterpret_cast<uintptr_t>(d_F) | reinterpret_cast<uintptr_t>(d_tmp) |
-       reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_conf) | reinterpret_cast<uintptr_t>(d_entropy) |
-       reinterpret_cast<uintptr_t>(d_residual)) & 3) return CMLPL_E_ARG;
-  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_graph, d_Y, d_F0, d_F, d_tmp, d_probs, d_conf, d_entropy, d_residual)) return CMLPL_E_ARG;
+  if (!aligned_to(7, d_labels)) return CMLPL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const LpLayout l = lp_layout(n, k);
   const float* wf = (const float*)d_graph;
@@ -381,20 +360,11 @@ extern "C" int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float
   LpStep s = {};
   s.idx = wi + l.dst; s.fwd = wf + l.fwd; s.ptr = wi + l.ptr; s.src = wi + l.src; s.rev = wf + l.rev;
   s.Y = d_Y; s.n = n; s.k = k; s.K = K; s.alpha = alpha; s.beta = (float)(1.0 - (double)alpha);
-  const int G = lp_group(K);
   const float* in = start;
   for (int t = 1; t <= iters; ++t) {
     float* out = (iters - t) % 2 == 0 ? d_F : d_tmp;             // the last one writes d_F
     s.in = in; s.out = out; s.residual = t == iters ? reinterpret_cast<unsigned*>(d_residual) : nullptr;
-    switch (G) {
-      case 1: lp_launch_step<1>(s, st); break;
-      case 2: lp_launch_step<2>(s, st); break;
-      case 4: lp_launch_step<4>(s, st); break;
-      case 8: lp_launch_step<8>(s, st); break;
-      case 16: lp_launch_step<16>(s, st); break;
-      case 32: lp_launch_step<32>(s, st); break;
-      default: lp_launch_step<64>(s, st); break;
-    }
+    with_group(K, [&](auto g) { hipLaunchKernelGGL(lp_step_kernel<g>, dim3(group_grid(n, 256, g)), dim3(256), 0, st, s); });
     in = out;
   }
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
@@ -402,15 +372,7 @@ extern "C" int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float
     LpFinish f = {};
     f.F = d_F; f.n = n; f.K = K; f.probs = d_probs; f.labels = reinterpret_cast<long long*>(d_labels); f.conf = d_conf;
     f.entropy = d_entropy;
-    switch (G) {
-      case 1: lp_launch_finish<1>(f, st); break;
-      case 2: lp_launch_finish<2>(f, st); break;
-      case 4: lp_launch_finish<4>(f, st); break;
-      case 8: lp_launch_finish<8>(f, st); break;
-      case 16: lp_launch_finish<16>(f, st); break;
-      case 32: lp_launch_finish<32>(f, st); break;
-      default: lp_launch_finish<64>(f, st); break;
-    }
+    with_group(K, [&](auto g) { hipLaunchKernelGGL(lp_finish_kernel<g>, dim3(group_grid(n, 256, g)), dim3(256), 0, st, f); });
     e = hipGetLastError();
   }
   return e == hipSuccess ? 0 : (int)e;

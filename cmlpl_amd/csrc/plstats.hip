@@ -15,6 +15,7 @@
 
 #include "../../include/cmlpl.h"
 #include "common.hpp"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -177,9 +178,7 @@ extern "C" int cmlpl_pl_stats(const float* d_probs, int btu, int K, const int64_
                               float adap_mask, float pos_thr, float neg_thr, int64_t* d_counts, void* stream) {
   using namespace cmlpl;
   if (!d_probs || !d_truth || !d_counts || btu < 1 || K < 1 || K > PL_KMAX) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_probs) & 3) || ((reinterpret_cast<uintptr_t>(d_truth) | reinterpret_cast<uintptr_t>(d_idx) |
-                                                      reinterpret_cast<uintptr_t>(d_counts)) & 7))
-    return CMLPL_E_ARG;
+  if (!aligned_to(3, d_probs) || !aligned_to(7, d_truth, d_idx, d_counts)) return CMLPL_E_ARG;
   long long wgs = ((long long)btu + PL_WAVES - 1) / PL_WAVES;
   if (wgs > PL_WG_MAX) wgs = PL_WG_MAX;
   hipLaunchKernelGGL(pl_stats_kernel, dim3((unsigned)wgs), dim3(64 * PL_WAVES), 0, (hipStream_t)stream, d_probs, btu, K,
@@ -191,9 +190,7 @@ extern "C" int cmlpl_pl_stats_hard(const int64_t* d_pseudo, int btu, int K, cons
                                    int64_t* d_counts, void* stream) {
   using namespace cmlpl;
   if (!d_pseudo || !d_truth || !d_counts || btu < 1 || K < 1 || K > PL_KMAX) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_pseudo) | reinterpret_cast<uintptr_t>(d_truth) | reinterpret_cast<uintptr_t>(d_idx) |
-       reinterpret_cast<uintptr_t>(d_counts)) & 7)
-    return CMLPL_E_ARG;
+  if (!aligned_to(7, d_pseudo, d_truth, d_idx, d_counts)) return CMLPL_E_ARG;
   long long wgs = (2LL * btu + 255) / 256;
   if (wgs > PL_WG_MAX) wgs = PL_WG_MAX;
   hipLaunchKernelGGL(pl_stats_hard_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream,

@@ -35,6 +35,7 @@
 
 #include "../../include/cmlpl.h"
 #include "kernels.hpp"
+#include "rowgroup.hpp"
 
 namespace cmlpl {
 namespace {
@@ -213,10 +214,7 @@ extern "C" int cmlpl_smooth_probs(const float* d_probs, const float* d_guide, in
   if (!std::isfinite(sigma_s) || !(sigma_s > 0.f)) return CMLPL_E_ARG;
   if (!(sigma_r > 0.f)) return CMLPL_E_ARG;                         // (a NaN fails the comparison; +inf is legal: b = 0)
   if (!d_probs || (!d_out_probs && !d_labels)) return CMLPL_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_probs) | reinterpret_cast<uintptr_t>(d_guide) | reinterpret_cast<uintptr_t>(d_out_probs) |
-       reinterpret_cast<uintptr_t>(d_conf) | reinterpret_cast<uintptr_t>(d_entropy)) & 3)
-    return CMLPL_E_ARG;
-  if (reinterpret_cast<uintptr_t>(d_labels) & 7) return CMLPL_E_ARG;
+  if (!aligned_to(3, d_probs, d_guide, d_out_probs, d_conf, d_entropy) || !aligned_to(7, d_labels)) return CMLPL_E_ARG;
   const int64_t count = (int64_t)rows * cols * K;
   if (d_out_probs && d_out_probs < d_probs + count && d_probs < d_out_probs + count) return CMLPL_E_ARG;   // not in place
   SmoothArgs s = {};

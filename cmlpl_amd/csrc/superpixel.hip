@@ -16,7 +16,7 @@
 // cmlpl_sp_vote_probs / cmlpl_sp_vote_labels: the map is arbitrary, so the sums are scattered with 64-bit INTEGER atomics
 //   into a zeroed [N][K] table; a run of neighbouring lanes with the same segment (a superpixel map has runs of S) is
 //   summed inside the wave first and its first lane issues the atomic.  One thread per segment finishes (q, the first
-//   maximum, the entropy c ascending), one group of 2^ceil(log2 K) lanes per pixel broadcasts.
+//   maximum, the entropy c ascending), one group of lanes per pixel (rowgroup.hpp) broadcasts.
 // Integer sums only: every output is the same bytes on every run.  Nothing is contracted into a fused multiply-add that
 // the definition does not name (the pragma below, and __fmul_rn / __fsub_rn where it matters).  No float atomics, no scratch.
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/cmlpl.h"
+#include "rowgroup.hpp"
 
 #pragma clang fp contract(off)
 
@@ -343,17 +344,7 @@ template <int G> __global__ __launch_bounds__(SP_THREADS) void sp_vote_broadcast
   }
 }
 
-template <int G> hipError_t launch_broadcast(const VoteArgs& a, hipStream_t st) {
-  constexpr int PPW = SP_THREADS / G;
-  i64 wgs = ((i64)a.n + PPW - 1) / PPW;
-  if (wgs > SP_WG_MAX) wgs = SP_WG_MAX;
-  hipLaunchKernelGGL(sp_vote_broadcast_kernel<G>, dim3((unsigned)wgs), dim3(SP_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
 size_t vote_ws_bytes(int N, int K) { return (size_t)12 * (size_t)N * (size_t)(K + 2); }
-
-bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 int vote(const int32_t* d_seg, const float* d_probs, const int64_t* d_src, int n, int K, int N, float* d_out_probs,
          int64_t* d_labels, float* d_conf, float* d_entropy, int64_t* d_sums, int64_t* d_cnt, float* d_seg_probs,
@@ -362,9 +353,8 @@ int vote(const int32_t* d_seg, const float* d_probs, const int64_t* d_src, int n
   if (!d_seg || (!d_probs && !d_src) || !d_ws) return CMLPL_E_ARG;
   if (!d_out_probs && !d_labels && !d_conf && !d_entropy && !d_sums && !d_cnt && !d_seg_probs && !d_seg_labels)
     return CMLPL_E_ARG;
-  if (misaligned(d_seg, 3) || misaligned(d_probs, 3) || misaligned(d_out_probs, 3) || misaligned(d_conf, 3) ||
-      misaligned(d_entropy, 3) || misaligned(d_seg_probs, 3) || misaligned(d_src, 7) || misaligned(d_labels, 7) ||
-      misaligned(d_sums, 7) || misaligned(d_cnt, 7) || misaligned(d_seg_labels, 7) || misaligned(d_ws, 7))
+  if (!aligned_to(3, d_seg, d_probs, d_out_probs, d_conf, d_entropy, d_seg_probs) ||
+      !aligned_to(7, d_src, d_labels, d_sums, d_cnt, d_seg_labels, d_ws))
     return CMLPL_E_ARG;
   if (ws_bytes < vote_ws_bytes(N, K)) return CMLPL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -386,13 +376,10 @@ int vote(const int32_t* d_seg, const float* d_probs, const int64_t* d_src, int n
   hipLaunchKernelGGL(sp_vote_finish_kernel, dim3((unsigned)((N + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   if (d_out_probs || d_labels || d_conf || d_entropy) {
-    if (K <= 1) e = launch_broadcast<1>(a, st);
-    else if (K <= 2) e = launch_broadcast<2>(a, st);
-    else if (K <= 4) e = launch_broadcast<4>(a, st);
-    else if (K <= 8) e = launch_broadcast<8>(a, st);
-    else if (K <= 16) e = launch_broadcast<16>(a, st);
-    else if (K <= 32) e = launch_broadcast<32>(a, st);
-    else e = launch_broadcast<64>(a, st);
+    e = with_group(K, [&](auto g) {
+      hipLaunchKernelGGL(sp_vote_broadcast_kernel<g>, dim3(group_grid(n, SP_THREADS, g, SP_WG_MAX)), dim3(SP_THREADS), 0, st, a);
+      return hipGetLastError();
+    });
   }
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -424,8 +411,7 @@ extern "C" int cmlpl_sp_segment(const float* d_guide, int64_t guide_stride, int 
   if (!std::isfinite(w) || !(w > 0.f)) return CMLPL_E_ARG;
   if (G > 0 && (!d_guide || guide_stride < G)) return CMLPL_E_ARG;
   if (!d_seg || !d_ws) return CMLPL_E_ARG;
-  if (misaligned(d_guide, 3) || misaligned(d_seg, 3) || misaligned(d_centres, 3) || misaligned(d_counts, 3) || misaligned(d_ws, 3))
-    return CMLPL_E_ARG;
+  if (!aligned_to(3, d_guide, d_seg, d_centres, d_counts, d_ws)) return CMLPL_E_ARG;
   if (ws_bytes < cmlpl_sp_workspace_bytes(rows, cols, G, S)) return CMLPL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   SpArgs a = {};

@@ -76,7 +76,7 @@ def ensemble_logits(logits: torch.Tensor, weights: Optional[Sequence[float]] = N
     if not 1 <= M <= MAX_MEMBERS:
         raise ValueError(f"logits: {M} members, the ensemble takes 1 .. {MAX_MEMBERS}")
     res = _alloc(n, K, logits.device, probs, conf, entropy, disagree)
-    st = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+    st = _lib.stream(logits.device)
     _reduce(_lib.load(), logits.data_ptr(), M, None, logits.stride(0) if M > 1 else n * K, 0, _weights(weights, M), n, K, res, 0, st)
     return res
 
@@ -122,7 +122,7 @@ def _ensemble(nets, cube, spectra, feed, keys, chunk, weights, asks) -> Ensemble
     fwd = _Forward(lib, cs, max(b[1] for b in bufs), cube, spectra, feed, n, chunk, views=keys is not None, labels=False)
     res = _alloc(n, K, dev, *asks)
     buf = torch.empty((V or 1) * M * fwd.chunk * K, dtype=torch.float32, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     _predict(fwd, bufs, keys or [None], n, buf=buf,
              reduce=lambda z, o, m: _reduce(lib, z.data_ptr(), M, V, m * K, M * m * K, cw, m, K, res, o, st))
     return res

@@ -9,7 +9,6 @@ matrix into OA / Kappa / per-class accuracy / AA with ``tools.hyper_tools.CalAcc
 host."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -74,7 +73,7 @@ class Evaluator:
         cm = self.cm_ens[:nn + 1] if ensemble else self.cm[:nn]
         cm.zero_()
         self.ignored.zero_()
-        st = C.c_void_p(torch.cuda.current_stream(self.cube.device).cuda_stream)
+        st = _lib.stream(self.cube.device)
         _lib.check("cmlpl_confusion", self.lib.cmlpl_confusion(
             labels.data_ptr(), nn, self.truth.data_ptr(), self.n, cs.K, cm.data_ptr(), self.ignored.data_ptr(), st))
         if ensemble:

@@ -24,7 +24,7 @@ def _net_buffers(net):
     (TrainEngine, net index) pair."""
     if isinstance(net, tuple):
         eng, i = net
-        eng._ensure_packed(C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
+        eng._ensure_packed(_lib.stream(eng.device))
         return eng.cshape, eng.params[i], eng.packed[i]
     flat, packed = net._flat_params(net._live_params())
     return net._cshape, flat, packed
@@ -61,7 +61,7 @@ def _nets_buffers(nets):
     BaseNet2 modules (their flat blocks are laid side by side once per call)."""
     if isinstance(nets, tuple) and len(nets) == 2 and nets[1] is None and hasattr(nets[0], "params"):
         eng = nets[0]
-        eng._ensure_packed(C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
+        eng._ensure_packed(_lib.stream(eng.device))
         return eng.cshape, 2, eng.params, int(eng.params.shape[1]), eng.packed, int(eng.packed.shape[1]), False
     if isinstance(nets, (tuple, list)) and len(nets) == 2 and not hasattr(nets[0], "params"):
         bufs = [_net_buffers(m) for m in nets]
@@ -199,7 +199,7 @@ class _Forward:
             return
         cs, cube, sr = self.cs, self.cube, self.spec_rows
         rows, cols, _ = cube.shape
-        st = C.c_void_p(torch.cuda.current_stream(cube.device).cuda_stream)
+        st = _lib.stream(cube.device)
         if key is None:
             _lib.check("cmlpl_extract_patches", self.lib.cmlpl_extract_patches(
                 cube.data_ptr(), rows, cols, cs.C, cs.H, self.pix.data_ptr() + 8 * o, m, self.xp.data_ptr(), st))
@@ -222,7 +222,7 @@ class _Forward:
         cs, nn, flat, pstride, packed, kstride, _ = group
         cube, K = self.cube, cs.K
         rows, cols, _ = cube.shape
-        st = C.c_void_p(torch.cuda.current_stream(cube.device).cuda_stream)
+        st = _lib.stream(cube.device)
         view = () if key is None else key
         if not self.fused:
             flat2, packed2 = flat.view(nn, -1), packed.view(nn, -1)
@@ -254,7 +254,7 @@ class _Forward:
             C.byref(cs), nn, flat.data_ptr(), pstride, packed.data_ptr(), kstride, cube.data_ptr(), rows, cols,
             self.spectra.data_ptr() + (0 if sr is not None else 4 * cs.bands * o),
             None if sr is None else sr.data_ptr() + 8 * o, self.pix.data_ptr() + 8 * o, m,
-            lab.data_ptr(), None if lg is None else lg.data_ptr(), self.ws.data_ptr(), self.ws.numel(), st, *view))
+            lab.data_ptr(), _lib.ptr(lg), self.ws.data_ptr(), self.ws.numel(), st, *view))
         if not whole:
             labels[:, at:at + m] = lab
             if logits is not None:

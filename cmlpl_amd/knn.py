@@ -132,11 +132,6 @@ def knn_host(query, gallery, gallery_labels, K: int, k: int, T: float = 1.0, ski
 
 
 # ------------------------------------------------------------------ the device side
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _rows_ok(t, name):
     import torch
     if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == D and t.is_contiguous() and t.shape[0] >= 1):
@@ -178,8 +173,8 @@ def embed(nets, spectra, spec_rows=None, out=None):
                 and norm.is_cuda and norm.dtype == torch.float32 and norm.is_contiguous() and norm.numel() == nn * n):
             raise ValueError("out: contiguous float32 cuda buffers [nets, n, 1024] and [nets, n]")
     _lib.check("cmlpl_embed", _lib.load().cmlpl_embed(
-        C.byref(cs), nn, flat.data_ptr(), pstride, spectra.data_ptr(), None if spec_rows is None else spec_rows.data_ptr(),
-        n, feat.data_ptr(), norm.data_ptr(), _stream(dev)))
+        C.byref(cs), nn, flat.data_ptr(), pstride, spectra.data_ptr(), _lib.ptr(spec_rows),
+        n, feat.data_ptr(), norm.data_ptr(), _lib.stream(dev)))
     if out is None and squeeze:
         return feat[0], norm[0]
     return feat, norm
@@ -228,11 +223,10 @@ def knn(query, gallery, gallery_labels, K: int, k: int, T: float = 1.0, skip=Non
                     torch.empty(n, K, dtype=torch.float32, device=dev) if vote and probs else None,
                     torch.empty(n, k, dtype=torch.int32, device=dev) if neighbours else None,
                     torch.empty(n, k, dtype=torch.float32, device=dev) if neighbours else None)
-    ptr = lambda t: None if t is None else t.data_ptr()
     _lib.check("cmlpl_knn", _lib.load().cmlpl_knn(
-        query.data_ptr(), n, gallery.data_ptr(), m, ptr(gallery_labels), K, ptr(skip), int(k),
-        inv_T_of(T) if vote else 1.0, ptr(res.nbr_idx), ptr(res.nbr_sim), ptr(res.probs), ptr(res.labels),
-        workspace.data_ptr(), workspace.numel(), _stream(dev)))
+        query.data_ptr(), n, gallery.data_ptr(), m, _lib.ptr(gallery_labels), K, _lib.ptr(skip), int(k),
+        inv_T_of(T) if vote else 1.0, _lib.ptr(res.nbr_idx), _lib.ptr(res.nbr_sim), _lib.ptr(res.probs), _lib.ptr(res.labels),
+        workspace.data_ptr(), workspace.numel(), _lib.stream(dev)))
     return res
 
 
@@ -305,15 +299,13 @@ class KnnEvaluator:
                                 None if self.nbr_sim is None else self.nbr_sim[j])
                 _lib.check("cmlpl_knn", self.lib.cmlpl_knn(
                     self.qfeat[j].data_ptr(), n, self.gfeat[j].data_ptr(), m, self.gallery_labels.data_ptr(), K,
-                    None if self.skip is None else self.skip.data_ptr(), k, inv,
-                    None if res.nbr_idx is None else res.nbr_idx.data_ptr(),
-                    None if res.nbr_sim is None else res.nbr_sim.data_ptr(), res.probs.data_ptr(), res.labels.data_ptr(),
-                    self.ws.data_ptr(), self.ws.numel(), _stream(dev)))
+                    _lib.ptr(self.skip), k, inv, _lib.ptr(res.nbr_idx), _lib.ptr(res.nbr_sim), res.probs.data_ptr(),
+                    res.labels.data_ptr(), self.ws.data_ptr(), self.ws.numel(), _lib.stream(dev)))
             self.last = KnnResult(self.labels[:nn], self.probs[:nn], None if self.nbr_idx is None else self.nbr_idx[:nn],
                                   None if self.nbr_sim is None else self.nbr_sim[:nn])
             cm = self.cm[:nn]
             cm.zero_()
             self.ignored.zero_()
             _lib.check("cmlpl_confusion", self.lib.cmlpl_confusion(
-                self.labels.data_ptr(), nn, self.truth.data_ptr(), n, K, cm.data_ptr(), self.ignored.data_ptr(), _stream(dev)))
+                self.labels.data_ptr(), nn, self.truth.data_ptr(), n, K, cm.data_ptr(), self.ignored.data_ptr(), _lib.stream(dev)))
             return cm

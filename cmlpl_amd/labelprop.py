@@ -10,7 +10,6 @@ the graph workspace (``cmlpl_lp_graph``, csrc/labelprop.hip), ``propagate`` iter
 it touches no GPU, and the tests hold the kernels to it."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -76,11 +75,6 @@ class LPGraph:
         return int(self.in_deg.max())
 
 
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def knn_graph(feat, k: int):
     """(nbr_idx int32 [n, k], nbr_sim float32 [n, k]) of the rows of ``feat`` [n, 1024] among themselves: the existing search
     alone (``cmlpl_amd.knn.knn`` without labels) with ``skip = arange(n)``"""
@@ -114,7 +108,7 @@ def build_graph(nbr_idx, nbr_sim, gamma: int = 3) -> LPGraph:
         raise ValueError("gamma: an integer 1 .. 8")
     buf = torch.empty(graph_bytes(n, k), dtype=torch.uint8, device=nbr_idx.device)
     _lib.check("cmlpl_lp_graph", _lib.load().cmlpl_lp_graph(nbr_idx.data_ptr(), nbr_sim.data_ptr(), n, k, int(gamma),
-                                                            buf.data_ptr(), buf.numel(), _stream(buf.device)))
+                                                            buf.data_ptr(), buf.numel(), _lib.stream(buf.device)))
     return LPGraph(buf, n, k)
 
 
@@ -154,10 +148,10 @@ def propagate(graph: LPGraph, Y, alpha: float, iters: int, F0=None, probs: bool 
     res = LPResult(new(n, dt=torch.int64), new(n, K) if probs else None, new(n) if conf else None, new(n) if entropy else None,
                    new(n, K), new(1) if residual else None)
     tmp = new(n, K)
-    ptr = lambda t: None if t is None else t.data_ptr()
     _lib.check("cmlpl_lp_propagate", _lib.load().cmlpl_lp_propagate(
-        graph.buf.data_ptr(), n, graph.k, Y.data_ptr(), K, alpha, int(iters), ptr(F0), res.F.data_ptr(), tmp.data_ptr(),
-        ptr(res.probs), res.labels.data_ptr(), ptr(res.conf), ptr(res.entropy), ptr(res.residual), _stream(dev)))
+        graph.buf.data_ptr(), n, graph.k, Y.data_ptr(), K, alpha, int(iters), _lib.ptr(F0), res.F.data_ptr(), tmp.data_ptr(),
+        _lib.ptr(res.probs), res.labels.data_ptr(), _lib.ptr(res.conf), _lib.ptr(res.entropy), _lib.ptr(res.residual),
+        _lib.stream(dev)))
     return res
 
 

@@ -29,10 +29,6 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
@@ -111,7 +107,7 @@ class MemoryBank:
         m = int(keys.shape[0])
         _lib.check("cmlpl_memobank_push", lib.cmlpl_memobank_push(
             _p(keys) if m else None, m, self.D, _p(self.data[c]), _p(self.state[c]), self.sizes[c],
-            _stream(self.device)))
+            _lib.stream(self.device)))
         rows, _ = self.host_state()
         self.note_enqueued(c, rows[c], m)
         return m
@@ -157,7 +153,7 @@ def unsupervised_loss(predict, target, percent, pred_teacher):
     need = lib.cmlpl_unsup_workspace_bytes(B)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     _lib.check("cmlpl_unsup_loss", lib.cmlpl_unsup_loss(_p(p), _p(target), _p(t), B, K, float(percent), _p(loss),
-                                                        _p(grad), _p(ws), need, _stream(dev)))
+                                                        _p(grad), _p(ws), need, _lib.stream(dev)))
     return _Scaled.apply(predict, loss[0], grad)
 
 
@@ -179,7 +175,7 @@ def contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask, high_m
         raise RuntimeError("cmlpl_amd.memobank needs CUDA (ROCm) tensors: there is no CPU fallback")
     if as_tensors is None:
         as_tensors = draws is None
-    st = _stream(dev)
+    st = _lib.stream(dev)
     N, D = rep.shape
     K = label_l.shape[1]
     Nl = label_l.shape[0]

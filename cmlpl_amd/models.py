@@ -38,12 +38,12 @@ class _BaseNet2Fn(torch.autograd.Function):
         K = mod.shape.K
         logits = torch.empty(1, n, K, device=x.device, dtype=torch.float32)
         feat = torch.empty(1, n, FEAT_DIM, device=x.device, dtype=torch.float32)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = _lib.stream(x.device)
         train = 1 if mod.training else 0
         mod._calls += 1
         _lib.check("cmlpl_basenet2_fwd", lib.cmlpl_basenet2_fwd(
             C.byref(mod._cshape), 1, n, flat.data_ptr(), mod._P, packed.data_ptr(), x.data_ptr(), y.data_ptr(), None,
-            None if dropmask is None else dropmask.data_ptr(), float(mod.dropout), train,
+            _lib.ptr(dropmask), float(mod.dropout), train,
             int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, mod._calls, None,
             logits.data_ptr(), feat.data_ptr(), ws.data_ptr(), ws.numel(), stream))
         ctx.mod, ctx.n, ctx.train = mod, n, train
@@ -61,7 +61,7 @@ class _BaseNet2Fn(torch.autograd.Function):
             dfeat = dfeat.contiguous()
             dfeat_ptr = dfeat.data_ptr()
         grads = torch.zeros(mod._P, device=x.device, dtype=torch.float32)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = _lib.stream(x.device)
         _lib.check("cmlpl_basenet2_bwd", lib.cmlpl_basenet2_bwd(
             C.byref(mod._cshape), 1, n, flat.data_ptr(), mod._P, packed.data_ptr(), x.data_ptr(), y.data_ptr(),
             dropmask.data_ptr() if dropmask.numel() else None, float(mod.dropout), ctx.train,
@@ -124,7 +124,7 @@ class BaseNet2(nn.Module):
                 off, numel = int(self._layout.param_off[i]), int(self._layout.param_numel[i])
                 flat[off:off + numel].copy_(p.detach().reshape(-1))
             packed = torch.empty(int(self._layout.packed_total), device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.stream(dev)
             _lib.check("cmlpl_pack_weights", lib.cmlpl_pack_weights(C.byref(self._cshape), 1, flat.data_ptr(),
                                                                      self._P, packed.data_ptr(), stream))
             self._cache = (key, flat, packed)
@@ -172,7 +172,7 @@ class _NTXentFn(torch.autograd.Function):
             ws = _NTXentFn._ws[key] = torch.empty(lib.cmlpl_ntxent_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
         out = torch.empty(2 * B * D + 1, device=dev, dtype=torch.float32)        # [gi | gj | loss]
         g2 = out[:2 * B * D].view(2, B, D)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         p = out.data_ptr()
         _lib.check("cmlpl_ntxent_fwd_bwd", lib.cmlpl_ntxent_fwd_bwd(
             emb_i.data_ptr(), emb_j.data_ptr(), B, D, temperature, p + 8 * B * D, p, p + 4 * B * D,
@@ -237,7 +237,7 @@ def WeightEMA_BN(Base, Ensemble, alpha):
             if e.dtype != torch.float32 or not (b.is_contiguous() and e.is_contiguous()):
                 raise ValueError(f"WeightEMA_BN: {k!r} must be contiguous float32, got {e.dtype}")
             with torch.cuda.device(e.device):
-                stream = C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
+                stream = _lib.stream(e.device)
                 _lib.check("cmlpl_ema_update", lib.cmlpl_ema_update(b.data_ptr(), e.data_ptr(), e.numel(), alpha, stream))
             torch.autograd.graph.increment_version(e)       # written behind torch's back: BaseNet2's flat copy follows
     return Ensemble

@@ -1,7 +1,6 @@
 """On-device patch extraction (reference tools/hyper_tools.py:226-243 ``ExtractPatches``): gathers the
 w x w windows of the requested pixels from the scene cube that stays resident in HBM, instead of
 materialising and re-reading the [K, C, w, w] patch tensor."""
-import ctypes as C
 
 import torch
 
@@ -19,7 +18,7 @@ def extract_patches(cube: torch.Tensor, pixel_idx: torch.Tensor, w: int, out: to
     if out is None:
         out = torch.empty(n, Cc, w, w, device=cube.device, dtype=torch.float32)
     lib = _lib.load()
-    st = C.c_void_p(torch.cuda.current_stream(cube.device).cuda_stream)
+    st = _lib.stream(cube.device)
     _lib.check("cmlpl_extract_patches", lib.cmlpl_extract_patches(
         cube.data_ptr(), rows, cols, Cc, int(w), pixel_idx.data_ptr(), n, out.data_ptr(), st))
     return out

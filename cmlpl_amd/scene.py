@@ -5,8 +5,6 @@ needed (``cmlpl_extract_patches``).  Only the bands x bands SVD runs on the host
 reference makes, so that the components keep the reference's signs.  ``make_splits`` is the reference's split logic."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -42,10 +40,6 @@ def _upload(raw: np.ndarray, device):
     return torch.from_numpy(host).to(device), code
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _workspace(pixels, bands, n_pc, device):
     nbytes = _lib.load().cmlpl_scene_workspace_bytes(int(pixels), int(bands), int(n_pc))
     if nbytes == 0:
@@ -61,7 +55,7 @@ def scene_gram(d_raw: torch.Tensor, code: int, ws: torch.Tensor):
     gram = torch.empty(bands, bands, dtype=torch.float64, device=d_raw.device)
     _lib.check("cmlpl_scene_gram", _lib.load().cmlpl_scene_gram(
         d_raw.data_ptr(), code, n, bands, mean.data_ptr(), gram.data_ptr(), ws.data_ptr(), ws.numel(),
-        _stream(d_raw.device)))
+        _lib.stream(d_raw.device)))
     return mean, gram
 
 
@@ -80,7 +74,7 @@ def scene_project(d_raw: torch.Tensor, code: int, mean: torch.Tensor, gram: torc
     spec = torch.empty(n, bands, dtype=torch.float64, device=d_raw.device) if spectra else None
     _lib.check("cmlpl_scene_project", _lib.load().cmlpl_scene_project(
         d_raw.data_ptr(), code, n, bands, mean.data_ptr(), gram.data_ptr(), basis.data_ptr(), n_pc, cube.data_ptr(),
-        spec.data_ptr() if spec is not None else None, ws.data_ptr(), ws.numel(), _stream(d_raw.device)))
+        _lib.ptr(spec), ws.data_ptr(), ws.numel(), _lib.stream(d_raw.device)))
     return cube, spec
 
 

@@ -11,7 +11,6 @@ The definition, down to the order of the fp32 operations, is in ``include/cmlpl.
 the whole scene followed by it.  Nothing here synchronises; everything runs on the current stream."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -72,18 +71,18 @@ def smooth_probs(probs: torch.Tensor, cube: torch.Tensor, smooth: Smooth, probs_
         raise ValueError(f"probs: {n} rows for a scene of {rows} x {cols} pixels (the filter needs the whole map)")
     R, ss, sr, G, iters = smooth.params(Cc)
     lib, dev = _lib.load(), cube.device
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     res = _alloc(n, K, dev, probs_out, conf, entropy, False)
     src, bufs = probs, []                # the input is never written: two buffers of our own from the third pass on
-    ptr = lambda t: None if t is None else t.data_ptr()
     for it in range(iters):
         last = it == iters - 1
         if not last and len(bufs) < 2:
             bufs.append(torch.empty(n, K, dtype=torch.float32, device=dev))
         dst = res.probs if last else bufs[it % 2]
         _lib.check("cmlpl_smooth_probs", lib.cmlpl_smooth_probs(
-            src.data_ptr(), cube.data_ptr() if G > 0 else None, cube.stride(1), G, rows, cols, K, R, ss, sr, ptr(dst),
-            res.labels.data_ptr() if last else None, ptr(res.conf) if last else None, ptr(res.entropy) if last else None, st))
+            src.data_ptr(), cube.data_ptr() if G > 0 else None, cube.stride(1), G, rows, cols, K, R, ss, sr, _lib.ptr(dst),
+            res.labels.data_ptr() if last else None, _lib.ptr(res.conf) if last else None,
+            _lib.ptr(res.entropy) if last else None, st))
         src = dst
     return res
 

@@ -12,7 +12,6 @@ Not built: moving the seeds to the lowest gradient, and SLIC's connectivity post
 they are confined to a 3 x 3 block of cells.  Nothing here synchronises; everything runs on the current stream."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -94,10 +93,6 @@ class RegionVote(NamedTuple):
     segments: Optional[Segments] = None         # superpixel_probs: the map that voted
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 @torch.no_grad()
 def segment(cube: torch.Tensor, sp: Superpixel) -> Segments:
     """the superpixel map of the scene ``cube`` [rows, cols, C] (float32 cuda, contiguous) under its first channels"""
@@ -116,7 +111,7 @@ def segment(cube: torch.Tensor, sp: Superpixel) -> Segments:
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
     _lib.check("cmlpl_sp_segment", lib.cmlpl_sp_segment(
         cube.data_ptr() if G > 0 else None, cube.stride(1), G, rows, cols, S, m, T, seg.data_ptr(), centres.data_ptr(),
-        counts.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)))
+        counts.data_ptr(), ws.data_ptr(), nbytes, _lib.stream(dev)))
     return Segments(seg, centres, counts, ny, nx)
 
 
@@ -158,12 +153,11 @@ def region_vote(segments, probs: Optional[torch.Tensor] = None, labels: Optional
                      f32(N, K), i64(N), i64(N), i64(N, K))
     nbytes = lib.cmlpl_sp_vote_workspace_bytes(N, K)
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
     fn, src = ("cmlpl_sp_vote_probs", probs) if probs is not None else ("cmlpl_sp_vote_labels", labels)
     _lib.check(fn, getattr(lib, fn)(
-        seg.data_ptr(), src.data_ptr(), n, K, N, ptr(res.probs), res.labels.data_ptr(), ptr(res.conf), ptr(res.entropy),
-        res.sums.data_ptr(), res.seg_counts.data_ptr(), res.seg_probs.data_ptr(), res.seg_labels.data_ptr(), ws.data_ptr(),
-        nbytes, _stream(dev)))
+        seg.data_ptr(), src.data_ptr(), n, K, N, _lib.ptr(res.probs), res.labels.data_ptr(), _lib.ptr(res.conf),
+        _lib.ptr(res.entropy), res.sums.data_ptr(), res.seg_counts.data_ptr(), res.seg_probs.data_ptr(),
+        res.seg_labels.data_ptr(), ws.data_ptr(), nbytes, _lib.stream(dev)))
     return res
 
 

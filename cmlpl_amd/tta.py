@@ -135,11 +135,11 @@ def views_of(cube: torch.Tensor, spectra: Optional[torch.Tensor], pix: torch.Ten
     xp = torch.empty(n, Cc, window, window, dtype=torch.float32, device=dev)
     sr = pix if spec_rows is None else spec_rows
     x = None if spectra is None else torch.empty(n, spectra.shape[1], dtype=torch.float32, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     _lib.check("cmlpl_tta_patches_sym", _lib.load().cmlpl_tta_patches_sym(
         cube.data_ptr(), rows, cols, Cc, int(window), pix.data_ptr(), n, xp.data_ptr(),
-        None if spectra is None else spectra.data_ptr(), None if spectra is None else sr.data_ptr(),
-        0 if spectra is None else spectra.shape[1], None if x is None else x.data_ptr(), sigma, seed, view, st, sym))
+        _lib.ptr(spectra), None if spectra is None else sr.data_ptr(),
+        0 if spectra is None else spectra.shape[1], _lib.ptr(x), sigma, seed, view, st, sym))
     return xp, x
 
 
@@ -156,7 +156,7 @@ def ensemble_views_logits(logits: torch.Tensor, weights: Optional[Sequence[float
     if not 1 <= M * V <= MAX_BLOCKS:
         raise ValueError(f"logits: {M} x {V} blocks, cmlpl_ensemble_views takes 1 .. {MAX_BLOCKS}")
     res = _alloc(n, K, logits.device, probs, conf, entropy, disagree)
-    st = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+    st = _lib.stream(logits.device)
     _reduce(_lib.load(), logits.data_ptr(), M, V, logits.stride(0), logits.stride(1), _weights(weights, M), n, K, res, 0, st)
     return res
 

@@ -239,7 +239,7 @@ def _temper(p, T, **kw):
     return res
 
 
-@pytest.mark.parametrize("K", [1, 2, 9, 16, 17, 64])
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 9, 16, 17, 64])            # every lane group: G = 1, 2, 4, 8, 16, 16, 32, 64
 def test_temper_probs_against_the_fp64_definition(K):
     n = 517                                               # more than one workgroup at every K, with a tail
     p, _ = make_probs(n, K, 40 + K)

@@ -64,7 +64,7 @@ def _check_against_fp64(z, weights=None, stride_pad=0, tag=""):
 
 
 @pytest.mark.parametrize("M", [1, 2, 4])
-@pytest.mark.parametrize("K", [1, 2, 9, 16, 17, 64])
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 9, 16, 17, 64])            # every lane group: G = 1, 2, 4, 8, 16, 16, 32, 64
 def test_kernel_against_fp64(K, M):
     got = _check_against_fp64(case_logits(K, M))
     if K == 1:

@@ -20,6 +20,9 @@ CASES = [(1500, 5, 1, 0.9, 3, 20, 0, False),          # G = 1; the hub's in-degr
          (1500, 5, 9, 0.9, 3, 20, 0, False),          # G = 16
          (1500, 5, 17, 0.9, 3, 20, 0, False),         # G = 32
          (1500, 5, 64, 0.9, 3, 20, 0, False),         # G = 64
+         (1500, 5, 2, 0.9, 3, 20, 0, False),          # G = 2
+         (1500, 5, 3, 0.9, 3, 20, 0, False),          # G = 4
+         (1500, 5, 5, 0.9, 3, 20, 0, False),          # G = 8
          (300, 32, 9, 0.5, 3, 10, 0, False),          # the longest lists
          (1500, 5, 9, 0.9, 1, 20, 0, False),
          (1500, 5, 17, 0.9, 8, 20, 0, False),         # (K = 17, 51 seeds: with K = 9 the smallest fp64 row sum is 9.7e-5, under

@@ -175,7 +175,7 @@ def _device_vote(seg, N, K, probs=None, labels=None):
 
 
 @pytest.mark.parametrize("source", ["soft", "hard"])
-@pytest.mark.parametrize("K", [1, 2, 9, 16, 17, 64])
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 9, 16, 17, 64])            # every lane group: G = 1, 2, 4, 8, 16, 16, 32, 64
 def test_the_vote_is_the_definitions(K, source):
     maps = _maps(K, K)
     p, lab = _sources(K, len(maps[0][1]), K)

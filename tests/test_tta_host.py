@@ -151,7 +151,8 @@ def ensemble_views_fp32_torch(z, weights=None):
     return p.numpy(), (-t.sum(-1)).numpy()
 
 
-VIEW_CASES = ((9, 2, 3), (9, 2, 6), (16, 4, 3), (20, 4, 16), (9, 1, 64))      # K, M, V: M V = 6, 12, 12, 64, 64
+# K, M, V: M V = 6, 12, 12, 64, 64, and K = 3 and 5 for the lane groups of 4 and 8 that the others leave out
+VIEW_CASES = ((9, 2, 3), (9, 2, 6), (16, 4, 3), (20, 4, 16), (9, 1, 64), (3, 2, 3), (5, 2, 3))
 
 
 def views_case(K, M, V, n=4099):

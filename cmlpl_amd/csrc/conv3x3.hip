@@ -2675,8 +2675,12 @@ __global__ __launch_bounds__(64 * NW, ((MODE >= 2 || KSG) && NW == 4 ? 2 : 1)) v
       if constexpr (BIG) conv3_fwd_tail_g<INFER>(a, c, smem);
       else conv3_fwd_tail<NW, INFER>(a, c, smem);
     }
+    // (only where this launch's pooled map IS p1 -- the fused forward, conv1's general launch.  conv2's general launch
+    //  left p1's maximum when it chose its loop; its own pooled map is p2, which is no weight gradient's operand: written
+    //  here it replaced p1's maximum as the scale of conv2's weight gradient -- tests/test_gpu_f16x2_range.py)
     if constexpr (H2X) {
-      if (a.hstat != nullptr && tid == 0) a.hstat[(1 * 2 + net) * a.n + s0] = ((const volatile uint32_t*)smem)[a.maxslot + 1];
+      if (a.hstat != nullptr && tid == 0 && (MODE == 2 || a.hkind == 0))
+        a.hstat[(1 * 2 + net) * a.n + s0] = ((const volatile uint32_t*)smem)[a.maxslot + 1];
     }
   } else if (MODE == 3) {
     // conv0 weight gradient fused in (S == 1, MTW == 1):  dW0[c][co] = sum_pix xn[c][pix] * da0[pix][co].

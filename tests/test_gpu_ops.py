@@ -124,7 +124,6 @@ def test_split_bf16_conv1_error_bound_per_element(mixed):
     the measured maxima are printed.  `mixed`: the 64 channels of a0 span 1e-6 .. 1e3 (conv0 scaled per channel, conv1's
     input channels scaled inversely): operands of very different magnitude meet in every sum, outputs of different
     channels differ by nine orders of magnitude, and every element still has to meet its own bound."""
-    import torch.nn.functional as F
     shape, n = SHAPES["B2"], 32
     params = O.closed_form_params(shape, 9)
     if mixed:
@@ -143,28 +142,18 @@ def test_split_bf16_conv1_error_bound_per_element(mixed):
     reg = ModuleRegions(net, lo, n)
     (lo * dlog.to(DEV)).sum().backward()
     torch.cuda.synchronize()
+    from tests import f16x2_bound as B             # the fp64 re-computation from the device's operands, shared
     H, W, H2, W2 = shape.H, shape.W, shape.H // 2, shape.W // 2
-    a0 = reg.debug_region("a0").view(1, n, H * W, 64)[0].cpu().double().permute(0, 2, 1).reshape(n, 64, H, W)
-    p1 = reg.debug_region("p1").view(1, n, H2 * W2, 64)[0].cpu().double().permute(0, 2, 1).reshape(n, 64, H2, W2)
-    dp1 = reg.debug_region("dp1").view(1, n, H2 * W2, 64)[0].cpu().double().permute(0, 2, 1).reshape(n, 64, H2, W2)
+    a0, p1, dp1 = B.nchw(reg.debug_region("a0"), n, H, W), B.nchw(reg.debug_region("p1"), n, H2, W2), B.nchw(reg.debug_region("dp1"), n, H2, W2)
     gate = hip_relu_gates(reg, shape, n)[0]["z1"]                                   # [n, 64, H, W] bool
-    w1, b1 = params["conv1.weight"].double(), params["conv1.bias"].double()
     # ---- forward: p1 = avgpool2(relu(conv1(a0) + b1 + a0)), the device's ReLU decisions
-    z1 = F.conv2d(a0, w1, b1, padding=1) + a0
-    s1 = F.conv2d(a0.abs(), w1.abs(), b1.abs(), padding=1) + a0.abs()
-    zero = torch.zeros((), dtype=torch.float64)
-    p1_ref = F.avg_pool2d(torch.where(gate, z1, zero), 2)
-    s_p1 = F.avg_pool2d(torch.where(gate, s1, zero), 2)
+    fs = B.forward_stage(a0, params["conv1.weight"], params["conv1.bias"], gate)
+    p1_ref, s_p1 = fs["p"], fs["S"]
     err = (p1 - p1_ref).abs()
     ratio_f = float((err / s_p1.clamp_min(1e-300)).max())
     # ---- weight gradient: dW1 = sum a0(shifted) * dz1, dz1 = mask * upsample(dp1) / 4 (avgpool + ReLU backward)
-    dz1 = torch.zeros(n, 64, H, W, dtype=torch.float64)
-    dz1[:, :, :2 * H2, :2 * W2] = dp1.repeat_interleave(2, 2).repeat_interleave(2, 3) / 4
-    dz1 = torch.where(gate, dz1, zero)
-    dz1[:, :, 2 * H2:, :] = 0
-    dz1[:, :, :, 2 * W2:] = 0
-    dw_ref = torch.nn.grad.conv2d_weight(a0, w1.shape, dz1, padding=1)
-    s_dw = torch.nn.grad.conv2d_weight(a0.abs(), w1.shape, dz1.abs(), padding=1)
+    ws = B.wgrad_stage(a0, B.grad_image(dp1, gate, H, W))
+    dw_ref, s_dw = ws["p"], ws["S"]
     dw = dict(net.named_parameters())["conv1.weight"].grad.cpu().double()
     errw = (dw - dw_ref).abs()
     ratio_w = float((errw / s_dw.clamp_min(1e-300)).max())

@@ -221,14 +221,20 @@ __global__ __launch_bounds__(512) void extract_patches_kernel(const float* __res
     r = (int)(k / cols); c = (int)(k - (long long)r * cols);
     interior = (c - hw >= 0) && (c - hw + w <= cols) && CMLPL_ABL != 50;      // workgroup-uniform
     if (!interior) return;
+    // a span shorter than 16 bytes (w*C < 4: NI == 0, workgroup-uniform) has no 16-byte item, and the placeholder item
+    // (tc = 0) of the threads beyond NI would read 16 bytes of it -- past the cube at the scene's last pixel: no loads
+    // at all then, the row tails below carry every float of such a span.  (cube_feed_kernel keeps the same placeholder
+    // unguarded: make_dims gives it w >= 4, so its NI is never 0.)
+    if (NI > 0) {
 #pragma unroll
-    for (int q = 0; q < GB; ++q) {
-      const int t = tid + 512 * q, tc = t < NI ? t : 0;
-      // row of the item: exact for t < 2^22 / n4 (the quotient is at least 0.5 / n4 away from an integer)
-      const int i = (int)(((float)tc + 0.5f) * inv4), e4 = tc - i * n4;
-      int rr = r + i - hw;
-      rr = rr < 0 ? -rr - 1 : (rr >= rows ? 2 * rows - 1 - rr : rr);
-      v[q] = *(const float4*)(cube + ((long long)rr * cols + (c - hw)) * C + 4 * e4);
+      for (int q = 0; q < GB; ++q) {
+        const int t = tid + 512 * q, tc = t < NI ? t : 0;
+        // row of the item: exact for t < 2^22 / n4 (the quotient is at least 0.5 / n4 away from an integer)
+        const int i = (int)(((float)tc + 0.5f) * inv4), e4 = tc - i * n4;
+        int rr = r + i - hw;
+        rr = rr < 0 ? -rr - 1 : (rr >= rows ? 2 * rows - 1 - rr : rr);
+        v[q] = *(const float4*)(cube + ((long long)rr * cols + (c - hw)) * C + 4 * e4);
+      }
     }
     if (tid < w * rem) {
       const int i = tid / rem, e = (NF & ~3) + (tid - i * rem);

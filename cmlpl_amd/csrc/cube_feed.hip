@@ -54,6 +54,8 @@ __global__ __launch_bounds__(512) void cube_feed_kernel(CubeFeedArgs a) {
     const int NF = w * C, n4 = NF >> 2, NI = w * n4, rem = NF & 3;
     const float inv4 = 1.0f / (float)(n4 > 0 ? n4 : 1), invC = 1.0f / (float)C;
     constexpr int GB = 8;
+    // (the placeholder item tc = 0 below is a real 16-byte item of the span: w >= 4 here (make_dims), so n4 >= 1 --
+    // extract_patches_kernel, which takes w * C < 4, skips its loads when NI == 0)
     for (int t0 = 0; t0 < NI; t0 += 512 * GB) {
       float4 v[GB];
 #pragma unroll

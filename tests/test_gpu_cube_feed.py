@@ -3,7 +3,8 @@ gathered from the resident scene cube inside the step -- no [rows][C][H][W] wind
 step computes must be BIT-equal to the split-fed step on `extract_patches(cube, pix)`: the gather is a pure copy and the
 noise counters do not depend on where a row came from.  The forward of the cube-fed step runs on the augmented rows as
 plain rows; its staging puts the same values into the same LDS places as the raw-row route, so no downstream quantity
-differs and the whole step is held to tolerance 0 directly (augmented rows included)."""
+differs and the whole step is held to tolerance 0 directly (augmented rows included).
+The rows themselves are held to the ORACLE's cut, over the gather's whole envelope, in tests/test_gpu_window_envelope.py."""
 import ctypes as C
 
 import pytest

@@ -1,5 +1,6 @@
 """Patch extraction.  CPU: the oracle restatement vs vectors produced by the reference's
-own ExtractPatches (tests/golden/make_golden_patches.py).  GPU: the HIP gather vs the oracle, bit-exact."""
+own ExtractPatches (tests/golden/make_golden_patches.py).  GPU: the HIP gather vs the oracle, bit-exact.
+The gather's whole envelope (every layout, tail, batch, margin and mirror regime) is held in tests/test_gpu_window_envelope.py."""
 import os
 
 import numpy as np

@@ -508,12 +508,14 @@ __global__ __launch_bounds__(256) void partial_reduce_kernel(ReduceTable t) {
 }
 
 // The weight-gradient reduce and the two small weight-gradient GEMMs (classifier, feat_spe) are independent and
-// both short: one launch, reduce blocks first, GEMM tiles after them.
+// both short: one launch.  The GEMM tiles come FIRST: alone they are the longest-running kind of block (11.0 us against
+// 8.9 for the 3x3 fold blocks and 6.7 for conv0's, profiles/gemm_tile_ab.txt), and the grid is a little larger than what
+// is resident at once, so the kind dispatched last starts late and ends the launch.
 __global__ __launch_bounds__(256) void reduce_gemm_kernel(ReduceTable t, int reduce_blocks, GemmTN2 g) {
   __shared__ GemmTNShared sh;
-  const int bid = (int)blockIdx.x;
-  if (bid < reduce_blocks) partial_reduce_block(t, bid % t.total_blocks, bid / t.total_blocks, (float (*)[64])&sh.red[0][0][0]);   // 4 KB of the 12 KB
-  else gemm_tn_block(g, bid - reduce_blocks, sh);
+  const int gemm_blocks = (int)gridDim.x - reduce_blocks, bid = (int)blockIdx.x - gemm_blocks;
+  if (bid >= 0) partial_reduce_block(t, bid % t.total_blocks, bid / t.total_blocks, (float (*)[64])&sh.red[0][0][0]);   // 4 KB of the 12 KB
+  else gemm_tn_block(g, (int)blockIdx.x, sh);
 }
 
 // ---- the fold with the Adam step behind it (the eager, unclipped training step: no optimizer launch follows)
@@ -701,9 +703,9 @@ __device__ __forceinline__ void reduce_adam_block(const ReduceTable& t, int bx, 
 __global__ __launch_bounds__(256) void reduce_gemm_adam_kernel(ReduceTable t, int reduce_blocks, GemmTN2 g, AdamFuse f) {
   __shared__ GemmTNShared sh;
   __shared__ float x0[16][64];                         // the GEMM tiles' fourth accumulator set (gemm_tn.hpp, UPD)
-  const int bid = (int)blockIdx.x;
-  if (bid < reduce_blocks) reduce_adam_block(t, bid % t.total_blocks, bid / t.total_blocks, &sh.red[0][0][0], f);   // 10.3 KB of the 12 KB
-  else gemm_tn_block<true>(g, bid - reduce_blocks, sh, &f, x0);
+  const int gemm_blocks = (int)gridDim.x - reduce_blocks, bid = (int)blockIdx.x - gemm_blocks;     // (tiles first, as above)
+  if (bid >= 0) reduce_adam_block(t, bid % t.total_blocks, bid / t.total_blocks, &sh.red[0][0][0], f);   // 10.3 KB of the 12 KB
+  else gemm_tn_block<true>(g, (int)blockIdx.x, sh, &f, x0);
 }
 
 hipError_t launch_reduce_gemm(int nets, const ReduceTable& t, const GemmTN& g0, const GemmTN& g1, hipStream_t st,

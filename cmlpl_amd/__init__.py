@@ -9,6 +9,8 @@ Public surface:
   Smooth, smooth_probs / smooth_cube ... edge-preserving spatial smoothing of the class probability maps of a scene
   Superpixel, segment, region_vote, superpixel_probs, asa, segment_host, region_vote_host ... superpixels: segment the scene,
                                  vote per region
+  components, Sieve, sieve, connect_segments, cc_label_host, sieve_host ... connected regions: label the components of a
+                                 map, sieve the small ones, make a segment map connected
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
   Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
   embed, KnnEvaluator, KnnResult, knn_host (cmlpl_amd.knn.knn: the vote itself) ... kNN evaluation of the spectral embedding
@@ -40,6 +42,10 @@ def __getattr__(name):
                 "region_vote_host"):
         from . import superpixel
         return getattr(superpixel, name)
+    if name in ("Components", "Sieve", "SieveResult", "components", "sieve", "connect_segments", "cc_label_host", "sieve_host",
+                "connect_segments_host"):
+        from . import regions
+        return getattr(regions, name)
     if name in ("PLCounts", "pl_stats_host", "pl_stats_hard_host"):
         from . import plstats
         return getattr(plstats, name)

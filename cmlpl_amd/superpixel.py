@@ -8,8 +8,10 @@ probabilities (or the labels) of its pixels, and the region is labelled as one. 
 fp32 operations, are in ``include/cmlpl.h`` ("THE DEFINITION OF A SUPERPIXEL MAP", "THE DEFINITION OF A REGION VOTE");
 ``segment_host`` and ``region_vote_host`` restate them in numpy, and the tests hold the kernels to those bit for bit.
 
-Not built: moving the seeds to the lowest gradient, and SLIC's connectivity post-pass -- small detached fragments can exist;
-they are confined to a 3 x 3 block of cells.  Nothing here synchronises; everything runs on the current stream."""
+Not built: moving the seeds to the lowest gradient.  A segment of the plain map need not be connected -- small detached
+fragments can exist, confined to a 3 x 3 block of cells; ``Superpixel(connect=True)`` runs SLIC's connectivity post-pass
+(cmlpl_amd.regions.connect_segments: the sieve on the segment ids, then the component ids) and votes on that map, every
+segment of which is one region.  Nothing else here synchronises; everything runs on the current stream."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -40,12 +42,16 @@ class Superpixel(NamedTuple):
     """A grid of ``step`` S pixels (2 .. 64), compactness ``compact`` m (the weight of the distance in the image against the
     distance in the guide), ``iters`` T rounds of assign and update, the first ``guide`` channels of the cube as the guide
     (0: none, a plain grid; clamped to the cube's channels), and the ``vote``: 'soft' sums the class probabilities of a
-    region's pixels, 'hard' counts their labels.  The defaults are a starting point, NOT tuned on any scene."""
+    region's pixels, 'hard' counts their labels.  ``connect``: the vote runs on the CONNECTED map -- fragments of fewer than
+    max(1, S S / 4) pixels join the largest region they touch and every remaining component is a segment of its own
+    (``params()`` does not return it: its five values are what the launches of the plain map take).  The defaults are a
+    starting point, NOT tuned on any scene."""
     step: int
     compact: float = 1.0
     iters: int = 10
     guide: int = 3
     vote: str = "soft"
+    connect: bool = False
 
     def params(self, channels: Optional[int] = None):
         """(step, compact, iters, guide channels, vote) as the launches take them, checked; ``channels``: the cube's"""
@@ -90,7 +96,9 @@ class RegionVote(NamedTuple):
     seg_labels: Optional[torch.Tensor] = None   # int64 [N] (-1: no valid row)
     seg_counts: Optional[torch.Tensor] = None   # int64 [N]: the valid rows of every segment
     sums: Optional[torch.Tensor] = None         # int64 [N, K]: P
-    segments: Optional[Segments] = None         # superpixel_probs: the map that voted
+    segments: Optional[Segments] = None         # superpixel_probs: the segmenter's map (connect=False: the map that voted)
+    connected: Optional[torch.Tensor] = None    # Superpixel(connect=True): int32 [n], the connected map that voted, ids 0 .. M - 1
+    M: Optional[int] = None                     # its number of segments
 
 
 @torch.no_grad()
@@ -167,17 +175,25 @@ def superpixel_probs(probs: torch.Tensor, cube: torch.Tensor, sp: Superpixel, la
                      segments: Optional[Segments] = None) -> RegionVote:
     """``segment(cube, sp)`` (or ``segments``, a map that exists) followed by the vote of ``probs`` [rows * cols, K] over it:
     ``sp.vote`` 'soft' sums the probabilities, 'hard' counts ``labels`` (None: the first maximum of every row of ``probs``).
-    The result carries the map as ``.segments``."""
+    The result carries the map as ``.segments``; with ``sp.connect`` the vote runs on ``connect_segments`` of that map (4
+    passes, 4-connected, min_size max(1, S S / 4); one word is read back for its M) and the result carries it as ``.connected``."""
     if cube.dim() != 3 or probs.dim() != 2 or probs.shape[0] != cube.shape[0] * cube.shape[1]:
         raise ValueError("probs: need [rows * cols, K] for the cube's scene (a region vote needs the whole map)")
     vote = sp.params(cube.shape[2])[4]
     segs = segment(cube, sp) if segments is None else segments
+    voters, extra = (segs,), {}
+    if sp.connect:
+        from .regions import connect_segments
+        S = sp.params()[0]
+        ids, M = connect_segments(segs.seg, cube.shape[0], cube.shape[1], max(1, S * S // 4))
+        voters, extra = (ids,), dict(N=M)
     if vote == "soft":
-        res = region_vote(segs, probs=probs, probs_out=probs_out, conf=conf, entropy=entropy)
+        res = region_vote(*voters, probs=probs, probs_out=probs_out, conf=conf, entropy=entropy, **extra)
     else:
         hard = torch.max(probs, 1)[1] if labels is None else labels
-        res = region_vote(segs, labels=hard.contiguous(), K=probs.shape[1], probs_out=probs_out, conf=conf, entropy=entropy)
-    return res._replace(segments=segs)
+        res = region_vote(*voters, labels=hard.contiguous(), K=probs.shape[1], probs_out=probs_out, conf=conf, entropy=entropy,
+                          **extra)
+    return res._replace(segments=segs, **(dict(connected=voters[0], M=extra["N"]) if sp.connect else {}))
 
 
 def asa_of_sums(sums) -> float:

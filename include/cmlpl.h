@@ -1343,8 +1343,10 @@ int cmlpl_lp_propagate(const void* d_graph, int n, int k, const float* d_Y /* [n
  *     float [N][2 + G] after the T-th update; counts int32 [N], the regular pixels per segment.
  *   Consequence.  A segment's pixels lie inside its 3 x 3 block of cells, so n <= 9 S^2: no int64 can overflow, and an
  *     implementation may gather per segment in place of scattering per pixel.
- *   Not built: moving the seeds to the lowest gradient, and SLIC's connectivity post-pass -- small detached fragments can
- *     exist; they are confined to a 3 x 3 cell block.
+ *   Not built: moving the seeds to the lowest gradient.  A segment of this map need not be connected -- small detached
+ *     fragments can exist, confined to a 3 x 3 cell block; SLIC's connectivity post-pass is the sieve of the segment ids
+ *     followed by the component ids of the result ("THE DEFINITION OF A COMPONENT MAP" and "THE DEFINITION OF A SIEVED
+ *     MAP" below).
  *
  * THE DEFINITION OF A REGION VOTE.
  *   Inputs.  Any int32 map seg[n], N, K <= 64, and one of two sources.
@@ -1400,6 +1402,58 @@ int cmlpl_sp_vote_labels(const int32_t* d_seg, const int64_t* d_src_labels, int 
  * does; 0 for C < 1 or w < 1.  Answered from the two launchers' own LDS sizes, which the entry points above compare as well.
  * Host arithmetic only. */
 int cmlpl_patches_fit(int C, int w);
+
+/* Added after ABI 6, no bump (nothing existing moves) -- CONNECTED REGIONS: which pixels of a map form one region.
+ *
+ * THE DEFINITION OF A COMPONENT MAP.
+ *   Inputs.  An int32 map v[n] of a rows x cols scene, i = y cols + x, n = rows cols <= 2^31 - 1; conn in {4, 8}.
+ *   Terms.  A pixel with v[i] < 0 is VOID.  Two pixels are adjacent when they differ by one step in y or in x (conn 4), or
+ *     by at most one step in each and not both zero (conn 8), inside the scene.  Adjacent non-void pixels with equal values
+ *     are joined; a component is a class of the transitive closure.
+ *   Outputs.  comp[i] = the smallest pixel index of i's component, -1 for a void pixel; a ROOT is a pixel with comp[i] == i.
+ *     size[i] (int32) = the number of pixels of i's component, 0 for a void pixel.  id[i] = the number of roots with a
+ *     smaller index than comp[i], so the components are numbered 0 .. M - 1 in the order of their first pixel; -1 for a void
+ *     pixel.  M, an int32 word on the device.
+ *   Every output is an integer that does not depend on any order.
+ *
+ * THE DEFINITION OF A SIEVED MAP (the operation GDAL calls sieve, with a parallel merge order).
+ *   Inputs.  v and conn as above; min_size in 1 .. 2^31 - 1; passes T in 1 .. 16.
+ *   u_0 = v.  Pass t works on the components of u_(t-1).  A component is SMALL when its size is less than min_size, else
+ *     LARGE.  The candidates of a small component a are the large components that hold a pixel adjacent (under the same
+ *     conn) to a pixel of a.  Its target is the candidate with the greatest size; ties go to the smaller root -- the maximum
+ *     of the 64-bit integer (size << 32) | (0xFFFFFFFF - root).  If a has a target, every pixel of a takes u_(t-1)[root of
+ *     the target]; otherwise a stays.  All components move at once, from u_(t-1).  Void pixels are never sources, never
+ *     targets, and never change.
+ *   Outputs.  u_T, and int32 stats[T][4] = {components, small components, small components with a target, pixels
+ *     relabelled} of pass t.
+ *   Consequences.  Large components only grow.  A relabelled pixel never changes again.  A pass with 0 relabelled pixels
+ *     makes every later pass the identity.  min_size = 1 returns v's bytes.  T passes in one call are the bytes of the same
+ *     passes in several calls.  A small component with only small neighbours waits for a later pass, possibly for ever:
+ *     that is the definition, not a defect.
+ *   Not built: GDAL's smallest-first sequential merge order, merging by class-weighted boundary length, 3-D connectivity.
+ *
+ * cmlpl_cc_workspace_bytes(rows, cols) = 8 + 16 n + 4 (ceil(n / 1024) + 2) + 272: a 64-bit target word, a parent word and a
+ *   size word per pixel, the root counts per block of 1024 pixels, the counters; 0 for rows or cols < 1 or n past 2^31 - 1.
+ * cmlpl_cc_label: union-find in a fixed number of launches whatever the map holds -- tile (a workgroup labels 32 x 32
+ *   pixels in LDS), border (unites across tile borders in global memory, the larger root always linked under the smaller
+ *   by a 32-bit atomic min), flatten (every pixel takes its root; sizes by 32-bit atomic adds, a run of lanes with one root
+ *   summed in the wave first); with d_id or d_M a one-workgroup scan of the per-block root counts and a rank launch; with
+ *   d_id or d_size a broadcast launch.  d_comp [n]; d_size [n], d_id [n], d_M [1], each or NULL.
+ * cmlpl_cc_sieve: per pass tile, border, flatten, candidates (64-bit integer atomic max per small root), apply; with
+ *   d_probs [n][K] AND d_conf [n] a finishing launch writes conf[i] = probs[i][out[i]] for 0 <= out[i] < K, else NaN.
+ *   d_out [n] may be d_map.  d_stats int32 [passes][4] or NULL.
+ * CMLPL_E_ARG before any launch: rows or cols < 1 (or rows cols past 2^31 - 1), conn not 4 or 8, min_size < 1, passes
+ *   outside 1 .. 16, a null d_map / d_comp / d_out / d_ws, one of d_probs and d_conf without the other, K < 1 with them, a
+ *   misaligned pointer (4 bytes), ws_bytes < cmlpl_cc_workspace_bytes.
+ * Nothing allocates, synchronises or reads back, so a call can be captured in a graph; no loop waits for another thread
+ * (csrc/regions.hip argues the termination).  Integer atomics only: every output is the same bytes on every run, and none
+ * depends on what the workspace held before. */
+size_t cmlpl_cc_workspace_bytes(int rows, int cols);
+int cmlpl_cc_label(const int32_t* d_map, int rows, int cols, int conn, int32_t* d_comp, int32_t* d_size /* or NULL */,
+                   int32_t* d_id /* or NULL */, int32_t* d_M /* or NULL */, void* d_ws, size_t ws_bytes, void* stream);
+int cmlpl_cc_sieve(const int32_t* d_map, int rows, int cols, int conn, int min_size, int passes, int32_t* d_out,
+                   int32_t* d_stats /* [passes][4] or NULL */, const float* d_probs /* [n][K] or NULL */, int K,
+                   float* d_conf /* [n] or NULL */, void* d_ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

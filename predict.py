@@ -50,7 +50,16 @@ channels and every region votes with the class probabilities of its pixels (cmlp
 given and in front of ``--temperature``: one line ``superpixel: segments=.. empty=.. mean_size=.. max_size=.. ASA=..`` (ASA: the
 accuracy on the labelled test pixels that no region-level labelling of this map can exceed), a further ``Result:`` block with
 ``_sp`` appended to the tag, and ``--out`` / ``--proba`` / ``--confidence`` / ``--entropy`` describe the last stage.  ``--save_segments
-FILE`` writes the int32 segment map."""
+FILE`` writes the int32 segment map.  ``--sp_connect`` makes the regions that vote CONNECTED (fragments of fewer than S S / 4 pixels
+join the largest region they touch, every remaining component is a segment of its own): the ``superpixel:`` line and
+``--save_segments`` then describe that map, and a line ``superpixel connectivity: components_before=.. fragments_merged=..
+segments=..`` follows.  ``--sieve N`` (``--sieve_conn 4 | 8``, ``--sieve_passes T``) sieves the label map, LAST in the chain -- behind
+``--smooth``, ``--superpixel`` and ``--temperature``, which never moves a label: a connected region of fewer than N pixels takes the
+label of the largest region of at least N pixels that it touches (cmlpl_amd.regions), with any single network or ensemble, with
+or without ``--tta``.  One line ``sieve: components=.. small=.. relabelled=.. passes_used=.. components_after=..``, a further
+``Result:`` block with ``_sv`` appended to the tag (no ``Reliability`` line: the sieve moves labels, not probabilities); ``--out`` is
+the sieved map, ``--confidence`` the pixel's own probability of the label it ends with, ``--proba`` the probabilities of the stage
+in front; ``--entropy`` is refused with ``--sieve``."""
 import argparse
 import os
 from collections import namedtuple
@@ -62,10 +71,11 @@ from cmlpl_amd import checkpoint
 from cmlpl_amd.tta import TTA
 from hsi_loader import HSIDataSet, SyntheticScene
 from scene_report import (NET_TAGS, PRINT, SCORE, SILENT, RelScore, SceneJob, build_nets, calibration_split, ensemble_first,
-                          evaluate_whole, print_block, print_result, run_scene, smooth_stage, superpixel_stage, temper_stage,
+                          evaluate_whole, print_block, print_result, run_scene, sieve_stage, smooth_stage, superpixel_stage,
+                          temper_stage,
                           tta_first, tta_tag)
-from train import (DATASETS, SPATIAL_MODES, SYNTH, add_propagate_flags, add_smooth_flags, add_superpixel_flags, on_device,
-                   propagate_nodes, propagate_of, smooth_of, superpixel_of)
+from train import (DATASETS, SPATIAL_MODES, SYNTH, add_propagate_flags, add_sieve_flags, add_smooth_flags, add_superpixel_flags,
+                   on_device, propagate_nodes, propagate_of, sieve_of, smooth_of, superpixel_of)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
@@ -126,6 +136,17 @@ def check_args(args):
         if args.knn is not None or args.embed or getattr(args, 'propagate', False):
             raise SystemExit("--superpixel votes over the scene's map: --knn / --embed / --propagate describe the labelled test "
                              "pixels, a list without a map")
+    if sieve_of(args) is not None:
+        if args.entropy:
+            raise SystemExit("--entropy together with --sieve: the sieve moves labels, not probabilities, so the sieved map has no "
+                             "entropy of its own (write --entropy without --sieve, or --confidence, the pixel's own probability of "
+                             "the label it ends with)")
+        if args.net in ('both', 'ema_both'):
+            raise SystemExit("--sieve gives ONE prediction: --net %s writes two label maps (name one network, or --net "
+                             "ensemble for the two together)" % args.net)
+        if args.knn is not None or args.embed or getattr(args, 'propagate', False):
+            raise SystemExit("--sieve works on the scene's map: --knn / --embed / --propagate describe the labelled test pixels, a "
+                             "list without a map")
 
 
 def check_knn_args(args):
@@ -242,7 +263,7 @@ def networks_of(args):
 
 # What a scene prediction does.  ``evaluate``: ``evaluate_whole`` first (networks one by one: their ``Result:`` blocks as ever).
 # ``first_block`` None: nothing more; else one ``run_scene`` -- ``tta`` (None: ``ensemble_first``; of one network: its own softmax)
-# under ``tag``, then ``stages`` = (('smooth' | 'superpixel' | 'temper', its configuration), ..).  ``labels``: the map is the LAST
+# under ``tag``, then ``stages`` = (('smooth' | 'superpixel' | 'temper' | 'sieve', its configuration), ..).  ``labels``: the map is the LAST
 # stage's, the argmax of one network's logits from EVALUATE, or two such maps STACKED.
 Plan = namedtuple('Plan', 'evaluate tta tag stages first_block labels')
 LAST, EVALUATE, STACKED = 'last', 'evaluate', 'stacked'
@@ -258,9 +279,9 @@ def plan(args, has_test, noise=0.0):
                                             clean=not args.tta_no_clean, spatial=args.tta_spatial)
     together = tta is not None or args.net in ENSEMBLES
     tag = (NET_TAGS['ens'] if tta is None else tta_tag(tta)) if together else NET_TAGS[networks_of(args)[0]]
-    # the regions vote behind --smooth and in front of --temperature, which tempers the FINAL probabilities
+    # the regions vote behind --smooth and in front of --temperature, which tempers the FINAL probabilities; the sieve is last
     stages = tuple((name, cfg) for name, cfg in (('smooth', smooth_of(args)), ('superpixel', superpixel_of(args)),
-                                                 ('temper', temperature)) if cfg is not None)
+                                                 ('temper', temperature), ('sieve', sieve_of(args))) if cfg is not None)
     if together:
         return Plan(False, tta, tag, stages, PRINT, LAST)
     # one network: its block comes from evaluate_whole; its own softmax is scored, handed to the stages or written, silently
@@ -272,7 +293,7 @@ def plan(args, has_test, noise=0.0):
 def build_stages(todo, job, args, fit=None):
     """the ``scene_report`` stages of ``Plan.stages``; ``fit``: the (rows, truth) on the device that --temperature fit fits on"""
     make = dict(smooth=smooth_stage, superpixel=lambda sp: superpixel_stage(sp, job, args.save_segments),
-                temper=lambda T: temper_stage(None if T == 'fit' else T, fit))
+                temper=lambda T: temper_stage(None if T == 'fit' else T, fit), sieve=sieve_stage)
     return [make[name](cfg) for name, cfg in todo]
 
 
@@ -390,6 +411,7 @@ def build_parser():
                              "geometry; the Result: tag becomes _tta_flips / _tta_d4")
     add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
     add_superpixel_flags(parser, 'the prediction of --net (with or without --tta, behind --smooth; not with both / ema_both)')
+    add_sieve_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both, not with --entropy)')
     parser.add_argument('--reliability', action='store_true',
                         help='behind every Result: block one line Reliability<tag>: ECE, MCE, NLL, Brier score, mean confidence '
                              'and accuracy of the block\'s class probabilities over the labelled test pixels (not with both / '

@@ -1,6 +1,6 @@
 """Whole-scene prediction and its report, under ``train.py`` (the end of a run) and ``predict.py``: one scene record
 (``SceneJob``), a first prediction (``ensemble_first`` / ``tta_first``), the stages behind it (``smooth_stage``,
-``superpixel_stage``, ``temper_stage``) and one runner (``run_scene``: the scene opened, then ``run_stages``), which owns the
+``superpixel_stage``, ``temper_stage``, ``sieve_stage``) and one runner (``run_scene``: the scene opened, then ``run_stages``), which owns the
 tags of the ``Result:`` blocks, what every step hands on and what becomes of the first block; ``evaluate_whole`` beside it."""
 import time
 from collections import namedtuple
@@ -19,6 +19,7 @@ NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whol
 SMOOTH_TAG = '_smooth'                                             # smooth_stage: appended to the tag of what it smooths
 SP_TAG = '_sp'                                                     # superpixel_stage: appended to the tag of what votes
 TEMPER_TAG = '_T'                                                  # temper_stage: appended to the tag of what it tempers
+SIEVE_TAG = '_sv'                                                  # sieve_stage: appended to the tag of the map it sieves
 PRINT, SCORE, SILENT = 'print', 'score', 'silent'                  # run_stages: what happens to the first prediction's block
 OUTPUTS = ("labels", "probs", "conf", "entropy")                   # the leading fields of every result tuple
 
@@ -40,9 +41,11 @@ class SceneJob(NamedTuple):
 # the first prediction: ``predict(models, cube, spectra, want)`` is the library call, ``timing`` its printed line (a format of the
 # seconds and the number of networks), ``tag`` that of its ``Result:`` lines, ``noun`` who asks for the scene cube.  A further stage:
 # ``call(result, cube, want)`` on the result in front of it, ``timing`` a format of the seconds, ``suffix`` what its lines append
-# to the running tag, ``noun`` as above (None: nobody new asks)
+# to the running tag, ``noun`` as above (None: nobody new asks), ``scored`` False: its probabilities are those of the stage in front
+# -- it moves labels only --, so ``score`` is not called behind its block
 First = namedtuple('First', 'predict timing tag noun', defaults=("the ensemble",))
-Stage = namedtuple('Stage', 'timing suffix call noun', defaults=(None,))
+Stage = namedtuple('Stage', 'timing suffix call noun scored', defaults=(None, True))
+SieveOut = namedtuple('SieveOut', 'labels probs conf entropy stats')
 
 
 def tta_tag(tta):
@@ -167,15 +170,22 @@ def superpixel_stage(sp, job, save_segments=None):
     def call(res, cube, want):
         out = superpixel_probs(res.probs, cube, sp, labels=res.labels, **stage_want(want))
         segs = out.segments
-        counts = segs.counts.cpu().numpy()
-        bound = 'n/a' if job.test_array is None else '%.4f' % asa(segs.seg, segs.N, job.test_array, job.Y_test, job.shape[4])
+        if out.connected is None:
+            seg, N, counts = segs.seg, segs.N, segs.counts.cpu().numpy()
+        else:           # --sp_connect: the line describes the connected map, the one that voted (the segmenter's counts are of regular pixels)
+            seg, N, counts = out.connected, out.M, torch.bincount(out.connected.long(), minlength=out.M).cpu().numpy()
+        bound = 'n/a' if job.test_array is None else '%.4f' % asa(seg, N, job.test_array, job.Y_test, job.shape[4])
         print('superpixel: segments=%d empty=%d mean_size=%.1f max_size=%d ASA=%s' %
-              (segs.N, int((counts == 0).sum()), counts.sum() / segs.N, counts.max(), bound))
+              (N, int((counts == 0).sum()), counts.sum() / N, counts.max(), bound))
+        if out.connected is not None:
+            from cmlpl_amd.regions import components
+            before = components(segs.seg, cube.shape[0], cube.shape[1]).count()
+            print('superpixel connectivity: components_before=%d fragments_merged=%d segments=%d' % (before, before - N, N))
         if save_segments:
-            np.save(save_segments, segs.seg.cpu().numpy())
+            np.save(save_segments, seg.cpu().numpy())
         return out
-    return Stage('superpixel time == %%.3f s (step %d, compactness %g, %d iterations, up to %d guide channels, %s vote)' %
-                 (S, m, T, G, vote), SP_TAG, call, "the superpixel vote")
+    return Stage('superpixel time == %%.3f s (step %d, compactness %g, %d iterations, up to %d guide channels, %s vote%s)' %
+                 (S, m, T, G, vote, ', connected' if sp.connect else ''), SP_TAG, call, "the superpixel vote")
 
 
 def temper_stage(T, fit=None):
@@ -192,10 +202,32 @@ def temper_stage(T, fit=None):
     return Stage('tempering time == %%.3f s (T %s)' % ('fitted' if T is None else '%g' % T), TEMPER_TAG, call)
 
 
+def sieve_stage(sv):
+    """the LAST stage: connected regions of fewer than ``min_size`` pixels of the label map in front take the label of the
+    largest large region they touch (``sv``: a cmlpl_amd.regions.Sieve; cmlpl_amd.regions.sieve).  One line ``sieve: components=
+    small= relabelled= passes_used= components_after=`` from the counters of its passes.  It moves labels, never probabilities:
+    ``probs`` are those of the stage in front, ``conf`` is every pixel's own probability of the label it ends with, there is no
+    entropy of its own, and no ``Reliability`` line behind its block."""
+    from cmlpl_amd.regions import components, sieve
+    min_size, conn, passes = sv.params()
+
+    def call(res, cube, want):
+        rows, cols = cube.shape[0], cube.shape[1]
+        out = sieve(res.labels.contiguous(), rows, cols, sv, probs=res.probs if want.get('conf') else None)
+        s = out.summary()
+        if s['components_after'] is None:       # (the last pass still moved pixels: its counters do not say what it left)
+            s['components_after'] = components(out.labels.to(torch.int32), rows, cols, conn).count()
+        print('sieve: components=%(components)d small=%(small)d relabelled=%(relabelled)d passes_used=%(passes_used)d '
+              'components_after=%(components_after)d' % s)
+        return SieveOut(out.labels, res.probs if want.get('probs') else None, out.conf, None, out.stats)
+    return Stage('sieve time == %%.3f s (min_size %d, %d-connected, up to %d pass%s)' %
+                 (min_size, conn, passes, '' if passes == 1 else 'es'), SIEVE_TAG, call, "the sieve", False)
+
+
 def run_stages(first, stages, cube, spectra, models, job, first_block=PRINT, want=None, score=None):
     """``first`` = (predict, timing, tag), then ``stages`` = [(timing, suffix, call), ..], each on the result in front of it.
     Per step: the library call, the copy to the host, the timing line, the ``Result:`` block (when ``job`` has the test pixels)
-    under the RUNNING tag -- ``first``'s, plus the suffix of every stage so far --, then ``score(tag, result)`` (a ``RelScore``).
+    under the RUNNING tag -- ``first``'s, plus the suffix of every stage so far --, then ``score(tag, result)`` (a ``RelScore``; not behind a stage that is not ``scored``).
     ``want`` (probs / conf / entropy: the caller's wishes) goes to the LAST step; every step in front of it is asked for its
     probabilities and nothing else, and with a ``score`` every step produces them.  ``first_block``: PRINT the first block and
     score it, SCORE it only (``evaluate_whole`` printed it), or SILENT.  Returns the last step's outputs as numpy arrays, by
@@ -205,7 +237,7 @@ def run_stages(first, stages, cube, spectra, models, job, first_block=PRINT, wan
     asked = [{k: bool(w.get(k)) for k in OUTPUTS[1:]} for w in [dict(probs=True)] * len(stages) + [want]]
     steps = [(timing, '', lambda res, cube, ask: predict(models, cube, spectra, ask)), *stages]
     res = None
-    for i, ((timing, suffix, call, *_), ask) in enumerate(zip(steps, asked)):
+    for i, ((timing, suffix, call, *more), ask) in enumerate(zip(steps, asked)):
         tag += suffix
         t1 = time.time()
         res = call(res, cube, ask)
@@ -213,7 +245,7 @@ def run_stages(first, stages, cube, spectra, models, job, first_block=PRINT, wan
         print(timing % ((time.time() - t1, len(models)) if i == 0 else time.time() - t1))
         if job.test_array is not None and (i > 0 or first_block == PRINT):
             print_result(tag, out["labels"], job.test_array, job.Y_test)
-        if score is not None and (i > 0 or first_block != SILENT):
+        if score is not None and (i > 0 or first_block != SILENT) and (len(more) < 2 or more[1]):
             score(tag, res)
     return out
 

@@ -40,7 +40,16 @@ Differences from the reference that are deliberate, MI355X-first choices:
     into superpixels on a grid of step S under the cube's leading principal components and every region votes as one
     (cmlpl_amd.superpixel; ``--sp_compact`` / ``--sp_iters`` / ``--sp_guide`` / ``--sp_vote`` / ``--save_segments``): a
     ``superpixel:`` line (segments, empty ones, sizes, ASA) and one more ``Result:`` block (``OA_ens_sp``; behind ``--smooth``:
-    ``OA_ens_smooth_sp``).  One GPU.  The run itself is untouched and no checkpoint records the flag.
+    ``OA_ens_smooth_sp``).  One GPU.  The run itself is untouched and no checkpoint records the flag.  ``--sp_connect``: the
+    regions that vote are CONNECTED -- detached fragments of fewer than S S / 4 pixels join the largest region they touch and
+    every remaining component is a segment of its own (cmlpl_amd.regions.connect_segments); the ``superpixel:`` line then
+    describes that map and a line ``superpixel connectivity: components_before= fragments_merged= segments=`` follows it.
+  * ``--sieve N`` (``--sieve_conn 4 | 8``, ``--sieve_passes T``): after the run the label map of Base and Base1 together --
+    behind ``--smooth`` and ``--superpixel`` when given -- is SIEVED: a connected region of fewer than N pixels takes the label
+    of the largest region of at least N pixels that it touches (cmlpl_amd.regions; the operation GDAL calls sieve).  One
+    ``sieve:`` line (components, small ones, pixels relabelled, passes used, components left) and one more ``Result:`` block
+    (``OA_ens_sv``, ``OA_ens_smooth_sv``, ..).  One GPU.  The run itself is untouched and no checkpoint records the flag.  An N
+    near the size of the true regions removes them; what the sieve buys on a real scene is not measured.
   * ``--aug_spatial flips | d4``: flip (and rotate) augmentation of the training windows, the reference's ``flip`` /
     ``Random_rot`` (hsi_loader.py:58-88): every batch row takes one element of the dihedral group per step, the same for
     both networks, applied inside the gather of ``--windows cube`` (which it needs; one GPU).  ``--tta --tta_spatial
@@ -87,7 +96,7 @@ import torch
 from cmlpl_amd import HyperParams, NetShape, checkpoint
 from hsi_loader import HSIDataSet, SyntheticHSIDataSet, SyntheticScene
 from scene_report import (NET_TAGS, PRINT, SILENT, SMOOTH_TAG, SP_TAG, RelScore, SceneJob, build_nets, calibration_split,  # noqa: F401
-                          ensemble_first, evaluate_whole, run_scene, smooth_stage, superpixel_stage, tta_first, tta_tag, tta_timing)
+                          ensemble_first, evaluate_whole, run_scene, sieve_stage, smooth_stage, superpixel_stage, tta_first, tta_tag, tta_timing)
 
 DATASETS = {1: (9, 103), 2: (16, 204), 3: (15, 144), 4: (16, 200)}     # num_classes, num_features (train.py:75-90)
 SYNTH = {"B2": (103, 11, 11, 103, 9), "P": (60, 20, 20, 103, 9), "B4": (200, 11, 11, 200, 16),
@@ -154,11 +163,12 @@ def run_record(args, hp, shape, from_scene):
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
     its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T, the optimiser flags) is left out at its default, so a file written without it is byte for byte what it
-    was before the flag existed; --propagate and its sub-flags only add lines behind the run and are never recorded"""
+    was before the flag existed; --propagate, --superpixel, --sieve and their sub-flags only add lines behind the run and are never recorded"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
             'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
             'knn': None, 'knn_T': None, **OPTIM_FLAGS}
-    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS and k not in SP_FLAGS}
+    return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS and k not in SP_FLAGS
+            and k not in SIEVE_FLAGS}
 
 
 LP_FLAGS = ('propagate', 'lp_k', 'lp_alpha', 'lp_gamma', 'lp_iters')     # --propagate: cmlpl_amd.labelprop.LabelProp's fields
@@ -317,7 +327,8 @@ def smooth_of(args):
     return smooth
 
 
-SP_FLAGS = ('superpixel', 'sp_compact', 'sp_iters', 'sp_guide', 'sp_vote', 'save_segments')
+SP_FLAGS = ('superpixel', 'sp_compact', 'sp_iters', 'sp_guide', 'sp_vote', 'save_segments', 'sp_connect')
+SIEVE_FLAGS = ('sieve', 'sieve_conn', 'sieve_passes')
 
 
 def add_superpixel_flags(parser, what):
@@ -338,6 +349,9 @@ def add_superpixel_flags(parser, what):
                              "labels (hard)")
     parser.add_argument('--save_segments', default=None, metavar='FILE',
                         help='--superpixel: write the int32 segment map [rows*cols] as .npy')
+    parser.add_argument('--sp_connect', action='store_const', const=True, default=None,
+                        help='--superpixel: the regions that vote are connected -- fragments of fewer than S S / 4 pixels join the '
+                             'largest region they touch, every remaining component is a segment of its own')
 
 
 def superpixel_of(args):
@@ -349,13 +363,42 @@ def superpixel_of(args):
             raise SystemExit("%s belong%s to --superpixel S" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
         return None
     from cmlpl_amd.superpixel import Superpixel
-    asked = {k: getattr(args, 'sp_' + k, None) for k in ('compact', 'iters', 'guide', 'vote')}
+    asked = {k: getattr(args, 'sp_' + k, None) for k in ('compact', 'iters', 'guide', 'vote', 'connect')}
     sp = Superpixel(args.superpixel, **{k: v for k, v in asked.items() if v is not None})
     try:
         sp.params()
     except ValueError as e:
         raise SystemExit("--superpixel: %s" % str(e).replace("Superpixel: ", ""))
     return sp
+
+
+def add_sieve_flags(parser, what):
+    """``--sieve N`` and its sub-flags (train.py and predict.py); every default is None: the flag was not given"""
+    parser.add_argument('--sieve', type=int, default=None, metavar='N',
+                        help='sieve the label map of %s, behind every other stage: a connected region of fewer than N pixels '
+                             'takes the label of the largest region of at least N pixels that it touches: one sieve: line and '
+                             'one more Result: block, tag ..._sv' % what)
+    parser.add_argument('--sieve_conn', type=int, choices=(4, 8), default=None, help='--sieve: 4- (the default) or 8-connected regions')
+    parser.add_argument('--sieve_passes', type=int, default=None, metavar='T',
+                        help='--sieve: passes (default 4, 1 .. 16); a pass that moves nothing ends the effect')
+
+
+def sieve_of(args):
+    """the ``cmlpl_amd.regions.Sieve`` of the command line, or None without ``--sieve``; what it cannot mean is a SystemExit
+    before anything is loaded"""
+    given = [k for k in SIEVE_FLAGS[1:] if getattr(args, k, None) is not None]
+    if getattr(args, 'sieve', None) is None:
+        if given:
+            raise SystemExit("%s belong%s to --sieve N" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
+        return None
+    from cmlpl_amd.regions import Sieve
+    asked = dict(conn=getattr(args, 'sieve_conn', None), passes=getattr(args, 'sieve_passes', None))
+    sv = Sieve(args.sieve, **{k: v for k, v in asked.items() if v is not None})
+    try:
+        sv.params()
+    except ValueError as e:
+        raise SystemExit("--sieve: %s" % str(e).replace("Sieve: ", ""))
+    return sv
 
 
 def load_data(run, args):
@@ -740,8 +783,10 @@ def report(run, args):
         from cmlpl_amd.tta import TTA
         run_scene(job, nets[:2], tta_first(TTA(args.m, args.noise, spatial=args.tta_spatial)), first_block=PRINT, score=score)
     # --smooth, then --superpixel behind the smoothed block (else behind the pair's, which is not printed again)
+    sv = sieve_of(args)                                              # --sieve: LAST, a temperature never moves a label
     stages = ([smooth_stage(run.smooth)] if run.smooth is not None else []) + \
-        ([superpixel_stage(run.sp, job, args.save_segments)] if run.sp is not None else [])
+        ([superpixel_stage(run.sp, job, args.save_segments)] if run.sp is not None else []) + \
+        ([sieve_stage(sv)] if sv is not None else [])
     if stages:
         run_scene(job, nets[:2], ensemble_first(), stages, first_block=SILENT, score=score)
 
@@ -778,6 +823,11 @@ def main(args, make_engine=None, device=None):
         raise SystemExit(f"--superpixel runs on one GPU (this job has {world} ranks)")
     if sp is not None and args.no_eval:
         raise SystemExit("--superpixel belongs to the end-of-run report: not with --no_eval")
+    sv = sieve_of(args)
+    if sv is not None and world > 1:
+        raise SystemExit(f"--sieve runs on one GPU (this job has {world} ranks)")
+    if sv is not None and args.no_eval:
+        raise SystemExit("--sieve belongs to the end-of-run report: not with --no_eval")
     if args.method != "cmlpl" and world > 1:      # before any device or communicator work
         raise SystemExit(f"--method {args.method} runs on one GPU: the sharded step exists for cmlpl only (this job has "
                          f"{world} ranks)")
@@ -920,6 +970,7 @@ def build_parser():
                         help='with an optimiser flag on: write [num_steps][5] = lr, norm, norm1, coef, coef1 of every step as .npy')
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     add_superpixel_flags(parser, 'Base and Base1 together after the run (behind --smooth when given; one GPU)')
+    add_sieve_flags(parser, 'Base and Base1 together after the run (one GPU)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
     parser.add_argument('--save_loss_hist', default=None, help='write loss_hist [num_steps,5] (train.py:136) as .npy')

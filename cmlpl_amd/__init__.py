@@ -11,6 +11,9 @@ Public surface:
                                  vote per region
   components, Sieve, sieve, connect_segments, cc_label_host, sieve_host ... connected regions: label the components of a
                                  map, sieve the small ones, make a segment map connected
+  RegionGraph, region_graph, region_propagate, merge_lists, pool_host, adjacency_host, merge_lists_host, region_graph_host
+                                 (cmlpl_amd.regiongraph.pool / .adjacency: the two steps themselves) ... the regions of a map
+                                 as the nodes of a label propagation: descriptors, adjacency, merged lists, a scene map
   PLCounts, pl_stats_host ...... the pseudo-label monitor's counters (TrainEngine(pl_monitor=True)) and their definition
   Reliability, reliability, temper_probs, fit_temperature ... calibration: reliability counters, ECE, a fitted temperature
   embed, KnnEvaluator, KnnResult, knn_host (cmlpl_amd.knn.knn: the vote itself) ... kNN evaluation of the spectral embedding
@@ -46,6 +49,10 @@ def __getattr__(name):
                 "connect_segments_host"):
         from . import regions
         return getattr(regions, name)
+    if name in ("RegionGraph", "region_graph", "region_propagate", "merge_lists", "pool_host", "adjacency_host",
+                "merge_lists_host", "region_graph_host"):
+        from . import regiongraph
+        return getattr(regiongraph, name)
     if name in ("PLCounts", "pl_stats_host", "pl_stats_hard_host"):
         from . import plstats
         return getattr(plstats, name)

@@ -58,6 +58,7 @@ EXPORTS = (
     "cmlpl_patches_fit",                                                         # added after ABI 6, no bump: which windows the cuts take
     "cmlpl_debug_ntxent_plan",                                                   # added after ABI 6, no bump: test aid (ntxent.hip)
     "cmlpl_cc_workspace_bytes", "cmlpl_cc_label", "cmlpl_cc_sieve",              # added after ABI 6, no bump: connected regions
+    "cmlpl_rg_workspace_bytes", "cmlpl_rg_pool", "cmlpl_rg_adjacency", "cmlpl_rg_lists",             # added after ABI 6, no bump: the region graph
 )
 METHODS = {"cmlpl": 0, "cps": 1}      # cmlpl_step_io.reserved, bits 0..7 (CMLPL_METHOD_*)
 PL_HEAD = 32                          # CMLPL_PL_HEAD: the head of the pseudo-label counter block, in front of cm[2][K][K]
@@ -360,6 +361,11 @@ def load(path: str = LIB_PATH):
     lib.cmlpl_cc_workspace_bytes.restype = sz
     lib.cmlpl_cc_label.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.cmlpl_cc_sieve.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, sz, vp]
+    lib.cmlpl_rg_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.cmlpl_rg_workspace_bytes.restype = sz
+    lib.cmlpl_rg_pool.argtypes = [vp, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp, sz, vp]
+    lib.cmlpl_rg_adjacency.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.cmlpl_rg_lists.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp]
     lib.cmlpl_step_graph_launch.argtypes = [vp, vp]
     lib.cmlpl_step_graph_destroy.argtypes = [vp]
     lib.cmlpl_debug_region.argtypes = [SP, i32, i32, C.c_char_p, C.POINTER(sz), C.POINTER(sz)]
@@ -371,7 +377,7 @@ def load(path: str = LIB_PATH):
                      "cmlpl_scene_workspace_bytes", "cmlpl_eval_workspace_bytes", "cmlpl_cps_loss_workspace_bytes",
                      "cmlpl_infer_tta_workspace_bytes", "cmlpl_eval_tta_workspace_bytes", "cmlpl_knn_workspace_bytes",
                      "cmlpl_grad_norm_partials_bytes", "cmlpl_lp_graph_bytes", "cmlpl_sp_workspace_bytes",
-                     "cmlpl_sp_vote_workspace_bytes", "cmlpl_cc_workspace_bytes"):
+                     "cmlpl_sp_vote_workspace_bytes", "cmlpl_cc_workspace_bytes", "cmlpl_rg_workspace_bytes"):
             getattr(lib, s).restype = i32
     if lib.cmlpl_abi_version() != ABI_VERSION:
         raise CmlplLibraryError(f"ABI version mismatch: library {lib.cmlpl_abi_version()}, binding {ABI_VERSION}")

@@ -8,8 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcmlpl_hip.so")
 # (api_aux.hip and api_infer.hip hold no kernel and come last: the kernel objects keep their places in the link, the
 #  order the step times of docs/EXPERIMENTS.md were measured with; regions.hip, which no step runs, goes behind them for
-#  the same reason)
-SOURCES = ["api.hip", "augment.hip", "calibrate.hip", "conv0.hip", "conv3x3.hip", "cps_loss.hip", "cube_feed.hip", "dense.hip", "dist.hip", "ema.hip", "ensemble.hip", "head.hip", "knn.hip", "labelprop.hip", "loss.hip", "memobank.hip", "metrics.hip", "ntxent.hip", "optim.hip", "plstats.hip", "scene.hip", "smooth.hip", "superpixel.hip", "tta.hip", "wgrad3x3.hip", "api_aux.hip", "api_infer.hip", "regions.hip"]
+#  the same reason, and regiongraph.hip behind that)
+SOURCES = ["api.hip", "augment.hip", "calibrate.hip", "conv0.hip", "conv3x3.hip", "cps_loss.hip", "cube_feed.hip", "dense.hip", "dist.hip", "ema.hip", "ensemble.hip", "head.hip", "knn.hip", "labelprop.hip", "loss.hip", "memobank.hip", "metrics.hip", "ntxent.hip", "optim.hip", "plstats.hip", "scene.hip", "smooth.hip", "superpixel.hip", "tta.hip", "wgrad3x3.hip", "api_aux.hip", "api_infer.hip", "regions.hip", "regiongraph.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

@@ -12,7 +12,7 @@ A ``min_size`` near the width of the true regions REMOVES them: on synthetic map
 lowers the accuracy where 4 raises it (tests/test_regions_host.py).  What the sieve buys on a real scene is not measured.
 
 Not built: a sieve inside ``--eval_every`` (a pixel list has no map), GDAL's smallest-first sequential merge order, merging
-by class-weighted boundary length, a sharded version, components as the nodes of ``--propagate``, 3-D connectivity.
+by class-weighted boundary length, a sharded version, 3-D connectivity.
 Nothing here synchronises (``Components.count()`` reads one word back); everything runs on the current stream."""
 from __future__ import annotations
 

@@ -1455,6 +1455,71 @@ int cmlpl_cc_sieve(const int32_t* d_map, int rows, int cols, int conn, int min_s
                    int32_t* d_stats /* [passes][4] or NULL */, const float* d_probs /* [n][K] or NULL */, int K,
                    float* d_conf /* [n] or NULL */, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Added after ABI 6, no bump (nothing existing moves) -- THE REGION GRAPH: from a region map to the neighbour lists that
+ * cmlpl_lp_graph takes, so that the regions of a scene become the nodes of a label propagation.
+ *
+ * The map.  int32 ids[n] of a rows x cols scene, i = y cols + x, n = rows cols <= 2^27; M in 1 .. 2^27.  Pixel p BELONGS to
+ *   region ids[p] when 0 <= ids[p] < M; anything else -- a negative value, a value >= M -- is VOID.  Any such map is taken:
+ *   a superpixel map, the ids of connected segments, the ids of a component map.  A region need not be connected and may be
+ *   empty.  (n <= 2^27: the adjacency's tables hold fewer than 16 n entries, which 31 bits index.)
+ *
+ * THE DEFINITION OF A REGION DESCRIPTOR.
+ *   Inputs.  The map; X float32 [n][B] under a row stride >= B (in floats), 1 <= B <= 1024.
+ *   Pixel p is POOLED iff it belongs to a region and every X[p][b], b < B, is finite with |x| <= 256 (z-scored spectra never
+ *     leave that range).  S[s][b] = sum over the pooled p of region s of llrintf(X[p][b] * 2^24), an int64: the product is
+ *     exact, a term is at most 2^32 in magnitude and a region has at most 2^31 - 1 pixels, and 2^32 x (2^31 - 1) < 2^63, so
+ *     no sum can overflow at any map size.  cnt[s] = the pooled pixels of s, an int64.
+ *     mean[s][b] = fl32(double(S[s][b]) / (double(cnt[s]) * 2^24)) -- the expression of the superpixel centres --, and a
+ *     row of zeros for cnt[s] == 0.
+ *   Every output is an integer sum, or one rounding of one: it does not depend on any order.
+ *
+ * THE DEFINITION OF A REGION ADJACENCY (4-connected only).
+ *   Inputs.  The map; A in 0 .. 16.
+ *   For every pixel p and its right and its lower neighbour q inside the scene: if both belong to regions and ids[p] !=
+ *     ids[q], 1 is added to b[ids p][ids q] and to b[ids q][ids p].  So b is symmetric, and b[s][t] is the length of the
+ *     boundary between s and t in pixel edges.
+ *   Outputs, all int32 and exact.  deg[s] = the number of t with b[s][t] > 0.  boundary[s] = sum_t b[s][t].  The LIST of s is
+ *     those t sorted by (b[s][t] descending, t ascending), cut to its first A entries: adj_idx[s][a] the region, -1 past
+ *     the end; adj_len[s][a] its b[s][t], 0 past the end.  A region with deg[s] > A is TRUNCATED.
+ *
+ * THE DEFINITION OF A REGION GRAPH.
+ *   Inputs.  feat float32 [M][1024], a row per region; the lists knn_idx int32 / knn_sim float32 [M][k] as cmlpl_knn writes
+ *     them (k >= 0); adj_idx [M][A]; 1 <= k + A <= 32 (the longest list cmlpl_lp_graph takes).
+ *   Outputs.  nbr_idx int32 / nbr_sim float32 [M][k + A].  Slots 0 .. k - 1 of row s are the kNN entries, copied.  Slot k + a
+ *     holds t = adj_idx[s][a]: -1 / -inf when t is outside 0 .. M - 1 or already stands in one of the k kNN slots of s;
+ *     otherwise t with sim = the fp32 dot product of feat[s] and feat[t] -- in any summation order, fused or not: within
+ *     1024 x 2^-24 x sum_i |a_i b_i| (first order) of the exact value.  A dot product that is not finite is stored as it is
+ *     (cmlpl_lp_graph gives such an entry the weight 0).
+ *   The graph is cmlpl_lp_graph of these lists and the labelling cmlpl_lp_propagate from Y[s] = the region vote's q[s] (a
+ *     NaN row becomes a zero row), both unchanged ("THE DEFINITION OF A PROPAGATED LABELLING"); every pixel of region s takes
+ *     the label, probabilities, confidence and entropy of s, a void pixel and a pixel of an unreached region -1 and NaN.
+ *   Not built: 8-connected adjacency, edge weights from the boundary length, a sharded version.
+ *
+ * cmlpl_rg_workspace_bytes(rows, cols, M, A) = 16 + 4 (3 M + 1 + ceil(M / 1024) + 2 + 33 n): what one call of
+ *   cmlpl_rg_pool or cmlpl_rg_adjacency needs; 0 for arguments outside the definitions.
+ * cmlpl_rg_pool: the pixel index by region (a histogram and a scatter with 32-bit integer atomics around an exclusive
+ *   scan), then a wavefront per region of up to 64 pixels and a workgroup per larger one, lanes along the bands, int64 sums
+ *   in registers.  d_mean [M][B], d_cnt int64 [M], d_S int64 [M][B] or NULL.  Eight launches.
+ * cmlpl_rg_adjacency: the directed contacts per region (= boundary), a scan that gives every region an open-addressing
+ *   table of the next power of two >= 2 boundary[s] entries, an init launch, an insert launch (32-bit atomicCAS on the key,
+ *   atomicAdd on the count: no thread waits for another), and a wavefront per region that picks the list in A rounds of a
+ *   wave-wide 64-bit integer maximum.  d_adj_idx / d_adj_len [M][A] (NULL allowed for A == 0), d_deg [M], d_boundary [M].
+ *   Eight launches.
+ * cmlpl_rg_lists: one launch, a wavefront per region.  d_knn_idx / d_knn_sim may be NULL for k == 0, d_adj_idx for A == 0.
+ * CMLPL_E_ARG before any launch: rows, cols or M < 1, n or M past 2^27, B outside 1 .. 1024, x_stride < B, A outside
+ *   0 .. 16, k < 0, k + A outside 1 .. 32, a null pointer that is not optional, a misaligned pointer (4 bytes; 8 for d_cnt
+ *   and d_S; 16 for d_feat); CMLPL_E_WORKSPACE: ws_bytes < cmlpl_rg_workspace_bytes.
+ * Nothing allocates, synchronises or reads back, and the number of launches does not depend on the map, so a call can be
+ * captured in a graph.  Integer atomics only: the integer outputs are the same bytes on every run, whatever the workspace
+ * and the output buffers held before; the sims of cmlpl_rg_lists are a fixed order of fp32 operations, so they are too. */
+size_t cmlpl_rg_workspace_bytes(int rows, int cols, int M, int A);
+int cmlpl_rg_pool(const int32_t* d_ids, int rows, int cols, int M, const float* d_X, int64_t x_stride, int B, float* d_mean,
+                  int64_t* d_cnt, int64_t* d_S /* or NULL */, void* d_ws, size_t ws_bytes, void* stream);
+int cmlpl_rg_adjacency(const int32_t* d_ids, int rows, int cols, int M, int A, int32_t* d_adj_idx, int32_t* d_adj_len,
+                       int32_t* d_deg, int32_t* d_boundary, void* d_ws, size_t ws_bytes, void* stream);
+int cmlpl_rg_lists(const float* d_feat, int M, const int32_t* d_knn_idx, const float* d_knn_sim, int k,
+                   const int32_t* d_adj_idx, int A, int32_t* d_nbr_idx, float* d_nbr_sim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

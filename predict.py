@@ -53,7 +53,11 @@ accuracy on the labelled test pixels that no region-level labelling of this map 
 FILE`` writes the int32 segment map.  ``--sp_connect`` makes the regions that vote CONNECTED (fragments of fewer than S S / 4 pixels
 join the largest region they touch, every remaining component is a segment of its own): the ``superpixel:`` line and
 ``--save_segments`` then describe that map, and a line ``superpixel connectivity: components_before=.. fragments_merged=..
-segments=..`` follows.  ``--sieve N`` (``--sieve_conn 4 | 8``, ``--sieve_passes T``) sieves the label map, LAST in the chain -- behind
+segments=..`` follows.  ``--region_graph`` (``--rg_k K``, ``--rg_adj A``, ``--rg_alpha a``, ``--rg_gamma g``, ``--rg_iters T``,
+``--rg_net i``; with ``--superpixel S``, directly behind it) makes the regions that voted the nodes of a label propagation: each is
+described by the embedding of its mean spectrum under member i of --net, linked to its K most similar and its A adjacent regions,
+and the vote is the prior that diffuses (cmlpl_amd.regiongraph): one line ``region graph: nodes=.. knn=.. adj=.. edges=..
+max_in_degree=.. truncated=.. unreached=.. residual=..`` and a further ``Result:`` block with ``_rg`` appended to the tag.  ``--sieve N`` (``--sieve_conn 4 | 8``, ``--sieve_passes T``) sieves the label map, LAST in the chain -- behind
 ``--smooth``, ``--superpixel`` and ``--temperature``, which never moves a label: a connected region of fewer than N pixels takes the
 label of the largest region of at least N pixels that it touches (cmlpl_amd.regions), with any single network or ensemble, with
 or without ``--tta``.  One line ``sieve: components=.. small=.. relabelled=.. passes_used=.. components_after=..``, a further
@@ -71,11 +75,11 @@ from cmlpl_amd import checkpoint
 from cmlpl_amd.tta import TTA
 from hsi_loader import HSIDataSet, SyntheticScene
 from scene_report import (NET_TAGS, PRINT, SCORE, SILENT, RelScore, SceneJob, build_nets, calibration_split, ensemble_first,
-                          evaluate_whole, print_block, print_result, run_scene, sieve_stage, smooth_stage, superpixel_stage,
+                          evaluate_whole, print_block, print_result, region_graph_stage, run_scene, sieve_stage, smooth_stage, superpixel_stage,
                           temper_stage,
                           tta_first, tta_tag)
-from train import (DATASETS, SPATIAL_MODES, SYNTH, add_propagate_flags, add_sieve_flags, add_smooth_flags, add_superpixel_flags,
-                   on_device, propagate_nodes, propagate_of, sieve_of, smooth_of, superpixel_of)
+from train import (DATASETS, SPATIAL_MODES, SYNTH, add_propagate_flags, add_region_graph_flags, add_sieve_flags, add_smooth_flags, add_superpixel_flags,
+                   on_device, propagate_nodes, propagate_of, region_graph_of, sieve_of, smooth_of, superpixel_of)
 
 ENSEMBLES = {'ensemble': [0, 1], 'ensemble_all': [0, 1, 'ema0', 'ema1']}
 CALIB_FRAC, CALIB_SEED, REL_BINS = 0.5, 1088, 15                 # the defaults of --calib_frac / --calib_seed / --rel_bins
@@ -129,6 +133,10 @@ def check_args(args):
     if smooth_of(args) is not None and args.net in ('both', 'ema_both'):
         raise SystemExit("--smooth gives ONE prediction: --net %s writes two label maps (name one network, or --net "
                          "ensemble for the two together)" % args.net)
+    if getattr(args, 'region_graph', None) is not None and args.net in ('both', 'ema_both'):
+        raise SystemExit("--region_graph gives ONE prediction: --net %s writes two label maps (name one network, or --net "
+                         "ensemble for the two together)" % args.net)
+    region_graph_of(args, len(networks_of(args)))
     if superpixel_of(args) is not None:
         if args.net in ('both', 'ema_both'):
             raise SystemExit("--superpixel gives ONE prediction: --net %s writes two label maps (name one network, or --net "
@@ -263,7 +271,7 @@ def networks_of(args):
 
 # What a scene prediction does.  ``evaluate``: ``evaluate_whole`` first (networks one by one: their ``Result:`` blocks as ever).
 # ``first_block`` None: nothing more; else one ``run_scene`` -- ``tta`` (None: ``ensemble_first``; of one network: its own softmax)
-# under ``tag``, then ``stages`` = (('smooth' | 'superpixel' | 'temper' | 'sieve', its configuration), ..).  ``labels``: the map is the LAST
+# under ``tag``, then ``stages`` = (('smooth' | 'superpixel' | 'region_graph' | 'temper' | 'sieve', its configuration), ..).  ``labels``: the map is the LAST
 # stage's, the argmax of one network's logits from EVALUATE, or two such maps STACKED.
 Plan = namedtuple('Plan', 'evaluate tta tag stages first_block labels')
 LAST, EVALUATE, STACKED = 'last', 'evaluate', 'stacked'
@@ -281,6 +289,7 @@ def plan(args, has_test, noise=0.0):
     tag = (NET_TAGS['ens'] if tta is None else tta_tag(tta)) if together else NET_TAGS[networks_of(args)[0]]
     # the regions vote behind --smooth and in front of --temperature, which tempers the FINAL probabilities; the sieve is last
     stages = tuple((name, cfg) for name, cfg in (('smooth', smooth_of(args)), ('superpixel', superpixel_of(args)),
+                                                 ('region_graph', region_graph_of(args, len(networks_of(args)))),
                                                  ('temper', temperature), ('sieve', sieve_of(args))) if cfg is not None)
     if together:
         return Plan(False, tta, tag, stages, PRINT, LAST)
@@ -293,7 +302,7 @@ def plan(args, has_test, noise=0.0):
 def build_stages(todo, job, args, fit=None):
     """the ``scene_report`` stages of ``Plan.stages``; ``fit``: the (rows, truth) on the device that --temperature fit fits on"""
     make = dict(smooth=smooth_stage, superpixel=lambda sp: superpixel_stage(sp, job, args.save_segments),
-                temper=lambda T: temper_stage(None if T == 'fit' else T, fit), sieve=sieve_stage)
+                region_graph=region_graph_stage, temper=lambda T: temper_stage(None if T == 'fit' else T, fit), sieve=sieve_stage)
     return [make[name](cfg) for name, cfg in todo]
 
 
@@ -411,6 +420,7 @@ def build_parser():
                              "geometry; the Result: tag becomes _tta_flips / _tta_d4")
     add_smooth_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both)')
     add_superpixel_flags(parser, 'the prediction of --net (with or without --tta, behind --smooth; not with both / ema_both)')
+    add_region_graph_flags(parser, 'the prediction of --net (not with both / ema_both)')
     add_sieve_flags(parser, 'the prediction of --net (with or without --tta; not with both / ema_both, not with --entropy)')
     parser.add_argument('--reliability', action='store_true',
                         help='behind every Result: block one line Reliability<tag>: ECE, MCE, NLL, Brier score, mean confidence '

@@ -1,6 +1,6 @@
 """Whole-scene prediction and its report, under ``train.py`` (the end of a run) and ``predict.py``: one scene record
 (``SceneJob``), a first prediction (``ensemble_first`` / ``tta_first``), the stages behind it (``smooth_stage``,
-``superpixel_stage``, ``temper_stage``, ``sieve_stage``) and one runner (``run_scene``: the scene opened, then ``run_stages``), which owns the
+``superpixel_stage``, ``region_graph_stage``, ``temper_stage``, ``sieve_stage``) and one runner (``run_scene``: the scene opened, then ``run_stages``), which owns the
 tags of the ``Result:`` blocks, what every step hands on and what becomes of the first block; ``evaluate_whole`` beside it."""
 import time
 from collections import namedtuple
@@ -18,6 +18,7 @@ NET_TAGS = {0: '', 1: '1', 'ema0': '_ema', 'ema1': '_ema1',      # evaluate_whol
             'tta': '_tta'}                                         # tta_first: over noisy views of every pixel
 SMOOTH_TAG = '_smooth'                                             # smooth_stage: appended to the tag of what it smooths
 SP_TAG = '_sp'                                                     # superpixel_stage: appended to the tag of what votes
+RG_TAG = '_rg'                                                     # region_graph_stage: appended to the tag of the vote it diffuses
 TEMPER_TAG = '_T'                                                  # temper_stage: appended to the tag of what it tempers
 SIEVE_TAG = '_sv'                                                  # sieve_stage: appended to the tag of the map it sieves
 PRINT, SCORE, SILENT = 'print', 'score', 'silent'                  # run_stages: what happens to the first prediction's block
@@ -42,9 +43,10 @@ class SceneJob(NamedTuple):
 # seconds and the number of networks), ``tag`` that of its ``Result:`` lines, ``noun`` who asks for the scene cube.  A further stage:
 # ``call(result, cube, want)`` on the result in front of it, ``timing`` a format of the seconds, ``suffix`` what its lines append
 # to the running tag, ``noun`` as above (None: nobody new asks), ``scored`` False: its probabilities are those of the stage in front
-# -- it moves labels only --, so ``score`` is not called behind its block
+# -- it moves labels only --, so ``score`` is not called behind its block; ``scene`` True: ``call(result, cube, want, spectra,
+# models)`` -- the stage also reads the scene's spectra and the member models
 First = namedtuple('First', 'predict timing tag noun', defaults=("the ensemble",))
-Stage = namedtuple('Stage', 'timing suffix call noun scored', defaults=(None, True))
+Stage = namedtuple('Stage', 'timing suffix call noun scored scene', defaults=(None, True, False))
 SieveOut = namedtuple('SieveOut', 'labels probs conf entropy stats')
 
 
@@ -188,6 +190,30 @@ def superpixel_stage(sp, job, save_segments=None):
                  (S, m, T, G, vote, ', connected' if sp.connect else ''), SP_TAG, call, "the superpixel vote")
 
 
+def region_graph_stage(cfg):
+    """the stage DIRECTLY behind the superpixel stage: the regions that voted become the nodes of a label propagation
+    (``cfg``: a cmlpl_amd.regiongraph.RegionGraph; region_graph + region_propagate) -- every region is described by the
+    embedding of its mean spectrum under member ``cfg.net``, linked to its most similar and to its adjacent regions, and the
+    vote's probabilities are the prior that diffuses.  One line ``region graph: nodes= knn= adj= edges= max_in_degree=
+    truncated= unreached= residual=`` (truncated: regions that touch more than ``adj`` others)."""
+    from cmlpl_amd.regiongraph import region_graph, region_propagate
+    cfg = cfg.check()
+
+    def call(res, cube, want, spectra, models):
+        if getattr(res, 'seg_probs', None) is None or getattr(res, 'segments', None) is None:
+            raise SystemExit("the region graph stands directly behind the superpixel vote")
+        rows, cols = cube.shape[0], cube.shape[1]
+        ids, M = (res.segments.seg, res.segments.N) if res.connected is None else (res.connected, res.M)
+        rg = region_graph(ids, M, rows, cols, spectra, list(models), cfg)
+        out = region_propagate(rg, res.seg_probs, cfg, **stage_want(want))
+        print('region graph: nodes=%d knn=%d adj=%d edges=%d max_in_degree=%d truncated=%d unreached=%d residual=%.3e' %
+              (M, cfg.k, cfg.adj, rg.graph.edges(), rg.graph.max_in_degree(), int((rg.adjacency.deg > cfg.adj).sum()),
+               int((out.regions.labels < 0).sum()), float(out.regions.residual.cpu()[0])))
+        return out
+    return Stage('region graph time == %%.3f s (member %d, %d kNN + %d adjacent neighbours, alpha %g, gamma %d, %d iterations)' %
+                 (cfg.net, cfg.k, cfg.adj, cfg.alpha, cfg.gamma, cfg.iters), RG_TAG, call, "the region graph", True, True)
+
+
 def temper_stage(T, fit=None):
     """the stage that tempers the probabilities in front of it (cmlpl_amd.calibrate.temper_probs).  ``T`` None: fitted first,
     on the pixels ``fit`` = (rows, truth) on the device"""
@@ -225,7 +251,8 @@ def sieve_stage(sv):
 
 
 def run_stages(first, stages, cube, spectra, models, job, first_block=PRINT, want=None, score=None):
-    """``first`` = (predict, timing, tag), then ``stages`` = [(timing, suffix, call), ..], each on the result in front of it.
+    """``first`` = (predict, timing, tag), then ``stages`` = [(timing, suffix, call), ..], each on the result in front of it
+    (a ``Stage`` with ``scene`` also takes the spectra and the models).
     Per step: the library call, the copy to the host, the timing line, the ``Result:`` block (when ``job`` has the test pixels)
     under the RUNNING tag -- ``first``'s, plus the suffix of every stage so far --, then ``score(tag, result)`` (a ``RelScore``; not behind a stage that is not ``scored``).
     ``want`` (probs / conf / entropy: the caller's wishes) goes to the LAST step; every step in front of it is asked for its
@@ -240,7 +267,7 @@ def run_stages(first, stages, cube, spectra, models, job, first_block=PRINT, wan
     for i, ((timing, suffix, call, *more), ask) in enumerate(zip(steps, asked)):
         tag += suffix
         t1 = time.time()
-        res = call(res, cube, ask)
+        res = call(res, cube, ask, spectra, models) if len(more) > 2 and more[2] else call(res, cube, ask)
         out = {k: v.cpu().numpy() for k, v in zip(OUTPUTS, res[:4]) if v is not None}
         print(timing % ((time.time() - t1, len(models)) if i == 0 else time.time() - t1))
         if job.test_array is not None and (i > 0 or first_block == PRINT):

@@ -44,6 +44,13 @@ Differences from the reference that are deliberate, MI355X-first choices:
     regions that vote are CONNECTED -- detached fragments of fewer than S S / 4 pixels join the largest region they touch and
     every remaining component is a segment of its own (cmlpl_amd.regions.connect_segments); the ``superpixel:`` line then
     describes that map and a line ``superpixel connectivity: components_before= fragments_merged= segments=`` follows it.
+  * ``--region_graph`` (``--rg_k K``, ``--rg_adj A``, ``--rg_alpha a``, ``--rg_gamma g``, ``--rg_iters T``, ``--rg_net i``), with
+    ``--superpixel S``: the regions that voted become the nodes of a label propagation -- every region is described by the
+    embedding of its mean spectrum under member i, linked to its K most similar and its A adjacent regions (by shared
+    boundary length), and the vote is the prior that diffuses (cmlpl_amd.regiongraph).  One ``region graph:`` line (nodes, knn,
+    adj, edges, max_in_degree, truncated, unreached, residual) and one more ``Result:`` block (``OA_ens_sp_rg``; behind
+    ``--smooth``: ``OA_ens_smooth_sp_rg``).  One GPU.  The run itself is untouched and no checkpoint records the flag.  The
+    defaults are not tuned.
   * ``--sieve N`` (``--sieve_conn 4 | 8``, ``--sieve_passes T``): after the run the label map of Base and Base1 together --
     behind ``--smooth`` and ``--superpixel`` when given -- is SIEVED: a connected region of fewer than N pixels takes the label
     of the largest region of at least N pixels that it touches (cmlpl_amd.regions; the operation GDAL calls sieve).  One
@@ -96,7 +103,7 @@ import torch
 from cmlpl_amd import HyperParams, NetShape, checkpoint
 from hsi_loader import HSIDataSet, SyntheticHSIDataSet, SyntheticScene
 from scene_report import (NET_TAGS, PRINT, SILENT, SMOOTH_TAG, SP_TAG, RelScore, SceneJob, build_nets, calibration_split,  # noqa: F401
-                          ensemble_first, evaluate_whole, run_scene, sieve_stage, smooth_stage, superpixel_stage, tta_first, tta_tag, tta_timing)
+                          ensemble_first, evaluate_whole, region_graph_stage, run_scene, sieve_stage, smooth_stage, superpixel_stage, tta_first, tta_tag, tta_timing)
 
 DATASETS = {1: (9, 103), 2: (16, 204), 3: (15, 144), 4: (16, 200)}     # num_classes, num_features (train.py:75-90)
 SYNTH = {"B2": (103, 11, 11, 103, 9), "P": (60, 20, 20, 103, 9), "B4": (200, 11, 11, 200, 16),
@@ -163,12 +170,12 @@ def run_record(args, hp, shape, from_scene):
 def saved_args(args):
     """the command line as a checkpoint keeps it: a flag that came after the format (--method, --ema, --ensemble, --tta, --smooth and
     its sub-flags, --aug_spatial, --tta_spatial, --pl_stats, --save_pl, --reliability, --knn, --knn_T, the optimiser flags) is left out at its default, so a file written without it is byte for byte what it
-    was before the flag existed; --propagate, --superpixel, --sieve and their sub-flags only add lines behind the run and are never recorded"""
+    was before the flag existed; --propagate, --superpixel, --region_graph, --sieve and their sub-flags only add lines behind the run and are never recorded"""
     late = {'method': 'cmlpl', 'ema': False, 'ensemble': False, 'tta': False, **{k: None for k in SMOOTH_FLAGS},
             'aug_spatial': 'none', 'tta_spatial': 'none', 'pl_stats': False, 'save_pl': None, 'reliability': False,
             'knn': None, 'knn_T': None, **OPTIM_FLAGS}
     return {k: v for k, v in vars(args).items() if not (k in late and v == late[k]) and k not in LP_FLAGS and k not in SP_FLAGS
-            and k not in SIEVE_FLAGS}
+            and k not in SIEVE_FLAGS and k not in RG_FLAGS}
 
 
 LP_FLAGS = ('propagate', 'lp_k', 'lp_alpha', 'lp_gamma', 'lp_iters')     # --propagate: cmlpl_amd.labelprop.LabelProp's fields
@@ -399,6 +406,45 @@ def sieve_of(args):
     except ValueError as e:
         raise SystemExit("--sieve: %s" % str(e).replace("Sieve: ", ""))
     return sv
+
+
+RG_FLAGS = ('region_graph', 'rg_k', 'rg_adj', 'rg_alpha', 'rg_gamma', 'rg_iters', 'rg_net')    # cmlpl_amd.regiongraph.RegionGraph's fields
+
+
+def add_region_graph_flags(parser, what):
+    """``--region_graph`` and its sub-flags (train.py and predict.py); every sub-flag's default is None: the flag was not given"""
+    parser.add_argument('--region_graph', action='store_const', const=True, default=None,
+                        help='--superpixel: the regions that voted become the nodes of a label propagation over their most '
+                             'similar (embedding of the mean spectrum) and their adjacent regions, the vote is its prior: one '
+                             'region graph: line and one more Result: block, tag ..._rg, for %s' % what)
+    parser.add_argument('--rg_k', type=int, default=None, metavar='K', help='--region_graph: kNN neighbours per region (default 8, 0 .. 32)')
+    parser.add_argument('--rg_adj', type=int, default=None, metavar='A',
+                        help='--region_graph: adjacent regions per region, by shared boundary length (default 8, 0 .. 16; K + A 1 .. 32)')
+    parser.add_argument('--rg_alpha', type=float, default=None, metavar='a',
+                        help='--region_graph: the share a region takes from its neighbours per iteration (default 0.5, 0 <= a < 1)')
+    parser.add_argument('--rg_gamma', type=int, default=None, metavar='G', help='--region_graph: an edge weighs similarity^G (default 3, 1 .. 8)')
+    parser.add_argument('--rg_iters', type=int, default=None, metavar='T', help='--region_graph: iterations (default 20, 1 .. 10000)')
+    parser.add_argument('--rg_net', type=int, default=None, metavar='I',
+                        help='--region_graph: the member whose embedding describes the regions (default 0, the first)')
+
+
+def region_graph_of(args, members=None):
+    """the ``cmlpl_amd.regiongraph.RegionGraph`` of the command line, or None without ``--region_graph``; what it cannot mean
+    is a SystemExit before anything is loaded.  ``members``: how many networks predict together (``--rg_net`` names one)"""
+    given = [k for k in RG_FLAGS[1:] if getattr(args, k, None) is not None]
+    if getattr(args, 'region_graph', None) is None:
+        if given:
+            raise SystemExit("%s belong%s to --region_graph" % (" / ".join("--" + k for k in given), "s" if len(given) == 1 else ""))
+        return None
+    if getattr(args, 'superpixel', None) is None:
+        raise SystemExit("--region_graph belongs to --superpixel S: its nodes are the regions that vote")
+    from cmlpl_amd.regiongraph import RegionGraph
+    cfg = RegionGraph(**{'adj' if k == 'rg_adj' else k[3:]: getattr(args, k) for k in given})
+    try:
+        cfg.check(members)
+    except ValueError as e:
+        raise SystemExit("--region_graph: %s" % str(e).replace("RegionGraph: ", ""))
+    return cfg
 
 
 def load_data(run, args):
@@ -784,8 +830,10 @@ def report(run, args):
         run_scene(job, nets[:2], tta_first(TTA(args.m, args.noise, spatial=args.tta_spatial)), first_block=PRINT, score=score)
     # --smooth, then --superpixel behind the smoothed block (else behind the pair's, which is not printed again)
     sv = sieve_of(args)                                              # --sieve: LAST, a temperature never moves a label
+    rg = region_graph_of(args, 2)                                    # --region_graph: directly behind the vote it diffuses
     stages = ([smooth_stage(run.smooth)] if run.smooth is not None else []) + \
         ([superpixel_stage(run.sp, job, args.save_segments)] if run.sp is not None else []) + \
+        ([region_graph_stage(rg)] if rg is not None else []) + \
         ([sieve_stage(sv)] if sv is not None else [])
     if stages:
         run_scene(job, nets[:2], ensemble_first(), stages, first_block=SILENT, score=score)
@@ -823,6 +871,9 @@ def main(args, make_engine=None, device=None):
         raise SystemExit(f"--superpixel runs on one GPU (this job has {world} ranks)")
     if sp is not None and args.no_eval:
         raise SystemExit("--superpixel belongs to the end-of-run report: not with --no_eval")
+    rg = region_graph_of(args, 2)
+    if rg is not None and world > 1:
+        raise SystemExit(f"--region_graph runs on one GPU (this job has {world} ranks)")
     sv = sieve_of(args)
     if sv is not None and world > 1:
         raise SystemExit(f"--sieve runs on one GPU (this job has {world} ranks)")
@@ -970,6 +1021,7 @@ def build_parser():
                         help='with an optimiser flag on: write [num_steps][5] = lr, norm, norm1, coef, coef1 of every step as .npy')
     add_smooth_flags(parser, 'Base and Base1 together after the run')
     add_superpixel_flags(parser, 'Base and Base1 together after the run (behind --smooth when given; one GPU)')
+    add_region_graph_flags(parser, 'Base and Base1 together after the run (behind --superpixel; one GPU)')
     add_sieve_flags(parser, 'Base and Base1 together after the run (one GPU)')
     parser.add_argument('--synthetic', choices=sorted(SYNTH), default=None,
                         help='run on seeded synthetic patches of this shape (datasets are not shipped)')
